@@ -9,7 +9,8 @@ used only for the barrier and the max over ranks of the timed region).
 Prints ONE JSON line on rank 0:
   value / ms_per_step   EXACTLY --steps pairs between two barriers, nothing but submit / wait in the timed region; before it
                         --warmup pairs per slot and at least 600 pairs in all run untimed (`warmup_pairs_run`), so that the
-                        device clocks have followed the load;
+                        device clocks have followed the load.
+A plain run stops there (--dump-outputs DIR: what the last timed pair returned, as DIR/<name>.npy).  --full adds:
   kernels               per-kernel device time, HIP events on the library's own stream, measured AFTER the timed region
                         on pairs run one at a time (what a rocprofv3 trace of `--streams 1` reproduces, profiles/);
   roofline(_fp64)       the dominant kernel of that pass against HBM (the metric asks for it) and against the FP64
@@ -128,6 +129,33 @@ def pmc_traffic(kernel_id, toed_mode):
             return None
         total += hit[0]["hbm_bytes_per_launch"]
     return total
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def write_outputs(dir_, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float64 (exact for the integer lists and flags)."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(dir_, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dir_, k + ".npy"), a)
+
+
+def pair_outputs(ctx, slot, with_sims):
+    """What a caller of the timed path receives for the slot's finished pair (ebvo_stereo_fetch_begin / _end): both edge
+    lists, the candidate CSR, best score and keep flag per pair, and the four scores when the pipeline stores them."""
+    from edge_based_visual_odometry_amd import _lib
+    ctx.stereo_fetch_begin(slot=slot, what=_lib.FETCH_ALL if with_sims else _lib.FETCH_DEFAULT)
+    out = ctx.stereo_fetch_end(slot=slot)
+    arrays = {f"{side}_{f}": out[side][f] for side in ("left", "right") for f in ("x", "y", "theta", "index")}
+    arrays.update((k, out[k]) for k in ("row_ptr", "col_idx", "best", "keep"))
+    if with_sims:
+        arrays["sims"] = out["sims"]
+    return arrays
 
 
 def xyi_hash(edges) -> str:
@@ -695,10 +723,27 @@ def sequence_bench(args, wl, H, W, F, device, rank, world, dist, reduce_device):
         totals["kept"] += tc["n_kept"]
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # the timed loop fetches no arrays (fetch=False): its caller receives the counts of every stage, here the last frame's
+        write_outputs(args.dump_outputs, {**{f"frame_{k}": [getattr(c, k)] for k in ("n_left", "n_right", "n_pairs", "n_matches")},
+                                          **{f"chain_{k}": [v] for k, v in fc.items()},
+                                          **{f"temporal_{k}": [v] for k, v in tc.items()}})
     per_rank = sharding.gather_over_ranks(args.steps / dt, dist, reduce_device)
     dt = sharding.max_over_ranks(dt, dist, reduce_device)
-    prof = None
     if rank == 0:
+        result = {
+            "metric": f"stereo frames/sec (undistort + TOED + stereo chain + temporal NCC) on {wl['cfg']} {W}x{H}; achieved HBM GB/s",
+            "value": sharding.job_throughput(world, args.steps, dt), "unit": "stereo frames/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "per_rank_frames_per_s": per_rank,
+            **sharding.rank_balance(per_rank, world, sharding.job_throughput(world, args.steps, dt)),
+            "config": {"workload": wl["label"], "shape": f"{W}x{H}", "toed_mode": args.toed_mode,
+                       "per_step_averages": {k: v / args.steps for k, v in totals.items()},
+                       "parallelism": f"{world} independent sequence(s), one per GPU, no collective"},
+        }
+    prof = None
+    if args.full and rank == 0:
         ctx.profile_reset()
         ctx.profile_enable(True, every=1)
         for k in range(min(4, n_frames)):
@@ -731,18 +776,10 @@ def sequence_bench(args, wl, H, W, F, device, rank, world, dist, reduce_device):
             threaded[str(T)] = threaded_sequence(T, args, H, W, F, device, frames, calib, cal, min(args.steps, 64))
         alg_bytes = algorithmic_bytes_per_pair(H, W, c.n_left, c.n_right, c.n_pairs)
         dom_s = kernels[dom]["ms_per_step"] * 1e-3 / max(1.0, kernels[dom]["launches_per_step"])
-        result = {
-            "metric": f"stereo frames/sec (undistort + TOED + stereo chain + temporal NCC) on {wl['cfg']} {W}x{H}; achieved HBM GB/s",
-            "value": sharding.job_throughput(world, args.steps, dt), "unit": "stereo frames/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "per_rank_frames_per_s": per_rank,
-            **sharding.rank_balance(per_rank, world, sharding.job_throughput(world, args.steps, dt)),
-            "config": {"workload": wl["label"], "shape": f"{W}x{H}", "toed_mode": args.toed_mode,
-                       "edges_left": c.n_left, "edges_right": c.n_right, "candidate_pairs": c.n_pairs, "ncc_matches": c.n_matches,
-                       "final_stereo_mates": fc["n_final"], "temporal_candidate_quads": tc["n_candidates"],
-                       "temporal_quads_kept": tc["n_kept"], "per_step_averages": {k: v / args.steps for k, v in totals.items()},
-                       "parallelism": f"{world} independent sequence(s), one per GPU, no collective"},
+        result["config"].update(edges_left=c.n_left, edges_right=c.n_right, candidate_pairs=c.n_pairs, ncc_matches=c.n_matches,
+                                final_stereo_mates=fc["n_final"], temporal_candidate_quads=tc["n_candidates"],
+                                temporal_quads_kept=tc["n_kept"])
+        result.update({
             "roofline": {"bound": "hbm", "kernel": dom, "achieved": alg_bytes / dom_s / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": alg_bytes / dom_s / 1e9 / HBM_PEAK_GBS, "traffic": None,
                          "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": dom_s * 1e3,
@@ -759,7 +796,7 @@ def sequence_bench(args, wl, H, W, F, device, rank, world, dist, reduce_device):
             "full_temporal_chain_note": "64 frames behind an untimed pass over the 16 slots: the same frame loop with the rest of get_Temporal_Edge_Pairs_from_Quads after the NCC "
                                         "filter (SIFT filter, Best-Nearly-Best on NCC and SIFT scores, photometric refinement "
                                         "of both cameras, edge clustering): %d final quads per frame" % tcf["n_final"],
-        }
+        })
         if not args.no_verify:
             problems, what = verify_sequence_frame(ctx, frames, min(3, n_frames - 1), params, calib, cal, H, W, F)
             result["verified"] = not problems
@@ -773,6 +810,7 @@ def sequence_bench(args, wl, H, W, F, device, rank, world, dist, reduce_device):
                                                       "for bit against the CPU oracle (tests/oracle_chain.py)")
             if problems:
                 result["verification_failures"] = problems
+    if rank == 0:
         print(json.dumps(result))
         if result.get("verified") is False:
             ctx.close()
@@ -812,7 +850,16 @@ def main():
     ap.add_argument("--host-threads", default="",
                     help="e.g. 2,4,8: also run the frame loops (euroc: the sequence; kitti / eth3d: the one-pass drop-in) in that "
                          "many host threads, one context each -- extra keys of the JSON line, never `value`")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, everything else the line can hold: the short-warmup and sustained rates, the "
+                         "result checks, the ingest and transfer loops, per-kernel times and rooflines, the CPU baseline (the "
+                         "--no-* options and --host-threads shape this part).  Without it: set up, warm up, time --steps, print")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy "
+                         "(float64; rank 0's sequence)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # ---- N > 1 without a launcher: this process becomes the launcher (before it has touched the GPU or loaded the HIP
     # library) -- N fresh child processes, one per GPU, each re-entering main() with RANK / WORLD_SIZE set ---------------
@@ -917,13 +964,18 @@ def main():
             done_ += 1
         return time.perf_counter() - t_, c_
 
-    # first the protocol as the command line states it (--warmup W pairs per slot, then K pairs timed; rank-local, no barrier):
-    # `value_short_warmup` next to `value`, so that the two protocols can be compared in one record
     n_short = max(1, args.warmup) * nslots
-    run_pairs(n_short)
-    t_short, counts = run_pairs(args.steps)
-    if n_warm > n_short + args.steps:
-        _, counts = run_pairs(n_warm - n_short - args.steps)
+    if args.full:
+        # first the protocol as the command line states it (--warmup W pairs per slot, then K pairs timed; rank-local, no
+        # barrier): `value_short_warmup` next to `value`, so that the two protocols can be compared in one record
+        run_pairs(n_short)
+        t_short, counts = run_pairs(args.steps)
+        if n_warm > n_short + args.steps:
+            _, counts = run_pairs(n_warm - n_short - args.steps)
+        n_warm_run = max(n_warm, n_short + args.steps)
+    else:
+        run_pairs(n_warm)
+        n_warm_run = n_warm
 
     def barrier():
         torch.cuda.synchronize()
@@ -957,15 +1009,18 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     graph_pairs = ctx.graph_launches - graphs_before   # timed pairs whose 18 launches went out as one hipGraphLaunch
-    # the sustained rate: 300 pairs more, rank-local, straight after the timed region (the same loop)
-    t_sus, _ = run_pairs(300)
-    t_sus_full = None
-    if not args.store_sims:                          # ... and with the four similarities stored (round 3's pipeline), for comparison
-        saved, params = params, params_full
-        run_pairs(4 * nslots)                        # (a new flag is a new graph: three submissions per slot)
-        t_sus_full, _ = run_pairs(300)
-        params = saved
-        run_pairs(4 * nslots)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, pair_outputs(ctx, last_slot, args.store_sims))
+    t_sus = t_sus_full = None
+    if args.full:
+        # the sustained rate: 300 pairs more, rank-local, straight after the timed region (the same loop)
+        t_sus, _ = run_pairs(300)
+        if not args.store_sims:                      # ... and with the four similarities stored (round 3's pipeline), for comparison
+            saved, params = params, params_full
+            run_pairs(4 * nslots)                    # (a new flag is a new graph: three submissions per slot)
+            t_sus_full, _ = run_pairs(300)
+            params = saved
+            run_pairs(4 * nslots)
     per_rank = sharding.gather_over_ranks(args.steps / dt, dist, reduce_device)
     dt = sharding.max_over_ranks(dt, dist, reduce_device)
     rank_cpu_counts = [len(c) for c in sharding.gather_int_lists(sorted(os.sched_getaffinity(0)), 1024, dist, reduce_device)]
@@ -973,7 +1028,7 @@ def main():
     # ---- what the timed region produced (every rank checks its own sequence) ---------------------------------
     problems = []
     out = None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         if len(seen) != 1:
             problems.append(f"counts changed between steps of the timed region: {sorted(seen)}")
         if not args.store_sims:                     # the same pair once more with all four similarities stored
@@ -993,7 +1048,7 @@ def main():
 
     # ---- the same pairs/s with every pair's images arriving from host memory (second key; every rank, same barriers) -----
     ingest = None
-    if not args.no_ingest:
+    if args.full and not args.no_ingest:
         ring = [tuple(np.ascontiguousarray(im) for im in synth.stereo_pair("s2", H, W, scene=seq["scene"], noise_base=seq["noise_base"] + 10 * k,
                                                                             disparity=seq["disparity"])) for k in range(4)]
         for pair in ring:                                   # the caller's frame ring, page-locked once
@@ -1046,7 +1101,7 @@ def main():
 
     # ---- per-kernel device time, pairs one at a time, HIP events around every kernel (outside the timed region) -
     prof = None
-    if rank == 0:
+    if args.full and rank == 0:
         ctx.profile_reset()
         ctx.profile_enable(True, every=1)
         for _ in range(min(8, max(1, args.steps))):
@@ -1070,7 +1125,7 @@ def main():
 
     # ---- PCIe-inclusive loops (never `value`) -------------------------------------------------------------------
     legs = None
-    if rank == 0 and world == 1 and not args.no_transfer_legs:
+    if args.full and rank == 0 and world == 1 and not args.no_transfer_legs:
         pool = [synth.stereo_pair("s2", H, W, scene=seq["scene"], noise_base=seq["noise_base"] + 10 * k,
                                   disparity=seq["disparity"]) for k in range(4)]
         from edge_based_visual_odometry_amd import _lib as L_
@@ -1151,6 +1206,32 @@ def main():
             ctx.stereo_upload(left, right, slot=k)
 
     if rank == 0:
+        result = {
+            "metric": "stereo pairs/sec (TOED+NCC match) on KITTI 1241\u00d7376; achieved HBM GB/s",   # BASELINE.json's string
+            "value": sharding.job_throughput(world, args.steps, dt),
+            "unit": "stereo pairs/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "warmup_pairs_run": n_warm_run, "warmup_overridden": n_warm > n_short,
+            "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f64", "data": "synthetic",
+            "per_rank_pairs_per_s": per_rank,
+            **sharding.rank_balance(per_rank, world, sharding.job_throughput(world, args.steps, dt)),
+            "rank_cpus": rank_cpu_counts,
+            "config": {"workload": wl["label"], "shape": f"{W}x{H}",
+                       "toed_mode": args.toed_mode,
+                       "edges_left": counts.n_left, "edges_right": counts.n_right,
+                       "candidate_pairs": counts.n_pairs, "ncc_matches": counts.n_matches,
+                       "sims_stored": bool(args.store_sims),
+                       "pairs_in_flight_per_gpu": nslots,
+                       "streams_per_gpu": nslots if nslots < 4 else min(4, nslots - 1),
+                       "pairs_submitted_as_hipgraph": graph_pairs, "toed_strict_fallbacks": ctx.toed_fallbacks,
+                       "parallelism": f"{world} independent sequence(s), one per GPU, no collective"},
+        }
+        if args.workload != "kitti":
+            result["metric"] = f"stereo pairs/sec (TOED+NCC match) on {wl['cfg']} {W}x{H}; achieved HBM GB/s"
+
+    if args.full and rank == 0:
         n_ser = max(1, prof["cand_count"][1])                   # (one launch of the counting pass per pair)
         kernels = {k: {"ms_per_step": v[0] / n_ser, "launches_per_step": v[1] / n_ser} for k, v in prof.items() if v[1]}
         dom = dom_name
@@ -1183,33 +1264,13 @@ def main():
             fp64_peak, fp64_bound = 4 * FP64_VALU_PEAK_NOFMA_TF, "valu_fp32_fma"   # 157 TFLOP/s: FP32 vector FMA (MI355X_MICROARCH.md)
         else:
             ops, executed, ops_note = None, None, "not an fp64-ALU kernel"
-        result = {
-            "metric": "stereo pairs/sec (TOED+NCC match) on KITTI 1241\u00d7376; achieved HBM GB/s",   # BASELINE.json's string
-            "value": sharding.job_throughput(world, args.steps, dt),
-            "unit": "stereo pairs/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "warmup_pairs_run": max(n_warm, n_short + args.steps), "warmup_overridden": n_warm > n_short,
+        result["config"]["toed_candidates"] = n_cand if args.toed_mode == "hybrid" else None
+        result.update({
             "value_short_warmup": args.steps / t_short, "value_sustained_300": 300 / t_sus,
             "value_sustained_300_sims_stored": None if t_sus_full is None else 300 / t_sus_full,
             "warmup_note": f"value: {args.steps} pairs timed after {max(n_warm, n_short + args.steps)} untimed ones (the device clocks follow "
                            f"the load with a delay); value_short_warmup: the same {args.steps} pairs timed after --warmup x slots = "
                            f"{n_short} pairs only (this rank, no barrier); value_sustained_300: 300 pairs straight after the timed region",
-            "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "per_rank_pairs_per_s": per_rank,
-            **sharding.rank_balance(per_rank, world, sharding.job_throughput(world, args.steps, dt)),
-            "rank_cpus": rank_cpu_counts,
-            "config": {"workload": wl["label"], "shape": f"{W}x{H}",
-                       "toed_mode": args.toed_mode,
-                       "edges_left": counts.n_left, "edges_right": counts.n_right,
-                       "toed_candidates": n_cand if args.toed_mode == "hybrid" else None,
-                       "candidate_pairs": counts.n_pairs, "ncc_matches": counts.n_matches,
-                       "sims_stored": bool(args.store_sims),
-                       "pairs_in_flight_per_gpu": nslots,
-                       "streams_per_gpu": nslots if nslots < 4 else min(4, nslots - 1),
-                       "pairs_submitted_as_hipgraph": graph_pairs, "toed_strict_fallbacks": ctx.toed_fallbacks,
-                       "parallelism": f"{world} independent sequence(s), one per GPU, no collective"},
             "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved_gbs, "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": achieved_gbs / HBM_PEAK_GBS, "traffic": pmc_traffic(dom, args.toed_mode),
                          "traffic_source": f"profiles/kernel_pmc_{args.toed_mode}.json (committed rocprofv3 PMC passes, "
@@ -1225,9 +1286,7 @@ def main():
                                  "reads longer (avg_launch_ms_every_stage_instrumented)."},
             "kernels": kernels,
             "kernel_groups": KERNEL_GROUPS[args.toed_mode],
-        }
-        if args.workload != "kitti":
-            result["metric"] = f"stereo pairs/sec (TOED+NCC match) on {wl['cfg']} {W}x{H}; achieved HBM GB/s"
+        })
         if ops is not None:
             tf = executed / dom_avg_s / 1e12               # operations the kernel EXECUTES (strict mode: after CSE)
             result["roofline_fp64"] = {"bound": fp64_bound, "kernel": dom, "achieved": tf,
@@ -1267,6 +1326,7 @@ def main():
             result["verified"] = not problems
             if problems:
                 result["verification_failures"] = problems
+    if rank == 0:
         print(json.dumps(result))
     elif problems:
         print(f"[rank {rank}] verification failed: {problems}", file=sys.stderr)

@@ -139,7 +139,7 @@ def test_all_ranks_ok_returns_zero(tmp_path):
 def test_bench_gpus_2_on_one_gpu_runs_the_hot_path_on_both_ranks():
     """Two ranks share the box's one GPU (gloo for the barrier: RCCL wants a device per rank); each owns its own sequence,
     rank 0 checks its pair's known answers and prints the job's line."""
-    out = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "5", "--warmup", "1", "--streams", "2",
+    out = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "5", "--warmup", "1", "--streams", "2", "--full",
                           "--no-cpu-baseline", "--no-transfer-legs"], env=_clean_env(), capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = _json_lines(out.stdout)
@@ -178,3 +178,21 @@ def test_rccl_reductions_of_the_bench_on_the_gpu(tmp_path):
         "print('rccl ok')\n")
     out = subprocess.run([sys.executable, str(prog)], env=_clean_env(), capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and "rccl ok" in out.stdout, out.stderr[-3000:]
+
+
+def test_dump_outputs_and_steps_argument(tmp_path):
+    """--dump-outputs writes float64 .npy files (integer lists exactly) under the 64 MB cap; --steps 0 is refused"""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_module_for_dump", BENCH)
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    b.write_outputs(str(tmp_path / "d"), {"col_idx": np.array([0, 7, 2**31 - 1], dtype=np.int32), "keep": np.array([1, 0], np.uint8)})
+    got = np.load(tmp_path / "d" / "col_idx.npy")
+    assert got.dtype == np.float64 and got.tolist() == [0, 7, 2**31 - 1]
+    assert np.load(tmp_path / "d" / "keep.npy").tolist() == [1.0, 0.0]
+    with pytest.raises(SystemExit):
+        b.write_outputs(str(tmp_path / "big"), {"x": np.zeros(b.DUMP_MAX_BYTES // 8 + 1)})
+    assert not (tmp_path / "big").exists()
+    out = subprocess.run([sys.executable, BENCH, "--steps", "0"], env=_clean_env(), capture_output=True, text=True, timeout=120)
+    assert out.returncode == 2 and "--steps" in out.stderr

@@ -5,7 +5,7 @@ set -u
 OUT=$1; BASE=$2; REPS=${3:-3}; shift; shift; shift || true
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$ROOT"
-ARGS="--steps 300 --warmup 10 --no-cpu-baseline --no-transfer-legs --no-ingest --no-verify $*"
+ARGS="--full --steps 300 --warmup 10 --no-cpu-baseline --no-transfer-legs --no-ingest --no-verify $*"
 echo "# python3 bench.py $ARGS   (A = $BASE, B = the tree's library), interleaved x $REPS" > "$OUT"
 for rep in $(seq 1 "$REPS"); do
   for which in A B; do

@@ -23,13 +23,13 @@ fi
 if [ "$PART" = "prof" ]; then ls -la "$EBVO_PROFILES_DST"; exit 0; fi
 # bench lines of the round (untraced)
 python3 bench.py --no-cpu-baseline --no-transfer-legs > /dev/null 2>&1   # the first run on a fresh box reads low (clocks)
-python3 bench.py > "$EBVO_PROFILES_DST/${TAG}_bench_kitti.json" 2> /dev/null
+python3 bench.py --full > "$EBVO_PROFILES_DST/${TAG}_bench_kitti.json" 2> /dev/null
 python3 bench.py --steps 20 --warmup 5 > "$EBVO_PROFILES_DST/${TAG}_bench_kitti_steps20.json" 2> /dev/null   # the driver's command line
-python3 bench.py --gpus 2 --steps 100 --no-cpu-baseline --no-transfer-legs > "$EBVO_PROFILES_DST/${TAG}_bench_kitti_2ranks_1gpu.json" 2> /dev/null
-python3 bench.py --streams 1 --no-cpu-baseline --no-transfer-legs > "$EBVO_PROFILES_DST/${TAG}_bench_kitti_1slot.json" 2> /dev/null
-python3 bench.py --toed-mode strict --no-cpu-baseline --no-transfer-legs > "$EBVO_PROFILES_DST/${TAG}_bench_kitti_strict.json" 2> /dev/null
-python3 bench.py --workload eth3d --no-cpu-baseline > "$EBVO_PROFILES_DST/${TAG}_bench_eth3d.json" 2> /dev/null
-python3 bench.py --workload euroc --steps 64 --warmup 4 > "$EBVO_PROFILES_DST/${TAG}_bench_euroc.json" 2> /dev/null
+python3 bench.py --full --gpus 2 --steps 100 --no-cpu-baseline --no-transfer-legs > "$EBVO_PROFILES_DST/${TAG}_bench_kitti_2ranks_1gpu.json" 2> /dev/null
+python3 bench.py --full --streams 1 --no-cpu-baseline --no-transfer-legs > "$EBVO_PROFILES_DST/${TAG}_bench_kitti_1slot.json" 2> /dev/null
+python3 bench.py --full --toed-mode strict --no-cpu-baseline --no-transfer-legs > "$EBVO_PROFILES_DST/${TAG}_bench_kitti_strict.json" 2> /dev/null
+python3 bench.py --full --workload eth3d --no-cpu-baseline > "$EBVO_PROFILES_DST/${TAG}_bench_eth3d.json" 2> /dev/null
+python3 bench.py --full --workload euroc --steps 64 --warmup 4 > "$EBVO_PROFILES_DST/${TAG}_bench_euroc.json" 2> /dev/null
 python3 tools/gpu_gn_ab.py > "$EBVO_PROFILES_DST/${TAG}_gn_layouts.txt" 2>&1
 python3 tools/gpu_pipeline_hosttime.py euroc > "$EBVO_PROFILES_DST/${TAG}_pipeline_hosttime.txt" 2>&1
 bash tools/gpu_stagewise_profile.sh 20 > "$EBVO_PROFILES_DST/${TAG}_stagewise_calls.txt" 2>&1
