@@ -685,7 +685,8 @@ class Context:
         profiler instruments one stage alone (index in profile_get()'s order + 1; 0 = every stage), 4 / 5 = launch layout
         of the refinements (1 = one thread per pair always / threshold of the eight-lanes layout); 10 = pair chain as a
         hipGraph; 11 / 12 / 17 = grids of the exact centre / mags / NCC tile kernels in blocks; 13 / 14 / 18 = A/B switches;
-        15 = bit mask of kernels launched twice, 16 = the chain ends after stage N (measurement only): include/ebvo_hip.h."""
+        15 = bit mask of kernels launched twice, 16 = the chain ends after stage N (measurement only): include/ebvo_hip.h.
+        A value outside the key's range raises EbvoError(EBVO_ERR_ARG) and changes nothing."""
         self._check(self.lib.ebvo_debug_set(self._ctx, key, value), "ebvo_debug_set")
 
     # -- profiling -----------------------------------------------------------------------------

@@ -4033,14 +4033,40 @@ extern "C" int ebvo_profile_get(ebvo_ctx *ctx, ebvo_kernel_time *out, int *n)
     return rc;
 }
 
+// the values each developer key accepts; anything else is refused before the context changes at all
+static bool debug_value_ok(int key, int value)
+{
+    switch (key)
+    {
+    case 4: case 7: case 10: case 13: case 14:
+        return value <= 1;
+    case 8:
+        return value == 2 || value == 3;
+    case 6:
+        return value >= 1;
+    case 11: case 12:
+        return value <= EBVO_DEBUG_MAX_EXACT_BLOCKS;
+    case 9:
+        return value <= EBVO_DEBUG_MAX_GN_BLOCKS;
+    case 18:
+        return value <= 512; // the smallest of the grids it divides: a larger divisor would launch zero blocks
+    case 19:
+        return value <= EBVO_TOTAL_PARTS;
+    case 0: case 1: case 2: case 3: case 5: case 15: case 16: case 17:
+        return true;
+    default:
+        return false;
+    }
+}
+
 extern "C" int ebvo_debug_set(ebvo_ctx *ctx, int key, int value)
 {
-    if (!ctx || value < 0)
+    if (!ctx || value < 0 || !debug_value_ok(key, value))
         return EBVO_ERR_ARG;
     ++ctx->graph_gen;
-    if (key == 10 && value <= 1)
+    if (key == 10)
         ctx->use_graphs = value; // the pair chain as a hipGraph (default) or as direct launches
-    else if (key == 14 && value <= 1)
+    else if (key == 14)
         ctx->no_prep = value;
     else if (key == 11 || key == 12)
         ctx->exact_blocks[key - 11] = value;
@@ -4052,9 +4078,9 @@ extern "C" int ebvo_debug_set(ebvo_ctx *ctx, int key, int value)
         ctx->ncc_blocks = value;
     else if (key == 18)
         ctx->small_div = value;
-    else if (key == 19 && value <= EBVO_TOTAL_PARTS)
+    else if (key == 19)
         ctx->cand_blocks = value;
-    else if (key == 13 && value <= 1)
+    else if (key == 13)
         ctx->ingest_stream = value;
     else if (key == 0)
         ctx->wait_attempts = value;
@@ -4064,24 +4090,22 @@ extern "C" int ebvo_debug_set(ebvo_ctx *ctx, int key, int value)
         ctx->lanes = value; // 0 = one stream per slot whatever their number
     else if (key == 3)
         ctx->prof_only = value - 1; // 0 = every stage; id + 1 = that stage alone: no event markers between the other kernels
-    else if (key == 4 && value <= 1)
+    else if (key == 4)
         ctx->gn_no_rows = value; // refinement launch layout (same bits either way, tests/test_gpu_refine.py)
     else if (key == 5)
         ctx->gn_rows_below = value;
     else if (key == 9)
         ctx->gn_persist_blocks = value;
-    else if (key == 8 && (value == 2 || value == 3))
+    else if (key == 8)
         ctx->gn_persist_waves = value;
-    else if (key == 7 && value <= 1)
+    else if (key == 7)
         ctx->gn_per_iteration_rows = value; // the stereo refinement's row layout as a launch per iteration (A/B and parity tests)
-    else if (key == 6 && value >= 1)
+    else // key 6
     {
         for (Slot *sl : ctx->slots) // test hook: the next temporal match of every slot finds its quad buffers too small
             if (sl->tq_cap > 0 && !sl->tq_in_flight)
                 sl->tq_cap = value;
     }
-    else
-        return EBVO_ERR_ARG;
     return EBVO_OK;
 }
 

@@ -102,6 +102,8 @@ struct ProfEvent
 constexpr int EBVO_CLEAR_MAX = 8;      // arrays one clear launch zeroes
 constexpr int EBVO_TOTAL_PARTS = 4096;  // most blocks the counting pass of the candidate search is launched with
 constexpr int EBVO_MATCH_PARTS = 4096; // most blocks ncc_tile_kernel is launched with
+constexpr int EBVO_DEBUG_MAX_EXACT_BLOCKS = 65536; // most blocks developer keys 11 / 12 accept (exact centre / mags grids)
+constexpr int EBVO_DEBUG_MAX_GN_BLOCKS = 1 << 20; // most workgroups developer key 9 accepts (persistent refinement launch)
 
 // Everything that belongs to one HIP stream: a stereo pair in flight (or the workspace of a host-buffer call).
 // What a captured pair chain (ebvo_stereo_submit) depends on besides the slot's buffers: every value a launch carries as an

@@ -714,20 +714,23 @@ int ebvo_profile_get(ebvo_ctx *ctx, ebvo_kernel_time *out /* EBVO_MAX_KERNELS */
  * key 4: 1 = the photometric refinements never use their eight-lanes-per-pair launch layout (0 = default: chosen per
  *        iteration from the number of active pairs); key 5: that threshold (0 = built-in).  Same bits either way.
  * key 7: 1 = the stereo refinement's eight-lanes layout as a launch per iteration instead of one persistent launch;
- * key 8: waves per SIMD the persistent launch is built for (2 or 3).  Same bits either way.
+ * key 8: waves per SIMD the persistent launch is built for (2 or 3); key 9: most workgroups of that launch (0 = the default,
+ *        1024; at most 1 << 20).  Same bits either way.
  * key 6: set the candidate-quad capacity of every slot's temporal stage to `value` (>= 1): the next ebvo_temporal_match
  *        finds more quads than its buffers hold and takes the regrow path.
  * key 10: 0 = ebvo_stereo_submit enqueues the pair as direct launches, 1 = as a captured hipGraph (default).
- * keys 11, 12: grid of toed_exact_centre / toed_exact_mags in blocks (0 = what the device keeps resident);
+ * keys 11, 12: grid of toed_exact_centre / toed_exact_mags in blocks (0 = what the device keeps resident; at most 65536);
  * key 13: 1 = ebvo_stereo_upload_async copies on the upload stream instead of the pull kernel; key 14: 1 = lines, boxes,
  *        sin / cos and row pairs as four launches instead of one; key 17: grid of ncc_tile_kernel in blocks (0 = resident);
  *        key 18: grids of decide / cand_scatter / candidates<fill> (512 / 512 / 4096 blocks) divided by `value` (0 = the
- *        default, 4); key 19: most blocks of candidates<count> (0 = the default, 1024).  Same bits either way (A/B switches).
+ *        default, 4; at most 512); key 19: most blocks of candidates<count> (0 = the default, 1024; at most 4096).  Same bits
+ *        either way (A/B switches).
  * key 15: bit mask -- an idempotent kernel of the resident pair's chain is launched TWICE (1 centre, 2 mags, 4 right bank,
  *        8 NCC tile): what one more launch costs the pair rate (tools/gpu_marginal_cost.py).
  * key 16: the resident pair's chain ENDS after stage `value` (0 = whole chain; the pair's record keeps the counts of the last
  *        whole run, the buffers behind the stage are stale): the pair rate of every prefix of the chain
- *        (tools/gpu_prefix_chain.py).  Measurement only. */
+ *        (tools/gpu_prefix_chain.py).  Measurement only.
+ * A negative value, an unknown key or a value outside the key's range returns EBVO_ERR_ARG and changes nothing. */
 int ebvo_debug_set(ebvo_ctx *ctx, int key, int value);
 
 /* Raw FP64 vector-ALU microbenchmark (mul + add, no FMA) used to anchor the compute roofline:
