@@ -1131,14 +1131,20 @@ extern "C" int ebvo_stereo_upload_slot(ebvo_ctx *ctx, int slot, const uint8_t *i
 {
     Slot *sp;
     int rc;
-    if (!img_left || !img_right || (rc = get_slot(ctx, slot, &sp)))
+    // every argument and the slot's state are checked before anything of the slot changes: a refused call leaves the
+    // resident pair, its results and the stage-wise tags as they were
+    if ((rc = get_slot(ctx, slot, &sp)))
+        return rc;
+    if (!img_left || !img_right)
         return EBVO_ERR_ARG;
-    EBVO_HIP(ctx, hipSetDevice(ctx->device));
     if ((rc = check_size(ctx, h, w)))
         return rc;
+    if (stride_left < w || stride_right < w)
+        return EBVO_ERR_ARG;
     Slot &s = *sp;
     if (s.in_flight || s.fin_in_flight || s.tq_in_flight)
         return EBVO_ERR_STATE;
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
     s.have_pair = s.have_run = s.have_refined = s.have_final = false; // results of the previous pair are gone
     s.have_push = false;
     if (slot == 0)
@@ -1174,10 +1180,15 @@ extern "C" int ebvo_stereo_upload_async(ebvo_ctx *ctx, int slot, const uint8_t *
 {
     Slot *sp;
     int rc;
-    if (!img_left || !img_right || (rc = get_slot(ctx, slot, &sp)))
+    // (validated in full before the slot's state changes, as in ebvo_stereo_upload_slot)
+    if ((rc = get_slot(ctx, slot, &sp)))
+        return rc;
+    if (!img_left || !img_right)
         return EBVO_ERR_ARG;
     if ((rc = check_size(ctx, h, w)))
         return rc;
+    if (stride_left < w || stride_right < w)
+        return EBVO_ERR_ARG;
     Slot &s = *sp;
     if (s.in_flight || s.fin_in_flight || s.tq_in_flight)
         return EBVO_ERR_STATE;
@@ -1188,8 +1199,6 @@ extern "C" int ebvo_stereo_upload_async(ebvo_ctx *ctx, int slot, const uint8_t *
     s.tq_final.n = -1;
     s.sift_left_valid = false;
     s.pull = false;
-    if (stride_left < w || stride_right < w)
-        return EBVO_ERR_ARG;
     if (!ctx->ingest_stream) // (the pull form makes no runtime call at all)
     {
         // pull form: both images entirely in page-locked memory the device can address?  Then the pair's own chain reads them
@@ -3688,10 +3697,12 @@ extern "C" int ebvo_temporal_fetch(ebvo_ctx *ctx, int slot, int32_t *row_ptr, in
     return EBVO_OK;
 }
 
-// the slot's page-locked result arena holds at least `bytes` (a re-allocation waits for copies still heading into the old one)
+// the slot's page-locked result arena holds at least `bytes` (a re-allocation waits for copies still heading into the old one).
+// It exists even for zero bytes: a selected array of a pair without edges or pairs is an empty array, not a NULL pointer
+// (NULL in a view means "not selected").
 static int ensure_arena(ebvo_ctx *ctx, Slot &s, size_t bytes)
 {
-    if (bytes <= s.h_arena_bytes)
+    if (bytes <= s.h_arena_bytes && s.h_arena)
         return EBVO_OK;
     if (s.fetch_pending)
         EBVO_HIP(ctx, hipEventSynchronize(s.ev_rebind));
@@ -3813,14 +3824,16 @@ __global__ __launch_bounds__(256) void pack_results_kernel(const ebvo_edge *__re
     for (int64_t i = t0; i < nL; i += stride)
     {
         const ebvo_edge e = L[i];
-        xyL[i] = make_double2(e.x, e.y);
+        if (xyL) // (a selection of orientations without (x, y) has no room for them: they would land on the orientations)
+            xyL[i] = make_double2(e.x, e.y);
         if (thL)
             thL[i] = e.theta;
     }
     for (int64_t i = t0; i < nR; i += stride)
     {
         const ebvo_edge e = R[i];
-        xyR[i] = make_double2(e.x, e.y);
+        if (xyR)
+            xyR[i] = make_double2(e.x, e.y);
         if (thR)
             thR[i] = e.theta;
     }
@@ -3896,6 +3909,11 @@ extern "C" int ebvo_stereo_fetch_compact_begin(ebvo_ctx *ctx, int slot, int what
         poff[k] = ptotal;
         ptotal += (psizes[k] + 63) & ~(size_t)63;
     }
+    // The staging below is fetch_pack, which also holds the block the chain of an EBVO_PAIR_PACK pair packed (one that asked
+    // for THETA without EBVO_PAIR_PUSH_THETA lands here).  That block is overwritten now, in this path's own layout, so the
+    // pair's later compact fetches take this path too instead of reading it with pack_layout.  (A staging buffer of its own
+    // would keep their one copy, but costs every slot another buffer of the capacity's size.)
+    s.have_pack = false;
     if (ptotal > s.fetch_pack.bytes && s.fetch_pending) // (re)allocation: the previous copies out of the old buffer must be over
         EBVO_HIP(ctx, hipEventSynchronize(s.ev_rebind));
     int rc;
@@ -3912,7 +3930,8 @@ extern "C" int ebvo_stereo_fetch_compact_begin(ebvo_ctx *ctx, int slot, int what
         // out of the staging buffer
         hipLaunchKernelGGL(pack_results_kernel, dim3(blocks), dim3(256), 0, ctx->copy_stream, (const ebvo_edge *)s.im[0].edges,
                            xy || th ? (int)nL : 0, (const ebvo_edge *)s.im[1].edges, xy || th ? (int)nR : 0,
-                           (const uint8_t *)s.keep.p, kb ? (int64_t)np : 0, (double2 *)(pk + poff[0]), (double2 *)(pk + poff[1]),
+                           (const uint8_t *)s.keep.p, kb ? (int64_t)np : 0, xy ? (double2 *)(pk + poff[0]) : nullptr,
+                           xy ? (double2 *)(pk + poff[1]) : nullptr,
                            th ? (double *)(pk + poff[2]) : nullptr, th ? (double *)(pk + poff[3]) : nullptr,
                            kb ? (uint32_t *)(pk + poff[4]) : nullptr);
         EBVO_HIP(ctx, hipGetLastError());

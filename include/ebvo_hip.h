@@ -618,7 +618,9 @@ int ebvo_stereo_upload_slot(ebvo_ctx *ctx, int slot, const uint8_t *img_left, co
  * engine, no second stream, no event.  The images must stay unchanged until the pair's ebvo_stereo_wait has returned, and
  * registered as long as the slot is submitted with them.  Images anywhere else (pageable memory) are copied into the slot's
  * own page-locked staging BEFORE the call returns -- the caller may free or overwrite them at once -- and go up from there on
- * the context's upload stream (ebvo_ingest_stats tells which form the calls took). */
+ * the context's upload stream (ebvo_ingest_stats tells which form the calls took).
+ * Both uploads check every argument (slot, pointers, size, both strides) and the slot's state before they touch it: a refused
+ * call leaves the slot's resident pair and its results as they were. */
 int ebvo_stereo_upload_async(ebvo_ctx *ctx, int slot, const uint8_t *img_left, const uint8_t *img_right, int h, int w,
                              ptrdiff_t stride_left, ptrdiff_t stride_right);
 /* page-lock / release caller memory (hipHostRegister / hipHostUnregister): no HIP header needed on the host side */
