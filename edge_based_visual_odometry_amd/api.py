@@ -583,11 +583,18 @@ class Context:
         self._check(self.lib.ebvo_temporal_set_keyframe(self._ctx, slot), "ebvo_temporal_set_keyframe")
 
     def temporal_match_submit(self, slot: int = 0, **kw):
-        """Enqueue the candidate + NCC stages of the slot's final mates against the keyframe (ebvo_temporal_match_submit)."""
+        """Enqueue the candidate + NCC stages of the slot's final mates against the keyframe (ebvo_temporal_match_submit).
+        kw: fields of ebvo_temporal_params; max_iter / tol / huber_delta set the nested Gauss-Newton parameters."""
         p = _lib.TemporalParams()
         self.lib.ebvo_temporal_default_params(C.byref(p))
+        fields = {name for name, _ in p._fields_} - {"gn"}
         for k, v in kw.items():
-            setattr(p, k, v)
+            if k in ("max_iter", "tol", "huber_delta"):
+                setattr(p.gn, k, v)
+            elif k in fields:
+                setattr(p, k, v)
+            else:
+                raise TypeError(f"temporal_match: unknown parameter {k!r}")
         self._check(self.lib.ebvo_temporal_match_submit(self._ctx, slot, C.byref(p)), "ebvo_temporal_match_submit")
         self._tq_stages = getattr(self, "_tq_stages", {})
         self._tq_stages[slot] = int(p.stages)

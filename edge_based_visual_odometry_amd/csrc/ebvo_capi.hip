@@ -699,6 +699,14 @@ extern "C" int ebvo_epipolar_lines(const double F[9], const ebvo_edge *edges, in
     return EBVO_OK;
 }
 
+// The thresholds every candidate search accepts: epi_thr, max_disp and orient_thr_deg in [0, +inf] (+inf: unbounded),
+// ncc_thr any value but NaN.  A negative max_disp would pass s = 0 through the squared test (s < max_disp^2) although
+// the reference's sqrt(0) <= max_disp fails; NaN would make every predicate false or the search box undefined.
+static bool stereo_thresholds_ok(double epi_thr, double max_disp, double orient_thr_deg, double ncc_thr)
+{
+    return epi_thr >= 0 && max_disp >= 0 && orient_thr_deg >= 0 && ncc_thr == ncc_thr;
+}
+
 static int epi_candidates_impl(ebvo_ctx *ctx, const ebvo_edge *L, int nL, const ebvo_edge *R, int nR, const double *lines,
                                double epi_thr, double max_disp, double orient_thr_deg, int stage_mask, int32_t *row_ptr,
                                int32_t *col_idx, uint8_t *orient_ok, int64_t cap, int64_t *n_pairs);
@@ -728,7 +736,8 @@ static int epi_candidates_impl(ebvo_ctx *ctx, const ebvo_edge *L, int nL, const 
                                int32_t *col_idx, uint8_t *orient_ok, int64_t cap, int64_t *n_pairs)
 {
     if (!ctx || nL < 0 || nR < 0 || !row_ptr || !n_pairs || cap < 0 || (cap > 0 && !col_idx) ||
-        (nL > 0 && (!L || !lines)) || (nR > 0 && !R) || (stage_mask & ~EBVO_STAGE_ALL) || stage_mask == 0)
+        (nL > 0 && (!L || !lines)) || (nR > 0 && !R) || (stage_mask & ~EBVO_STAGE_ALL) || stage_mask == 0 ||
+        !stereo_thresholds_ok(epi_thr, max_disp, orient_thr_deg, 0.0))
         return EBVO_ERR_ARG;
     EBVO_HIP(ctx, hipSetDevice(ctx->device));
     int rc;
@@ -1731,6 +1740,7 @@ extern "C" int ebvo_stereo_submit(ebvo_ctx *ctx, int slot, const ebvo_stereo_par
 {
     Slot *sp;
     if (!p || (p->stage_mask & ~EBVO_STAGE_ALL) || p->stage_mask == 0 || (p->reserved & ~(EBVO_PAIR_NO_SIMS | EBVO_PAIR_PUSH | EBVO_PAIR_PUSH_THETA | EBVO_PAIR_PACK)) ||
+        !stereo_thresholds_ok(p->epi_thr, p->max_disp, p->orient_thr_deg, p->ncc_thr) ||
         ((p->reserved & EBVO_PAIR_PUSH) && (p->reserved & EBVO_PAIR_PACK)) || get_slot(ctx, slot, &sp))
         return EBVO_ERR_ARG;
     Slot &s = *sp;
@@ -2115,7 +2125,8 @@ extern "C" int ebvo_epi_candidates_resident(ebvo_ctx *ctx, uint64_t tag_left, ui
                                             double epi_thr, double max_disp, double orient_thr_deg, int stage_mask,
                                             int want_orient_flags, ebvo_candidates_view *view)
 {
-    if (!ctx || !view || (stage_mask & ~EBVO_STAGE_ALL) || stage_mask == 0)
+    if (!ctx || !view || (stage_mask & ~EBVO_STAGE_ALL) || stage_mask == 0 ||
+        !stereo_thresholds_ok(epi_thr, max_disp, orient_thr_deg, 0.0))
         return EBVO_ERR_ARG;
     memset(view, 0, sizeof *view);
     const int iL = resident_ws(ctx, tag_left), iR = resident_ws(ctx, tag_right);
@@ -3467,8 +3478,13 @@ static int temporal_stage0_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_temporal_p
     EBVO_HIP(ctx, hipMemsetAsync(cnt, 0, sizeof(int32_t) * 2 * nk1, s.stream));
     const ebvo_edge *cfL, *cfR;
     final_mates(s, &cfL, &cfR);
-    const int cell = p->cell_size, gw = (w + cell - 1) / cell, gh = (h + cell - 1) / cell;
-    const int sr = (int)ceil(p->grid_radius / cell);
+    const int cell = p->cell_size, gw = (int)(((int64_t)w + cell - 1) / cell), gh = (int)(((int64_t)h + cell - 1) / cell);
+    // ceil(radius / cell) in double, saturated: the keyframe may come from a frame of another size, so the bound is not
+    // gw + gh of this one but 2^30 cells, more than any distance between the cell of an edge of a frame the context holds
+    // (at most 2^28 pixels) and a grid cell -- the saturated radius selects the same cells.  temporal_candidates_kernel
+    // clips its walk to the grid, so a radius wider than the grid costs what the whole grid costs.
+    const double sr_d = ceil(p->grid_radius / cell);
+    const int sr = sr_d < (double)(1 << 30) ? (int)sr_d : (1 << 30);
     if ((rc = ebvo_grow(ctx, s, s.tq_cells, match_temporal_grid_bytes(n_cf, gw * gh))))
         return rc;
     void *grid = s.tq_cells.p;
@@ -3515,7 +3531,7 @@ static int temporal_stage0_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_temporal_p
 extern "C" int ebvo_temporal_match_submit(ebvo_ctx *ctx, int slot, const ebvo_temporal_params *p)
 {
     Slot *sp;
-    if (!p || p->cell_size < 1 || !(p->grid_radius >= 0) || !(p->orient_thr_deg >= 0) || (p->stages & ~1) ||
+    if (!p || p->cell_size < 1 || !(p->grid_radius >= 0 && std::isfinite(p->grid_radius)) || !(p->orient_thr_deg >= 0) || (p->stages & ~1) ||
         (p->stages && (!(p->sift_thr > 0) || !(p->bnb_ncc >= 0) || !(p->bnb_sift >= 0) || p->gn.max_iter < 1 || !(p->gn.tol >= 0) ||
                        !(p->gn.huber_delta > 0))) ||
         get_slot(ctx, slot, &sp))

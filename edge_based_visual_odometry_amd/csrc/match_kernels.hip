@@ -1684,12 +1684,16 @@ __global__ __launch_bounds__(256) void temporal_candidates_kernel(const ebvo_edg
         const bool live = i0 < n_kf;
         const int i = live ? i0 : 0;
         const ebvo_edge kl = kfL[i], kr = kfR[i];
-        // the query cells are not clipped (include/Dataset.h:95-96); neighbour cells outside the grid hold nothing
+        // the query cells are not clipped (include/Dataset.h:95-96); neighbour cells outside the grid hold nothing, so the
+        // walk visits only the neighbours inside the grid, in the reference's order (dy outer, dx inner).  The bounds are
+        // uniform over a group of sixteen lanes; the ballots below only read the group's own bits.
         const int qlx = (int)kl.x / cell, qly = (int)kl.y / cell, qrx = (int)kr.x / cell, qry = (int)kr.y / cell;
+        const int dy0 = max(-sr, -qly), dy1 = live ? min(sr, gh - 1 - qly) : dy0 - 1;
+        const int dx0 = max(-sr, -qlx), dx1 = min(sr, gw - 1 - qlx);
         int c = 0;
         int64_t o = (FILL && live) ? row_ptr[i] : 0;
-        for (int dy = -sr; dy <= sr; ++dy)
-            for (int dx = -sr; dx <= sr; ++dx)
+        for (int dy = dy0; dy <= dy1; ++dy)
+            for (int dx = dx0; dx <= dx1; ++dx)
             {
                 const int ny = qly + dy, nx = qlx + dx;
                 const bool in_grid = live && ny >= 0 && ny < gh && nx >= 0 && nx < gw;
@@ -1703,8 +1707,10 @@ __global__ __launch_bounds__(256) void temporal_candidates_kernel(const ebvo_edg
                     {
                         j = cell_list[k];
                         const MateCells m = cells[j];
-                        // right_set.count(cf_idx): the mate's right edge is in a neighbour cell of the right query
-                        ok = abs(m.rx - qrx) <= sr && abs(m.ry - qry) <= sr && orient_close(kl.theta, cfL[j].theta, orient_thr) &&
+                        // right_set.count(cf_idx): the mate's right edge is in the right grid (mate_cells_kernel leaves
+                        // both right cells negative otherwise) and in a neighbour cell of the right query
+                        const bool r_in_grid = m.rx >= 0;
+                        ok = r_in_grid && abs(m.rx - qrx) <= sr && abs(m.ry - qry) <= sr && orient_close(kl.theta, cfL[j].theta, orient_thr) &&
                              orient_close(kr.theta, cfR[j].theta, orient_thr);
                     }
                     const unsigned hits = (unsigned)((__ballot(ok) >> gshift) & 0xffffull);

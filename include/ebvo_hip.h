@@ -511,7 +511,12 @@ int ebvo_ncc_quads(ebvo_ctx *ctx, const float *kfL, const float *kfR, const floa
  * patches from the undistorted right image at the final right edge (src/Stereo_Matches.cpp:1621-1622).
  * Mates = the final pairs of ebvo_stereo_finalize on a slot.  The candidates of a keyframe mate are listed in the order
  * of the reference's `left_candidates`: neighbour cell by neighbour cell (dy outer, dx inner), ascending mate index
- * within a cell (include/Dataset.h:92-113). */
+ * within a cell (include/Dataset.h:92-113).
+ * Accepted ranges (anything else: EBVO_ERR_ARG from ebvo_temporal_match(_submit), nothing touched): cell_size >= 1;
+ * grid_radius finite and >= 0 (a radius wider than the grid selects the whole grid and costs no more); orient_thr_deg >= 0;
+ * stages 0 or 1; with stages = 1 also sift_thr > 0, bnb_ncc >= 0, bnb_sift >= 0, gn.max_iter >= 1, gn.tol >= 0,
+ * gn.huber_delta > 0.  ebvo_finalize_params: bnb_ratio >= 0, ncc_thr not NaN, the same gn ranges, and with use_sift
+ * sift_thr > 0 and bnb_sift >= 0. */
 typedef struct ebvo_temporal_params
 {
     int cell_size;         /* GRID_SIZE 15, include/definitions.h:45 */
@@ -560,6 +565,11 @@ int ebvo_temporal_fetch(ebvo_ctx *ctx, int slot, int32_t *row_ptr, int32_t *col_
 /* images and every intermediate in HBM.  This is what bench.py times.                        */
 /* ---------------------------------------------------------------------------------------- */
 
+/* Accepted ranges.  epi_thr, max_disp, orient_thr_deg: >= 0, +inf allowed (the predicate then bounds nothing); ncc_thr: any
+ * value but NaN (keep = best > ncc_thr).  stage_mask: 1 ... 7.  ebvo_stereo_submit / ebvo_stereo_run and every
+ * ebvo_epi_candidates* call refuse a NaN threshold or a negative epi_thr / max_disp / orient_thr_deg with EBVO_ERR_ARG
+ * before touching any state: the slot keeps its pair and its results (a negative max_disp would otherwise need its own
+ * rule: the reference's sqrt(0) <= max_disp rejects even coincident points). */
 typedef struct ebvo_stereo_params
 {
     double F21[9]; /* row-major fundamental matrix, Dataset::get_fund_mat_21 */

@@ -39,9 +39,11 @@ def filter_rows(rp, mask):
 
 
 def stereo_edge_pairs(left_img, right_img, F, calib=None, bnb_ratio=0.9, ncc_thr=0.6, stage1=None, right_img_undist=None,
-                      left_img_undist=None, sift=False, sift_thr=500.0, bnb_sift=0.4, cluster_args=(True, False)):
+                      left_img_undist=None, sift=False, sift_thr=500.0, bnb_sift=0.4, cluster_args=(True, False),
+                      max_iter=20, tol=1e-3, huber_delta=3.0):
     """Runs the whole chain on the oracle.  stage1 = dict(left, right, row_ptr, col_idx, best, keep) may carry the
-    results of TOED + candidates + first NCC pass if the caller already has them (they are oracle outputs too).
+    results of TOED + candidates + first NCC pass if the caller already has them (they are oracle outputs too); ncc_thr is
+    then the threshold of the second NCC pass only.  max_iter / tol / huber_delta: the refinement's (ebvo_gn_params).
     left/right_img_undist: the undistorted images TOED and the refinement run on (None: the same as the raw ones, which
     is the KITTI / ETH3D case: zero distortion)."""
     lu = left_img if left_img_undist is None else left_img_undist
@@ -88,7 +90,7 @@ def stereo_edge_pairs(left_img, right_img, F, calib=None, bnb_ratio=0.9, ncc_thr
     counts["n_bnb"] = len(cand)
     # shift to the epipolar line (:1465), refine along it (:1468)
     cand = orc.epipolar_shift(cand, lines, rp)
-    ref = orc.gn_refine_stereo(lu, ru, L, lines, rp, np.stack([cand["x"], cand["y"]], 1))
+    ref = orc.gn_refine_stereo(lu, ru, L, lines, rp, np.stack([cand["x"], cand["y"]], 1), max_iter, tol, huber_delta)
     cand = cand.copy()
     cand["x"], cand["y"] = ref["refined_xy"][:, 0], ref["refined_xy"][:, 1]
     # shift again and cluster by orientation, single-candidate rows included (:1483 as the arguments bind)
@@ -216,13 +218,15 @@ def temporal_edge_pairs(kfL, kfR, cfL, cfR, kf_imgs, cf_imgs, rp, ci, sim_left, 
                 valid=valid[f_src])
 
 
-def temporal_reference(kfL, kfR, cfL, cfR, kf_imgs, cf_imgs, w, h, chain=True, ncc_thr=0.8):
+def temporal_reference(kfL, kfR, cfL, cfR, kf_imgs, cf_imgs, w, h, chain=True, ncc_thr=0.8, cell=15, radius=30.0,
+                       orient_thr_deg=10.0, sift_thr=200.0, bnb_ncc=0.8, bnb_sift=0.8, max_iter=20, tol=1e-3, huber=3.0):
     """One frame of Temporal_Matches::get_Temporal_Edge_Pairs_from_Quads on the oracle, from the stereo mates of the keyframe
     and of the current frame (src/Temporal_Matches.cpp:168-218): grid + orientation candidates (:335-414), NCC on the
     stored patches (:416-469), and with chain=True every later stage (temporal_edge_pairs above).
     kf_imgs / cf_imgs = (RAW left, undistorted left, undistorted right): the left patches of a mate are sampled from the raw
-    left image (src/Stereo_Matches.cpp:562), the right ones from the undistorted right image (:1580-1582)."""
-    rp, ci = orc.temporal_candidates(kfL, kfR, cfL, cfR, w, h)
+    left image (src/Stereo_Matches.cpp:562), the right ones from the undistorted right image (:1580-1582).
+    The parameters are those of ebvo_temporal_params (defaults: the reference's constants)."""
+    rp, ci = orc.temporal_candidates(kfL, kfR, cfL, cfR, w, h, cell, radius, orient_thr_deg)
     pkL, pkR = orc.edge_patches(kf_imgs[0], kfL), orc.edge_patches(kf_imgs[2], kfR)
     pcL, pcR = orc.edge_patches(cf_imgs[0], cfL), orc.edge_patches(cf_imgs[2], cfR)
     rows = rows_of(rp)
@@ -230,7 +234,8 @@ def temporal_reference(kfL, kfR, cfL, cfR, kf_imgs, cf_imgs, w, h, chain=True, n
     ref = dict(row_ptr=rp, col_idx=ci, sim_left=sl, sim_right=sr, keep=keep,
                counts=dict(n_kf=len(kfL), n_cf=len(cfL), n_candidates=len(ci), n_kept=int(keep.sum())))
     if chain:
-        ref["final"] = temporal_edge_pairs(kfL, kfR, cfL, cfR, kf_imgs[1:], cf_imgs[1:], rp, ci, sl, keep)
+        ref["final"] = temporal_edge_pairs(kfL, kfR, cfL, cfR, kf_imgs[1:], cf_imgs[1:], rp, ci, sl, keep, sift_thr, bnb_ncc,
+                                           bnb_sift, max_iter, tol, huber)
         ref["counts"].update(ref["final"]["counts"])
     return ref
 
