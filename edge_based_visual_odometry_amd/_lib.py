@@ -47,6 +47,7 @@ ABI_SYMBOLS = (
     "ebvo_undistort", "ebvo_stereo_set_undistort", "ebvo_sift_descriptors", "ebvo_sift_min_distances",
     "ebvo_toed_resident", "ebvo_epi_candidates_resident", "ebvo_ncc_pairs_resident",
     "ebvo_temporal_default_params", "ebvo_temporal_set_keyframe", "ebvo_temporal_match", "ebvo_temporal_match_submit", "ebvo_temporal_match_wait", "ebvo_temporal_fetch", "ebvo_temporal_fetch_final",
+    "ebvo_pose_default_params", "ebvo_temporal_estimate_pose", "ebvo_pose_from_quads", "ebvo_temporal_final_size",
 )
 
 
@@ -99,6 +100,23 @@ class TemporalCounts(C.Structure):
     _fields_ = [("n_kf", C.c_int32), ("n_cf", C.c_int32), ("n_candidates", C.c_int64), ("n_kept", C.c_int64),
                 ("n_sift", C.c_int64), ("n_bnb_ncc", C.c_int64), ("n_bnb_sift", C.c_int64), ("n_refined_valid", C.c_int64),
                 ("n_final", C.c_int64)]
+
+
+class PoseParams(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("min_iterations", C.c_int32), ("dyn_num_trials_mult", C.c_double),
+                ("success_prob", C.c_double), ("max_reproj_error", C.c_double), ("top_rank_fraction", C.c_double),
+                ("tau_length", C.c_double), ("tau_t1", C.c_double), ("tau_t2", C.c_double), ("tau_tangent", C.c_double),
+                ("rand_seed", C.c_uint32), ("continue_stream", C.c_int32), ("max_draws", C.c_int64)]
+
+
+class PoseResult(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("status", C.c_int32), ("found", C.c_int32),
+                ("n_quads", C.c_int64), ("top_n", C.c_int64), ("iterations", C.c_int64), ("draws", C.c_int64),
+                ("hypotheses", C.c_int64), ("best_inliers", C.c_int64), ("dynamic_max_iter", C.c_int64),
+                ("inlier_ratio", C.c_double), ("best_q1", C.c_int32), ("best_q2", C.c_int32)]
+
+
+POSE_OK, POSE_INSUFFICIENT, POSE_DRAW_CAP = 0, 1, 2
 
 
 class StereoView(C.Structure):
@@ -237,6 +255,15 @@ def load_library() -> C.CDLL:
     lib.ebvo_temporal_fetch.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     lib.ebvo_temporal_fetch_final.restype = i32
     lib.ebvo_temporal_fetch_final.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.ebvo_pose_default_params.restype = None
+    lib.ebvo_pose_default_params.argtypes = [C.POINTER(PoseParams)]
+    lib.ebvo_temporal_estimate_pose.restype = i32
+    lib.ebvo_temporal_estimate_pose.argtypes = [vp, i32, C.POINTER(StereoCalib), C.POINTER(PoseParams), C.POINTER(PoseResult), vp]
+    lib.ebvo_temporal_final_size.restype = i32
+    lib.ebvo_temporal_final_size.argtypes = [vp, i32, C.POINTER(C.c_int32), C.POINTER(i64)]
+    lib.ebvo_pose_from_quads.restype = i32
+    lib.ebvo_pose_from_quads.argtypes = [vp, vp, vp, i32, vp, vp, vp, C.POINTER(StereoCalib), C.POINTER(PoseParams),
+                                         C.POINTER(PoseResult), vp, vp, vp]
     lib.ebvo_undistort.argtypes = [vp, vp, i32, i32, ssz, vp, vp, i32, vp, ssz]
     lib.ebvo_stereo_set_undistort.argtypes = [vp, C.POINTER(UndistortParams)]
     lib.ebvo_stereo_fetch_end.argtypes = [vp, i32, C.POINTER(StereoView)]

@@ -388,11 +388,7 @@ class Context:
 
     # -- write_finalized_stereo_edge_pairs_to_file, numeric body (src/Stereo_Matches.cpp:1656-1699) -----------------
     def finalize_pairs(self, K_left, K_right, R21, T21, left, right) -> np.ndarray:
-        from ._lib import StereoCalib
-        cal = StereoCalib()
-        for name, v, n in (("K_left", K_left, 9), ("K_right", K_right, 9), ("R21", R21, 9), ("T21", T21, 3)):
-            a = np.ascontiguousarray(v, dtype=np.float64).reshape(n)
-            getattr(cal, name)[:] = a.tolist()
+        cal = self._calib((K_left, K_right, R21, T21))
         left, right = _edges(left), _edges(right)
         assert len(left) == len(right)
         out = np.zeros((len(left), 16))
@@ -421,16 +417,11 @@ class Context:
         return out
 
     def _finalize_args(self, calib, bnb_ratio, ncc_thr, use_sift, sift_thr, bnb_sift, gn):
-        from ._lib import FinalizeParams, StereoCalib
+        from ._lib import FinalizeParams
         p = FinalizeParams()
         p.bnb_ratio, p.ncc_thr, p.gn = bnb_ratio, ncc_thr, self._gn_params(**gn)
         p.use_sift, p.sift_thr, p.bnb_sift = int(bool(use_sift)), sift_thr, bnb_sift
-        cal = None
-        if calib is not None:
-            cal = StereoCalib()
-            for name, v, n in zip(("K_left", "K_right", "R21", "T21"), calib, (9, 9, 9, 3)):
-                getattr(cal, name)[:] = np.ascontiguousarray(v, dtype=np.float64).reshape(n).tolist()
-        return p, cal
+        return p, None if calib is None else self._calib(calib)
 
     def stereo_finalize_submit(self, calib=None, slot=0, bnb_ratio=0.9, ncc_thr=0.6, use_sift=False, sift_thr=500.0,
                                bnb_sift=0.4, **gn):
@@ -631,6 +622,68 @@ class Context:
             out["final"] = fin
         return counts, out
 
+    # -- relative pose from the final quads (MotionTracker::estimate_Relative_Pose_From_Quad_Pairs) -----------------------
+    def pose_params(self, **kw) -> _lib.PoseParams:
+        """ebvo_pose_params: the reference's defaults with `kw` (field names of the struct) applied."""
+        p = _lib.PoseParams()
+        self.lib.ebvo_pose_default_params(C.byref(p))
+        fields = {name for name, _ in p._fields_}
+        for k, v in kw.items():
+            if k not in fields:
+                raise TypeError(f"pose: unknown parameter {k!r}")
+            setattr(p, k, v)
+        return p
+
+    @staticmethod
+    def _calib(calib) -> _lib.StereoCalib:
+        """(K_left, K_right, R21, T21) -> ebvo_stereo_calib (row-major 3x3 matrices, T21 of 3)"""
+        cal = _lib.StereoCalib()
+        for name, v, n in zip(("K_left", "K_right", "R21", "T21"), calib, (9, 9, 9, 3)):
+            getattr(cal, name)[:] = np.ascontiguousarray(v, dtype=np.float64).reshape(n).tolist()
+        return cal
+
+    @staticmethod
+    def _pose_dict(r) -> dict:
+        out = {k: getattr(r, k) for k in ("status", "n_quads", "top_n", "iterations", "draws", "hypotheses", "best_inliers",
+                                          "dynamic_max_iter", "inlier_ratio", "best_q1", "best_q2")}
+        out["found"] = bool(r.found)
+        out["R"] = np.array(r.R[:], dtype=np.float64).reshape(3, 3)
+        out["t"] = np.array(r.t[:], dtype=np.float64)
+        return out
+
+    def temporal_estimate_pose(self, calib, slot: int = 0, **params) -> dict:
+        """RANSAC relative pose on the slot's final quads (after temporal_match(stages=1)) and the keyframe mates
+        (ebvo_temporal_estimate_pose).  calib = (K_left, K_right, R21, T21); params: fields of ebvo_pose_params.
+        Returns the result fields, R (3x3), t and `inlier` (uint8 per final quad, CSR order of the final quads)."""
+        p, cal, r = self.pose_params(**params), self._calib(calib), _lib.PoseResult()
+        n_kf, n = C.c_int32(), C.c_int64()   # the slot's own count of final quads sizes the mask
+        self._check(self.lib.ebvo_temporal_final_size(self._ctx, slot, C.byref(n_kf), C.byref(n)), "ebvo_temporal_final_size")
+        inlier = np.zeros(n.value, dtype=np.uint8)
+        self._check(self.lib.ebvo_temporal_estimate_pose(self._ctx, slot, C.byref(cal), C.byref(p), C.byref(r), ptr(inlier)),
+                    "ebvo_temporal_estimate_pose")
+        out = self._pose_dict(r)
+        out["inlier"] = inlier
+        return out
+
+    def pose_from_quads(self, kf_left, kf_right, row_ptr, cf_left, cf_right, calib, **params) -> dict:
+        """The same on host arrays (ebvo_pose_from_quads): KF mates per row, CSR row_ptr, CF left / right centres per quad.
+        Also returns `quad_geom` (n x 12: Gamma, Gamma_bar, T, T_bar) and `rank_order` (CSR index per rank position); both
+        stay zero when status = 1 (insufficient quads)."""
+        kf_left, kf_right = _edges(kf_left), _edges(kf_right)
+        cf_left, cf_right = _edges(cf_left), _edges(cf_right)
+        row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int32)
+        assert len(kf_left) == len(kf_right) == len(row_ptr) - 1
+        n = int(row_ptr[-1])
+        assert len(cf_left) == len(cf_right) == n
+        p, cal, r = self.pose_params(**params), self._calib(calib), _lib.PoseResult()
+        inlier, geom, order = np.zeros(n, dtype=np.uint8), np.zeros((n, 12)), np.zeros(n, dtype=np.int32)
+        self._check(self.lib.ebvo_pose_from_quads(self._ctx, ptr(kf_left), ptr(kf_right), len(kf_left), ptr(row_ptr), ptr(cf_left),
+                                                  ptr(cf_right), C.byref(cal), C.byref(p), C.byref(r), ptr(inlier), ptr(geom),
+                                                  ptr(order)), "ebvo_pose_from_quads")
+        out = self._pose_dict(r)
+        out.update(inlier=inlier, quad_geom=geom, rank_order=order)
+        return out
+
     def stereo_fetch_begin(self, slot: int = 0, what: int = _lib.FETCH_DEFAULT):
         """Enqueue the device-to-host copies of a finished pair's results into the slot's page-locked staging."""
         self._check(self.lib.ebvo_stereo_fetch_begin(self._ctx, slot, what), "ebvo_stereo_fetch_begin")
@@ -692,7 +745,8 @@ class Context:
         profiler instruments one stage alone (index in profile_get()'s order + 1; 0 = every stage), 4 / 5 = launch layout
         of the refinements (1 = one thread per pair always / threshold of the eight-lanes layout); 10 = pair chain as a
         hipGraph; 11 / 12 / 17 = grids of the exact centre / mags / NCC tile kernels in blocks; 13 / 14 / 18 = A/B switches;
-        15 = bit mask of kernels launched twice, 16 = the chain ends after stage N (measurement only): include/ebvo_hip.h.
+        15 = bit mask of kernels launched twice, 16 = the chain ends after stage N (measurement only), 20 = draws per batch
+        of the pose search (same bits for any value): include/ebvo_hip.h.
         A value outside the key's range raises EbvoError(EBVO_ERR_ARG) and changes nothing."""
         self._check(self.lib.ebvo_debug_set(self._ctx, key, value), "ebvo_debug_set")
 

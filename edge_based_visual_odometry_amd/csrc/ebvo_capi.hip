@@ -172,7 +172,8 @@ static void slot_destroy(Slot *s)
                        &s->scan_tmp,     &s->col_idx,      &s->rc_edges,       &s->sims,           &s->best,
                        &s->keep,         &s->patches_raw,  &s->patches_norm,   &s->patches_flag,   &s->patches_norm_r,
                        &s->patches_flag_r, &s->pair_left,  &s->sincos,         &s->scratch_b,      &s->scratch_c,
-                       &s->scratch_d,    &s->fetch_pack};
+                       &s->scratch_d,    &s->fetch_pack,   &s->pose_in,        &s->pose_geom,      &s->pose_order,
+                       &s->pose_draw,    &s->pose_hyp};
     for (GrowBuf *b : bufs)
         free_buf(*b);
     (void)hipFree(s->d_total);
@@ -3214,6 +3215,7 @@ extern "C" int ebvo_temporal_set_keyframe(ebvo_ctx *ctx, int slot)
         ctx->kf_cap = cap;
     }
     ctx->kf_n = (int)n;
+    ++ctx->kf_gen; // quads matched against the previous keyframe no longer belong to ctx->kf_L / kf_R
     {
         // the keyframe's undistorted images stay with it: the photometric refinement of the quads samples them
         const size_t bytes = (size_t)s.cur_h * s.cur_w;
@@ -3549,6 +3551,7 @@ extern "C" int ebvo_temporal_match_submit(ebvo_ctx *ctx, int slot, const ebvo_te
         return rc_f;
     s.tq_n = -1;
     s.tq_n_kf = ctx->kf_n;
+    s.tq_kf_gen = ctx->kf_gen;
     s.tq_final = Slot::TqFinal();
     s.tq_params = *p;
     s.tq_empty = ctx->kf_n == 0 || s.n_final == 0;
@@ -3711,6 +3714,118 @@ extern "C" int ebvo_temporal_fetch(ebvo_ctx *ctx, int slot, int32_t *row_ptr, in
     }
     EBVO_HIP(ctx, hipStreamSynchronize(st));
     return EBVO_OK;
+}
+
+// ---- relative pose from the temporal quads (pose_kernels.hip) ----------------------------------------------------------
+extern "C" void ebvo_pose_default_params(ebvo_pose_params *p)
+{
+    if (!p)
+        return;
+    p->max_iterations = 5000; // Ransac_Options (include/MotionTracker.h)
+    p->min_iterations = 1000;
+    p->dyn_num_trials_mult = 3.0;
+    p->success_prob = 0.97;
+    p->max_reproj_error = 1.5;
+    p->top_rank_fraction = 0.7;
+    p->tau_length = 0.13; // TAU_C1..C4 (include/definitions.h)
+    p->tau_t1 = 0.12;
+    p->tau_t2 = 0.12;
+    p->tau_tangent = 0.32;
+    p->rand_seed = 1;
+    p->continue_stream = 0;
+    p->max_draws = (int64_t)1 << 22;
+}
+
+static bool pose_args_ok(const ebvo_stereo_calib *cal, const ebvo_pose_params *p, const ebvo_pose_result *res)
+{
+    if (!cal || !p || !res)
+        return false;
+    for (int i = 0; i < 9; ++i)
+        if (std::isnan(cal->K_left[i]) || std::isnan(cal->R21[i]))
+            return false;
+    for (int i = 0; i < 3; ++i)
+        if (std::isnan(cal->T21[i]))
+            return false;
+    const double tau[] = {p->max_reproj_error, p->tau_length, p->tau_t1, p->tau_t2, p->tau_tangent};
+    for (double v : tau)
+        if (!(v >= 0)) // NaN or negative; +inf is allowed
+            return false;
+    return p->success_prob > 0 && p->success_prob < 1 && p->top_rank_fraction > 0 && p->top_rank_fraction <= 1 &&
+           p->max_iterations >= 0 && p->min_iterations >= 0 && p->max_draws >= 1 && p->dyn_num_trials_mult > 0;
+}
+
+extern "C" int ebvo_temporal_final_size(ebvo_ctx *ctx, int slot, int32_t *n_kf, int64_t *n_final)
+{
+    Slot *sp;
+    if (get_slot(ctx, slot, &sp) || !n_kf || !n_final)
+        return EBVO_ERR_ARG;
+    Slot &s = *sp;
+    if (s.tq_final.n < 0 || s.in_flight || s.tq_in_flight)
+        return EBVO_ERR_STATE;
+    *n_kf = s.tq_n_kf;
+    *n_final = s.tq_final.n;
+    return EBVO_OK;
+}
+
+extern "C" int ebvo_temporal_estimate_pose(ebvo_ctx *ctx, int slot, const ebvo_stereo_calib *cal, const ebvo_pose_params *p,
+                                           ebvo_pose_result *res, uint8_t *inlier)
+{
+    Slot *sp;
+    if (get_slot(ctx, slot, &sp) || !pose_args_ok(cal, p, res))
+        return EBVO_ERR_ARG;
+    Slot &s = *sp;
+    if (s.tq_final.n < 0 || s.in_flight || s.fin_in_flight || s.tq_in_flight || s.tq_kf_gen != ctx->kf_gen)
+    {
+        ctx->last_error = s.tq_final.n < 0 ? "the slot holds no final quads (ebvo_temporal_match with stages = 1 first)"
+                          : s.tq_kf_gen != ctx->kf_gen ? "the keyframe was replaced since the slot's quads were matched"
+                                                       : "the slot has work in flight (wait for it first)";
+        return EBVO_ERR_STATE;
+    }
+    if (s.tq_final.n > INT32_MAX)
+        return EBVO_ERR_ARG;
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    const Slot::TqFinal &F = s.tq_final;
+    return pose_run(ctx, s, ctx->kf_L, ctx->kf_R, F.rp, s.tq_n_kf, F.L, F.R, (int)F.n, cal, p, res, inlier, nullptr, nullptr);
+}
+
+extern "C" int ebvo_pose_from_quads(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *kf_right, int n_kf,
+                                    const int32_t *row_ptr, const ebvo_edge *cf_left, const ebvo_edge *cf_right,
+                                    const ebvo_stereo_calib *cal, const ebvo_pose_params *p, ebvo_pose_result *res,
+                                    uint8_t *inlier, double *quad_geom, int32_t *rank_order)
+{
+    if (!ctx || n_kf < 0 || !row_ptr || (n_kf > 0 && (!kf_left || !kf_right)) || !pose_args_ok(cal, p, res) || row_ptr[0] != 0)
+        return EBVO_ERR_ARG;
+    for (int i = 0; i < n_kf; ++i)
+        if (row_ptr[i + 1] < row_ptr[i])
+            return EBVO_ERR_ARG;
+    const int n = row_ptr[n_kf];
+    if (n > 0 && (!cf_left || !cf_right))
+        return EBVO_ERR_ARG;
+    Slot &s = *ctx->slots[0];
+    if (s.in_flight || s.fin_in_flight || s.tq_in_flight)
+    {
+        ctx->last_error = "slot 0 has submitted work in flight; wait for it first";
+        return EBVO_ERR_STATE;
+    }
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    if (n < 2 || (int64_t)(p->top_rank_fraction * (double)n) < 2) // insufficient: nothing to upload or launch
+        return pose_run(ctx, s, nullptr, nullptr, nullptr, n_kf, nullptr, nullptr, n, cal, p, res, inlier, nullptr, nullptr);
+    // uploaded into the slot's own pose buffer: the slot's resident results stay as they are
+    const size_t ek = sizeof(ebvo_edge) * (size_t)n_kf, eq = sizeof(ebvo_edge) * (size_t)n, rb = sizeof(int32_t) * ((size_t)n_kf + 1);
+    int rc;
+    if ((rc = ebvo_grow(ctx, s, s.pose_in, 2 * ek + 2 * eq + rb)))
+        return rc;
+    uint8_t *base = (uint8_t *)s.pose_in.p;
+    ebvo_edge *d_kfL = (ebvo_edge *)base, *d_kfR = (ebvo_edge *)(base + ek), *d_cfL = (ebvo_edge *)(base + 2 * ek),
+              *d_cfR = (ebvo_edge *)(base + 2 * ek + eq);
+    int32_t *d_rp = (int32_t *)(base + 2 * ek + 2 * eq);
+    hipStream_t st = s.stream;
+    EBVO_HIP(ctx, hipMemcpyAsync(d_kfL, kf_left, ek, hipMemcpyHostToDevice, st));
+    EBVO_HIP(ctx, hipMemcpyAsync(d_kfR, kf_right, ek, hipMemcpyHostToDevice, st));
+    EBVO_HIP(ctx, hipMemcpyAsync(d_cfL, cf_left, eq, hipMemcpyHostToDevice, st));
+    EBVO_HIP(ctx, hipMemcpyAsync(d_cfR, cf_right, eq, hipMemcpyHostToDevice, st));
+    EBVO_HIP(ctx, hipMemcpyAsync(d_rp, row_ptr, rb, hipMemcpyHostToDevice, st));
+    return pose_run(ctx, s, d_kfL, d_kfR, d_rp, n_kf, d_cfL, d_cfR, n, cal, p, res, inlier, quad_geom, rank_order);
 }
 
 // the slot's page-locked result arena holds at least `bytes` (a re-allocation waits for copies still heading into the old one).
@@ -4087,6 +4202,8 @@ static bool debug_value_ok(int key, int value)
         return value <= 512; // the smallest of the grids it divides: a larger divisor would launch zero blocks
     case 19:
         return value <= EBVO_TOTAL_PARTS;
+    case 20:
+        return value <= 1 << 20;
     case 0: case 1: case 2: case 3: case 5: case 15: case 16: case 17:
         return true;
     default:
@@ -4115,6 +4232,8 @@ extern "C" int ebvo_debug_set(ebvo_ctx *ctx, int key, int value)
         ctx->small_div = value;
     else if (key == 19)
         ctx->cand_blocks = value;
+    else if (key == 20)
+        ctx->pose_batch = value; // draws per batch of the pose search (same bits for any value)
     else if (key == 13)
         ctx->ingest_stream = value;
     else if (key == 0)

@@ -1,0 +1,118 @@
+/*
+ * ebvo_geom.h -- the stereo geometry of one (left edge, right edge) pair, shared by the finalisation rows
+ * (refine_kernels.hip: finalize_pairs_kernel) and the pose search (pose_kernels.hip): Gamma from
+ * Utility::backproject_2D_point_to_3D_point_using_rays and T from reconstruct_3D_Tangent_through_intersection_of_planes
+ * (src/utility.cpp:95-112).  The calibration inverses are formed once on the host (Eigen's cofactor inverse, restated),
+ * every product / cross / normalize in Eigen's fixed-size order.  Compiled with -ffp-contract=off (no FMA).
+ */
+#ifndef EBVO_GEOM_H
+#define EBVO_GEOM_H
+
+#include "../../include/ebvo_hip.h"
+#include "ebvo_math.h"
+
+struct FinalCalib
+{
+    double Kli[9], Kri[9], R21[9], T21[3];
+};
+
+#ifdef __HIPCC__
+__device__ static inline void mv3(const double *m, const double *v, double *o)
+{
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        o[i] = (m[i * 3] * v[0] + m[i * 3 + 1] * v[1]) + m[i * 3 + 2] * v[2];
+}
+__device__ static inline void mtv3(const double *m, const double *v, double *o)
+{
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        o[i] = (m[i] * v[0] + m[3 + i] * v[1]) + m[6 + i] * v[2];
+}
+__device__ static inline void cross3(const double *a, const double *b, double *o)
+{
+    o[0] = a[1] * b[2] - a[2] * b[1];
+    o[1] = a[2] * b[0] - a[0] * b[2];
+    o[2] = a[0] * b[1] - a[1] * b[0];
+}
+__device__ static inline double dot3(const double *a, const double *b)
+{
+    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2];
+}
+// Eigen's normalize() / normalized(): unchanged when the squared norm is not positive
+__device__ static inline void normalize3(double *v)
+{
+    const double z = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
+    if (z > 0)
+    {
+        const double n = sqrt(z);
+        v[0] /= n;
+        v[1] /= n;
+        v[2] /= n;
+    }
+}
+
+// Gamma (3-D point, left camera) and T (unit 3-D tangent) of one pair; g1 / g2: the two rays K^-1 (x, y, 1)
+__device__ static inline void stereo_gamma_tangent(const FinalCalib &C, const ebvo_edge &l, const ebvo_edge &r, double *G,
+                                                   double *T, double *g1, double *g2)
+{
+    const double el[3] = {l.x, l.y, 1.0}, er[3] = {r.x, r.y, 1.0};
+    double Rg1[3];
+    mv3(C.Kli, el, g1);
+    mv3(C.Kri, er, g2);
+    mv3(C.R21, g1, Rg1);
+    const double numerator = C.T21[0] - C.T21[2] * g2[0]; // e1.dot(T) - e3.dot(T) * e1.dot(ray2)
+    const double denominator = Rg1[2] * g2[0] - Rg1[0];
+    const double rho1 = numerator / denominator;
+    double sl, cl, sr, cr;
+    ebvo_sincos(l.theta, &sl, &cl);
+    ebvo_sincos(r.theta, &sr, &cr);
+    const double t1r[3] = {cl, sl, 0.0}, t2r[3] = {cr, sr, 0.0};
+    double t1[3], t2[3], n1[3], c2[3], n2[3];
+    mv3(C.Kli, t1r, t1);
+    mv3(C.Kri, t2r, t2);
+    cross3(t1, g1, n1);
+    cross3(t2, g2, c2);
+    mtv3(C.R21, c2, n2);
+    cross3(n1, n2, T);
+    normalize3(T);
+    G[0] = rho1 * g1[0];
+    G[1] = rho1 * g1[1];
+    G[2] = rho1 * g1[2];
+}
+#endif
+
+static inline double cof3_host(const double *m, int i, int j)
+{
+    const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+    return m[i1 * 3 + j1] * m[i2 * 3 + j2] - m[i1 * 3 + j2] * m[i2 * 3 + j1];
+}
+
+// Matrix3d::inverse() (Eigen/src/LU/InverseImpl.h, cofactor form), row-major
+static inline void inverse3_host(const double *m, double *inv)
+{
+    const double c0 = cof3_host(m, 0, 0), c1 = cof3_host(m, 1, 0), c2 = cof3_host(m, 2, 0);
+    const double det = (c0 * m[0] + c1 * m[3]) + c2 * m[6];
+    const double invdet = 1.0 / det;
+    inv[0] = c0 * invdet;
+    inv[1] = c1 * invdet;
+    inv[2] = c2 * invdet;
+    for (int i = 1; i < 3; ++i)
+        for (int j = 0; j < 3; ++j)
+            inv[i * 3 + j] = cof3_host(m, j, i) * invdet;
+}
+
+// the calibration of the finalisation rows: K_left^-1, K_right^-1, R21, T21
+static inline FinalCalib final_calib_host(const double *K_left, const double *K_right, const double *R21, const double *T21)
+{
+    FinalCalib C;
+    inverse3_host(K_left, C.Kli);
+    inverse3_host(K_right, C.Kri);
+    for (int i = 0; i < 9; ++i)
+        C.R21[i] = R21[i];
+    for (int i = 0; i < 3; ++i)
+        C.T21[i] = T21[i];
+    return C;
+}
+
+#endif /* EBVO_GEOM_H */

@@ -158,6 +158,9 @@ struct Slot
     GrowBuf grad_x, grad_y, gn_xy, gn_out, gn_valid, gn_iters, gn_state, gn_lists, gn_pack; // photometric refinement (refine_kernels.hip)
     GrowBuf tq_i32, tq_cols, tq_f64, tq_u8, tq_cells; // temporal quads of the slot's pair against the keyframe
     GrowBuf tq_chain;                                  // ... and what the stages after the NCC filter need
+    uint64_t tq_kf_gen = 0;                            // the keyframe (ebvo_ctx::kf_gen) the quads were matched against
+    GrowBuf pose_in, pose_geom, pose_order, pose_draw, pose_hyp; // pose search (pose_kernels.hip): uploaded quads, geometry, rank
+                                                                 // order, one batch of draws, its hypotheses
     bool sift_left_valid = false;                      // sift_desc holds the descriptors of every left TOED edge of this pair
     struct TqFinal                                     // the quads that leave the chain (pointers into tq_chain)
     {
@@ -234,6 +237,14 @@ struct PinnedBuf
     size_t bytes = 0;
 };
 
+// glibc's rand() (random_r TYPE_3: x[i] = x[i - 31] + x[i - 3], output x[i] >> 1) restated for the pose search
+struct PoseRng
+{
+    int32_t r[31]; // the last 31 words; r[pos] is x[i - 31] of the next word
+    int pos = 0;
+    bool seeded = false;
+};
+
 struct ebvo_ctx
 {
     int device = 0;
@@ -244,6 +255,7 @@ struct ebvo_ctx
     std::vector<Slot *> slots; // slot 0 always exists; it also serves the host-buffer entry points
     // keyframe of the temporal stage (ebvo_temporal_set_keyframe): final stereo mates and their stored patches, device-resident
     int kf_n = -1;             // -1: no keyframe
+    uint64_t kf_gen = 0;       // bumped by every ebvo_temporal_set_keyframe
     ebvo_edge *kf_L = nullptr, *kf_R = nullptr;
     float *kf_Ln = nullptr, *kf_Rn = nullptr;   // [n][2][49] normalised patches (left image raw, right image undistorted)
     uint8_t *kf_Lf = nullptr, *kf_Rf = nullptr; // [n][2] sentinel flags
@@ -297,6 +309,8 @@ struct ebvo_ctx
                                 // one more launch of each costs the pair rate, tools/gpu_marginal_cost.py)
     int no_prep = 0;            // developer key (ebvo_debug_set 14): 1 = lines, boxes, sincos and row pairs as four launches (A/B)
     int ingest_stream = 0;      // developer key (ebvo_debug_set 13): 1 = ebvo_stereo_upload_async copies on the upload stream (A/B)
+    PoseRng pose_rng;           // ebvo_pose_params::continue_stream continues it across pose calls
+    int pose_batch = 0;         // developer key (ebvo_debug_set 20): index pairs per batch of the pose search, 0 = 4096
     bool screen_audit = false;  // ebvo_toed_screen_audit is running: the screen keeps its gx, gy, |g| (toed_kernels.hip)
     int64_t toed_fallbacks = 0; // hybrid TOED runs repeated on the strict path (more screened candidates than cap_edges)
 
@@ -517,6 +531,9 @@ int sift_distances_enqueue(ebvo_ctx *ctx, Slot &s, const uint8_t *d_left, const 
 int sift_and_flags_enqueue(ebvo_ctx *ctx, Slot &s, const uint8_t *d_a, const uint8_t *d_b, int64_t n, uint8_t *d_out);
 int match_expand_rows_enqueue(ebvo_ctx *ctx, Slot &s, const int32_t *d_row_ptr, int nL, int64_t n_pairs, int32_t *d_pair_left);
 int match_ncc_stored_enqueue(ebvo_ctx *ctx, Slot &s, const float *d_A, const float *d_B, int n, double *d_sim);
+int pose_run(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, const int32_t *d_rp, int n_kf,
+             const ebvo_edge *d_cfL, const ebvo_edge *d_cfR, int n, const ebvo_stereo_calib *cal, const ebvo_pose_params *p,
+             ebvo_pose_result *res, uint8_t *inlier, double *quad_geom, int32_t *rank_order);
 int misc_fp64_peak(ebvo_ctx *ctx, Slot &s, int iters, double *tf_muladd, double *tf_fma);
 
 #endif

@@ -24,6 +24,7 @@
 #ifndef EBVO_ADAPTERS_HPP
 #define EBVO_ADAPTERS_HPP
 
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstdio>
@@ -814,6 +815,63 @@ class TemporalMatcherHIP
 
   private:
     Context::Ptr ctx_;
+};
+
+// MotionTracker (src/MotionTracker.cpp): estimate_Relative_Pose_From_Quad_Pairs on the final quads a TemporalMatcherHIP left
+// in `slot` (match with stages = 1) against the keyframe -- the quads never leave the device.  The options and the state
+// mirror Ransac_Options / Ransac_State (include/MotionTracker.h); `opt` defaults to the reference's values (plus TAU_C1..4).
+// Returns false, with the identity pose, where the reference returns false (fewer than two quads to sample) and on an error
+// (last_status); a search that hit the draw cap (pose.status = 2) returns true with the best hypothesis so far.
+class MotionTrackerHIP
+{
+  public:
+    explicit MotionTrackerHIP(Context::Ptr ctx, const ebvo_stereo_calib &calib) : ctx_(std::move(ctx)), calib_(calib) {}
+    int last_status = EBVO_OK;
+
+    struct Ransac_Options
+    {
+        ebvo_pose_params p;
+        Ransac_Options() { ebvo_pose_default_params(&p); }
+    };
+    struct Ransac_State
+    {
+        std::array<double, 9> R{{1, 0, 0, 0, 1, 0, 0, 0, 1}}; // best_pose_hypothesis, row-major
+        std::array<double, 3> t{{0, 0, 0}};
+        size_t iterations = 0;
+        double inlier_ratio = 0;
+        size_t best_minimal_inlier_count = 0;
+        size_t dynamic_max_iter = 0;
+        std::vector<uint8_t> inliers; // per final quad (CSR order of TemporalMatcherHIP::Quads) when asked for
+        ebvo_pose_result pose{};      // every field of the search
+    };
+
+    bool estimate_Relative_Pose_From_Quad_Pairs(int slot, const Ransac_Options &opt, Ransac_State &state, bool want_inliers = false)
+    {
+        state = Ransac_State();
+        int32_t n_kf = 0;
+        int64_t n_final = 0;
+        last_status = ebvo_temporal_final_size(ctx_->get(), slot, &n_kf, &n_final); // the slot's own count sizes the mask
+        if (!report(*ctx_, last_status, "ebvo_temporal_final_size"))
+            return false;
+        if (want_inliers)
+            state.inliers.assign((size_t)n_final, 0);
+        last_status = ebvo_temporal_estimate_pose(ctx_->get(), slot, &calib_, &opt.p, &state.pose,
+                                                  want_inliers ? state.inliers.data() : nullptr);
+        if (!report(*ctx_, last_status, "ebvo_temporal_estimate_pose"))
+            return false;
+        const ebvo_pose_result &r = state.pose;
+        std::copy(r.R, r.R + 9, state.R.begin());
+        std::copy(r.t, r.t + 3, state.t.begin());
+        state.iterations = (size_t)r.iterations;
+        state.inlier_ratio = r.inlier_ratio;
+        state.best_minimal_inlier_count = (size_t)r.best_inliers;
+        state.dynamic_max_iter = (size_t)r.dynamic_max_iter;
+        return r.status != 1;
+    }
+
+  private:
+    Context::Ptr ctx_;
+    ebvo_stereo_calib calib_;
 };
 
 // cv::undistort(src, dst, K, dist) of src/Pipeline.cpp:78-79 on a CV_8UC1 image (K = fx fy cx cy, dist = k1 k2 p1 p2 [k3])

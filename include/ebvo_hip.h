@@ -34,7 +34,10 @@ extern "C" {
 #define EBVO_ABI_VERSION 6 /* 2: photometric refinement, stage glue, finalisation, resident chain; 3: pinned result views,
                               undistortion, SIFT descriptors, SIFT stages of the chain; 4: the temporal chain after the
                               NCC filter (ebvo_temporal_params / _counts grew, ebvo_temporal_fetch_final); 5: the resident
-                              stage-wise calls (ebvo_toed_resident, ebvo_epi_candidates_resident, ebvo_ncc_pairs_resident); 6: ebvo_toed_screen_audit, ebvo_stereo_upload_async, ebvo_host_register, ebvo_stereo_fetch_compact_begin / _end, ebvo_stereo_pushed_view */
+                              stage-wise calls (ebvo_toed_resident, ebvo_epi_candidates_resident, ebvo_ncc_pairs_resident); 6: ebvo_toed_screen_audit, ebvo_stereo_upload_async, ebvo_host_register, ebvo_stereo_fetch_compact_begin / _end, ebvo_stereo_pushed_view;
+                              still 6 with the additive pose search: ebvo_pose_params / _result, ebvo_pose_default_params,
+                              ebvo_temporal_estimate_pose, ebvo_pose_from_quads, ebvo_temporal_final_size,
+                              ebvo_debug_set key 20 */
 
 typedef struct ebvo_ctx ebvo_ctx;
 
@@ -560,6 +563,81 @@ int ebvo_temporal_fetch_final(ebvo_ctx *ctx, int slot, int32_t *row_ptr, int32_t
 int ebvo_temporal_fetch(ebvo_ctx *ctx, int slot, int32_t *row_ptr, int32_t *col_idx, double *sim_left, double *sim_right,
                         uint8_t *keep);
 
+/* ---- relative pose from the temporal quads (MotionTracker::estimate_Relative_Pose_From_Quad_Pairs) ----------------- */
+/* RANSAC over pairs of final quads (src/MotionTracker.cpp:175-253, Ransac_Options / Ransac_State of include/MotionTracker.h,
+ * TAU_C1..C4 of include/definitions.h), restated literally:
+ *   - per quad (KF mate i, candidate j) Gamma / T from the keyframe mate and Gamma_bar / T_bar from the quad's left and right
+ *     cluster centres (get_Gammas_and_Tangents_From_Quads :28-66): columns 6-11 of ebvo_finalize_pairs with K_right := K_left
+ *     (the reference uses get_left_calib_matrix() for both cameras here; K_right of `cal` is not read);
+ *   - rank order (:90-103): ascending row length of the KF mate, then KF index, then candidate index; every quad is kept
+ *     (there is no ground truth on the device: the has_gt() filter and b_is_veridical do not apply);
+ *     top_n = (size_t)(top_rank_fraction * n_quads);
+ *   - the loop: termination test at its top (iterations > min_iterations && iterations > dynamic_max_iter), two indices
+ *     rand() % top_n redrawn together while equal, the length / T1 / T2 / tangent constraints (:108-134; a rejected draw
+ *     sets iterations = iterations > 0 ? iterations - 1 : 0, so a rejection at iteration 0 still advances it to 1), the pose
+ *     R = B_bar B^T, t = Gamma_bar_1 - R Gamma_1 (:136-153), the score over ALL quads (sqrt(dx^2 + dy^2) < max_reproj_error
+ *     of K_left (R Gamma + t) against the quad's left centre, :155-173), the best hypothesis replaced only by a strictly
+ *     larger count, and dynamic_max_iter from the three branches (>= 0.95 / <= 0.05 / ceil(log(1 - success_prob) /
+ *     log(1 - ratio^2) * dyn_num_trials_mult)).
+ *   - the random stream is glibc's rand() (TYPE_3 additive generator) restated per context: rand_seed is the srand() value
+ *     (1 = the never-seeded rand() of main_VO; Ransac_Options::seed is dead code in the reference).  libc rand() is never
+ *     called.  continue_stream = 1 continues the context's generator where the previous pose call left it (one
+ *     process-global rand() across frames); the first call of a context seeds it with rand_seed.
+ * Deliberate divergences, where the reference has undefined behaviour or never returns:
+ *   - fewer than 2 quads or top_n < 2 (rand() % 0, or an endless redraw of idx1 == idx2): status 1, identity pose, nothing
+ *     launched and no random number drawn (quads_by_kf.size() < 2 of the reference counts GT-veridical KF mates only, which
+ *     the device cannot form; this rule replaces it);
+ *   - at most max_draws index pairs (idx1 != idx2) are drawn: when the loop still needs one more, status 2 (the reference
+ *     loops forever when no pair passes the constraints);
+ *   - the ceil(...) of the third branch is clamped to [0, 2^62] before its conversion to an integer.
+ * Accepted ranges (anything else: EBVO_ERR_ARG, nothing touched): no NaN anywhere; 0 < success_prob < 1;
+ * 0 < top_rank_fraction <= 1; max_reproj_error and the four taus >= 0 (+inf allowed); max_iterations, min_iterations >= 0;
+ * max_draws >= 1; dyn_num_trials_mult > 0. */
+typedef struct ebvo_pose_params /* defaults (ebvo_pose_default_params) = Ransac_Options + TAU_C1..4 */
+{
+    int32_t max_iterations, min_iterations;         /* 5000, 1000 */
+    double dyn_num_trials_mult, success_prob;       /* 3.0, 0.97 */
+    double max_reproj_error, top_rank_fraction;     /* 1.5 px, 0.7 */
+    double tau_length, tau_t1, tau_t2, tau_tangent; /* 0.13 0.12 0.12 0.32 */
+    uint32_t rand_seed;      /* srand() value (0 acts as 1, as in glibc); default 1 = the never-seeded rand() of main_VO */
+    int32_t continue_stream; /* 1: continue this ctx's generator from the previous pose call (a process-global rand()) */
+                             /* The generator is ONE per context, shared by its slots: pose calls on one context from several
+                                threads race on it (a context is not thread-safe), and with continue_stream = 1 calls on
+                                different slots continue one stream in call order, as one process-global rand() would. */
+    int64_t max_draws;       /* index pairs drawn at most (reference: unbounded); default 1 << 22 */
+} ebvo_pose_params;
+typedef struct ebvo_pose_result
+{
+    double R[9], t[3];        /* row-major; identity / 0 if no hypothesis beat 0 inliers */
+    int32_t status, found;    /* 0 ok / 1 insufficient quads / 2 draw cap reached; found = best_inliers > 0 */
+    int64_t n_quads, top_n;
+    int64_t iterations;       /* Ransac_State::iterations when the loop ended */
+    int64_t draws;            /* index pairs (idx1 != idx2) the loop consumed */
+    int64_t hypotheses;       /* ... of them passing the four constraints (scored) */
+    int64_t best_inliers;     /* best_minimal_inlier_count */
+    int64_t dynamic_max_iter;
+    double inlier_ratio;
+    int32_t best_q1, best_q2; /* positions in the rank order of the best hypothesis' pair; -1 if none */
+} ebvo_pose_result;
+void ebvo_pose_default_params(ebvo_pose_params *p);
+/* On the slot's final quads (after ebvo_temporal_match with stages = 1) and the ctx's keyframe mates.  EBVO_ERR_STATE when
+ * the slot has no final quads, a pair, finalisation or temporal stage of it is in flight, or the keyframe was replaced since
+ * the quads were matched.  inlier (may be NULL): n_final bytes in the CSR order of ebvo_temporal_fetch_final, 1 = inlier of
+ * the best hypothesis.  The slot's results (ebvo_temporal_fetch_final / ebvo_temporal_fetch) are not changed. */
+int ebvo_temporal_estimate_pose(ebvo_ctx *ctx, int slot, const ebvo_stereo_calib *cal, const ebvo_pose_params *p,
+                                ebvo_pose_result *res, uint8_t *inlier);
+/* The sizes of the slot's final quads (what ebvo_temporal_fetch_final returns and `inlier` above needs): keyframe mates and
+ * quads.  EBVO_ERR_STATE when the slot has none or a pair or temporal stage of it is in flight. */
+int ebvo_temporal_final_size(ebvo_ctx *ctx, int slot, int32_t *n_kf, int64_t *n_final);
+/* The same on host arrays: KF mates per row (n_kf), CSR row_ptr (n_kf + 1, row_ptr[0] = 0, non-decreasing), the CF left / right
+ * centres per quad (row_ptr[n_kf]).  quad_geom (may be NULL): n x 12 = Gamma, Gamma_bar, T, T_bar in CSR order; rank_order
+ * (may be NULL): n, the CSR index at each rank position.  Both are left untouched when status = 1.  Runs on slot 0's
+ * stream (EBVO_ERR_STATE while work of slot 0 is in flight) without touching slot 0's results. */
+int ebvo_pose_from_quads(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *kf_right, int n_kf, const int32_t *row_ptr,
+                         const ebvo_edge *cf_left, const ebvo_edge *cf_right, const ebvo_stereo_calib *cal,
+                         const ebvo_pose_params *p, ebvo_pose_result *res, uint8_t *inlier, double *quad_geom,
+                         int32_t *rank_order);
+
 /* ---------------------------------------------------------------------------------------- */
 /* Device-resident stereo pipeline: TOED(left) + TOED(right) + candidates + NCC of one pair,  */
 /* images and every intermediate in HBM.  This is what bench.py times.                        */
@@ -742,6 +820,8 @@ int ebvo_profile_get(ebvo_ctx *ctx, ebvo_kernel_time *out /* EBVO_MAX_KERNELS */
  * key 16: the resident pair's chain ENDS after stage `value` (0 = whole chain; the pair's record keeps the counts of the last
  *        whole run, the buffers behind the stage are stale): the pair rate of every prefix of the chain
  *        (tools/gpu_prefix_chain.py).  Measurement only.
+ * key 20: index pairs per batch of the pose search (ebvo_temporal_estimate_pose / ebvo_pose_from_quads; 0 = the default,
+ *        4096; at most 1 << 20).  Same bits for any value.
  * A negative value, an unknown key or a value outside the key's range returns EBVO_ERR_ARG and changes nothing. */
 int ebvo_debug_set(ebvo_ctx *ctx, int key, int value);
 

@@ -1,0 +1,46 @@
+"""Microseconds per pose call (ebvo_temporal_estimate_pose / ebvo_pose_from_quads) at the EuRoC frame-loop size (the resident
+chain's final quads of the half-size EuRoC frames: keyframe 0, frame 2) and on 20k synthetic quads (30 % outliers), with the
+number of device batches each call needed (draws / batch size, rounded up).  Prints one JSON line."""
+import json
+import math
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from edge_based_visual_odometry_amd.api import Context  # noqa: E402
+from tests import oracle_pose as op  # noqa: E402
+from tests.pose_scenes import R_GT, T_GT, resident_chain, rig  # noqa: E402
+
+BATCH = 4096  # the default of ebvo_debug_set key 20
+
+
+def timed(fn, reps):
+    fn()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        r = fn()
+    return (time.perf_counter() - t0) / reps * 1e6, r
+
+
+def main():
+    out = {}
+    with Context(512, 1280, device=0) as ctx:
+        calib, kfL, kfR, fin, counts = resident_chain(ctx, 2)
+        us, r = timed(lambda: ctx.temporal_estimate_pose(calib), 50)
+        out["euroc_resident"] = dict(n_quads=int(r["n_quads"]), us_per_call=round(us, 1), draws=int(r["draws"]),
+                                     hypotheses=int(r["hypotheses"]), batches=math.ceil(r["draws"] / BATCH))
+        K = rig("euroc")
+        kf_l, kf_r, rp, cf_l, cf_r, _ = op.synthetic_quads(20000, 0.3, (K[0], K[2], K[3]), R_GT, T_GT, seed=1)
+        us, r = timed(lambda: ctx.pose_from_quads(kf_l, kf_r, rp, cf_l, cf_r, K), 10)
+        out["synthetic_20k_host_arrays"] = dict(n_quads=int(r["n_quads"]), us_per_call=round(us, 1), draws=int(r["draws"]),
+                                                hypotheses=int(r["hypotheses"]), batches=math.ceil(r["draws"] / BATCH))
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
