@@ -48,6 +48,8 @@ ABI_SYMBOLS = (
     "ebvo_toed_resident", "ebvo_epi_candidates_resident", "ebvo_ncc_pairs_resident",
     "ebvo_temporal_default_params", "ebvo_temporal_set_keyframe", "ebvo_temporal_match", "ebvo_temporal_match_submit", "ebvo_temporal_match_wait", "ebvo_temporal_fetch", "ebvo_temporal_fetch_final",
     "ebvo_pose_default_params", "ebvo_temporal_estimate_pose", "ebvo_pose_from_quads", "ebvo_temporal_final_size",
+    "ebvo_gt_default_params", "ebvo_stereo_set_gt", "ebvo_stereo_gt_size", "ebvo_stereo_gt_fetch", "ebvo_stereo_gt_metrics",
+    "ebvo_stereo_gt_stage_rows", "ebvo_gt_locate", "ebvo_gt_evaluate_rows",
 )
 
 
@@ -117,6 +119,26 @@ class PoseResult(C.Structure):
 
 
 POSE_OK, POSE_INSUFFICIENT, POSE_DRAW_CAP = 0, 1, 2
+
+
+class GtParams(C.Structure):
+    _fields_ = [("orient_gate_deg", C.c_double), ("pool_epi_thr", C.c_double), ("pool_dist", C.c_double),
+                ("pool_orient_deg", C.c_double), ("tp_dist", C.c_double)]
+
+
+class GtStage(C.Structure):
+    _fields_ = [("stage", C.c_int32), ("present", C.c_int32), ("rows", C.c_int64), ("nonempty", C.c_int64),
+                ("rows_with_tp", C.c_int64), ("sum_tp", C.c_int64), ("sum_n", C.c_int64), ("recall", C.c_double),
+                ("precision", C.c_double), ("precision_pair", C.c_double), ("ambiguity", C.c_double)]
+
+
+# stage ids (ebvo_hip.h EBVO_GT_*) and the names the reference gives them in Frame_Evaluation_Metrics
+# (src/Stereo_Matches.cpp:1382-1535; "NCC" appears twice there)
+GT_STAGE_NAMES = ("Epipolar Proximity", "Location Proximity", "Orientation", "SIFT", "NCC", "BNB-NCC", "BNB-SIFT",
+                  "Photometric Refinement", "Edge Clustering", "NCC", "Best", "Final")
+(GT_EPIPOLAR, GT_DISPARITY, GT_ORIENTATION, GT_SIFT, GT_NCC, GT_BNB_NCC, GT_BNB_SIFT, GT_REFINE, GT_CLUSTER, GT_NCC2, GT_BEST,
+ GT_FINAL) = range(12)
+GT_NUM_STAGES = 12
 
 
 class StereoView(C.Structure):
@@ -264,6 +286,15 @@ def load_library() -> C.CDLL:
     lib.ebvo_pose_from_quads.restype = i32
     lib.ebvo_pose_from_quads.argtypes = [vp, vp, vp, i32, vp, vp, vp, C.POINTER(StereoCalib), C.POINTER(PoseParams),
                                          C.POINTER(PoseResult), vp, vp, vp]
+    lib.ebvo_gt_default_params.restype = None
+    lib.ebvo_gt_default_params.argtypes = [C.POINTER(GtParams)]
+    lib.ebvo_stereo_set_gt.argtypes = [vp, i32, vp, i32, i32, ssz, C.POINTER(StereoCalib), C.POINTER(GtParams)]
+    lib.ebvo_stereo_gt_size.argtypes = [vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(i64)]
+    lib.ebvo_stereo_gt_fetch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+    lib.ebvo_stereo_gt_metrics.argtypes = [vp, i32, C.POINTER(GtStage)]
+    lib.ebvo_stereo_gt_stage_rows.argtypes = [vp, i32, i32, vp, i32]
+    lib.ebvo_gt_locate.argtypes = [vp, vp, i32, vp, i32, i32, ssz, C.POINTER(StereoCalib), C.POINTER(GtParams), vp, vp, vp, vp]
+    lib.ebvo_gt_evaluate_rows.argtypes = [vp, vp, vp, i32, vp, vp, dbl, vp, C.POINTER(GtStage)]
     lib.ebvo_undistort.argtypes = [vp, vp, i32, i32, ssz, vp, vp, i32, vp, ssz]
     lib.ebvo_stereo_set_undistort.argtypes = [vp, C.POINTER(UndistortParams)]
     lib.ebvo_stereo_fetch_end.argtypes = [vp, i32, C.POINTER(StereoView)]

@@ -684,6 +684,107 @@ class Context:
         out.update(inlier=inlier, quad_geom=geom, rank_order=order)
         return out
 
+    # -- ground-truth evaluation from a disparity map (Find_Stereo_GT_Locations, get_Stereo_Edge_GT_Pairs,
+    # -- Evaluate_Stereo_Edge_Correspondences) ---------------------------------------------------------------
+    def gt_params(self, **kw) -> _lib.GtParams:
+        """ebvo_gt_params: the reference's constants (4.0, 0.5, 1.0, 5.0, DIST_TO_GT_THRESH 1.0) with `kw` applied."""
+        p = _lib.GtParams()
+        self.lib.ebvo_gt_default_params(C.byref(p))
+        fields = {name for name, _ in p._fields_}
+        for k, v in kw.items():
+            if k not in fields:
+                raise TypeError(f"gt: unknown parameter {k!r}")
+            setattr(p, k, v)
+        return p
+
+    @staticmethod
+    def _disp(disp) -> np.ndarray:
+        disp = np.asarray(disp)
+        if disp.ndim != 2 or disp.dtype != np.float32:
+            raise TypeError("the disparity map is a 2-D float32 array (disp0GT.pfm as the reference reads it)")
+        if disp.strides[1] != 4 or disp.strides[0] % 4 or disp.strides[0] < 4 * disp.shape[1]:
+            disp = np.ascontiguousarray(disp)
+        return disp
+
+    def stereo_set_gt(self, disp, calib, slot: int = 0, **params) -> dict:
+        """Arm `slot` (its pair has run) with the left disparity map: GT locations, veridical pool and the metrics of the
+        stages the run formed (ebvo_stereo_set_gt).  Returns dict(n_valid, n_focused, n_pool)."""
+        disp = self._disp(disp)
+        p, cal = self.gt_params(**params), self._calib(calib)
+        self._check(self.lib.ebvo_stereo_set_gt(self._ctx, slot, ptr(disp), disp.shape[0], disp.shape[1], disp.strides[0] // 4,
+                                                C.byref(cal), C.byref(p)), "ebvo_stereo_set_gt")
+        return self.stereo_gt_size(slot)
+
+    def stereo_gt_size(self, slot: int = 0) -> dict:
+        nv, nf, npool = C.c_int32(), C.c_int32(), C.c_int64()
+        self._check(self.lib.ebvo_stereo_gt_size(self._ctx, slot, C.byref(nv), C.byref(nf), C.byref(npool)), "ebvo_stereo_gt_size")
+        return dict(n_valid=nv.value, n_focused=nf.value, n_pool=npool.value)
+
+    def stereo_gt_fetch(self, slot: int = 0) -> dict:
+        """What Stereo_Edge_Pairs holds after get_Stereo_Edge_GT_Pairs, per focused left edge in index order."""
+        sz = self.stereo_gt_size(slot)
+        nf, npool = sz["n_focused"], sz["n_pool"]
+        out = dict(focused_index=np.zeros(nf, dtype=np.int32), gt_xy=np.zeros((nf, 2)), gamma_left=np.zeros((nf, 3)),
+                   gamma_right=np.zeros((nf, 3)), pool_row_ptr=np.zeros(nf + 1, dtype=np.int32),
+                   pool_idx=np.zeros(npool, dtype=np.int32))
+        self._check(self.lib.ebvo_stereo_gt_fetch(self._ctx, slot, ptr(out["focused_index"]), ptr(out["gt_xy"]),
+                                                  ptr(out["gamma_left"]), ptr(out["gamma_right"]), ptr(out["pool_row_ptr"]),
+                                                  ptr(out["pool_idx"])), "ebvo_stereo_gt_fetch")
+        out.update(sz)
+        return out
+
+    @staticmethod
+    def _gt_stage_dict(g) -> dict:
+        d = {k: getattr(g, k) for k in ("stage", "rows", "nonempty", "rows_with_tp", "sum_tp", "sum_n", "recall", "precision",
+                                        "precision_pair", "ambiguity")}
+        d["name"] = _lib.GT_STAGE_NAMES[g.stage]
+        d["present"] = bool(g.present)
+        return d
+
+    def stereo_gt_metrics(self, slot: int = 0) -> list:
+        """One dict per stage of get_Stereo_Edge_Pairs, in the reference's order and under its names; `present` False for a
+        stage the chain did not run (SIFT stages without use_sift, the later stages before stereo_finalize)."""
+        arr = (_lib.GtStage * _lib.GT_NUM_STAGES)()
+        rc = self.lib.ebvo_stereo_gt_metrics(self._ctx, slot, arr)
+        if rc < 0:
+            self._check(rc, "ebvo_stereo_gt_metrics")
+        return [self._gt_stage_dict(arr[k]) for k in range(rc)]
+
+    def stereo_gt_stage_rows(self, stage: int, n_left: int, slot: int = 0) -> np.ndarray:
+        """(n, tp) of every left edge at `stage` ([n_left, 2] int32, zero on rows that are not focused).  n_left: the run's
+        counts.n_left; a smaller value raises EbvoError(EBVO_ERR_CAPACITY), nothing is written."""
+        out = np.zeros((n_left, 2), dtype=np.int32)   # the library refuses an array shorter than the slot's edge list
+        self._check(self.lib.ebvo_stereo_gt_stage_rows(self._ctx, slot, stage, ptr(out), n_left), "ebvo_stereo_gt_stage_rows")
+        return out
+
+    def gt_locate(self, edges, disp, calib, **params) -> dict:
+        """Find_Stereo_GT_Locations on host arrays (ebvo_gt_locate): valid, gt_xy, gamma_left, gamma_right per edge."""
+        edges, disp = _edges(edges), self._disp(disp)
+        p, cal = self.gt_params(**params), self._calib(calib)
+        n = len(edges)
+        out = dict(valid=np.zeros(n, dtype=np.uint8), gt_xy=np.zeros((n, 2)), gamma_left=np.zeros((n, 3)),
+                   gamma_right=np.zeros((n, 3)))
+        self._check(self.lib.ebvo_gt_locate(self._ctx, ptr(edges), n, ptr(disp), disp.shape[0], disp.shape[1], disp.strides[0] // 4,
+                                            C.byref(cal), C.byref(p), ptr(out["valid"]), ptr(out["gt_xy"]), ptr(out["gamma_left"]),
+                                            ptr(out["gamma_right"])), "ebvo_gt_locate")
+        return out
+
+    def gt_evaluate_rows(self, row_ptr, cand_edges, focused, gt_xy, tp_dist: float = 1.0):
+        """Evaluate_Stereo_Edge_Correspondences on a CSR list of candidate edges per left edge (ebvo_gt_evaluate_rows).
+        Returns (n_tp [nL, 2] int32, stage dict)."""
+        row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int32)
+        nL = len(row_ptr) - 1
+        cand, focused = _edges(cand_edges), np.ascontiguousarray(focused, dtype=np.uint8)
+        gt_xy = np.ascontiguousarray(gt_xy, dtype=np.float64).reshape(-1, 2)
+        if nL < 0 or len(focused) != nL or len(gt_xy) != nL or (nL >= 0 and len(cand) != int(row_ptr[-1])):
+            raise ValueError("gt_evaluate_rows: row_ptr, cand_edges, focused and gt_xy do not describe the same rows")
+        n_tp, g = np.zeros((nL, 2), dtype=np.int32), _lib.GtStage()
+        self._check(self.lib.ebvo_gt_evaluate_rows(self._ctx, ptr(row_ptr), ptr(cand), nL, ptr(focused), ptr(gt_xy), float(tp_dist),
+                                                   ptr(n_tp), C.byref(g)), "ebvo_gt_evaluate_rows")
+        d = self._gt_stage_dict(g)
+        d.pop("name")
+        return n_tp, d
+
     def stereo_fetch_begin(self, slot: int = 0, what: int = _lib.FETCH_DEFAULT):
         """Enqueue the device-to-host copies of a finished pair's results into the slot's page-locked staging."""
         self._check(self.lib.ebvo_stereo_fetch_begin(self._ctx, slot, what), "ebvo_stereo_fetch_begin")
@@ -746,7 +847,7 @@ class Context:
         of the refinements (1 = one thread per pair always / threshold of the eight-lanes layout); 10 = pair chain as a
         hipGraph; 11 / 12 / 17 = grids of the exact centre / mags / NCC tile kernels in blocks; 13 / 14 / 18 = A/B switches;
         15 = bit mask of kernels launched twice, 16 = the chain ends after stage N (measurement only), 20 = draws per batch
-        of the pose search (same bits for any value): include/ebvo_hip.h.
+        of the pose search, 21 = most blocks of the ground-truth kernels (same bits for any value): include/ebvo_hip.h.
         A value outside the key's range raises EbvoError(EBVO_ERR_ARG) and changes nothing."""
         self._check(self.lib.ebvo_debug_set(self._ctx, key, value), "ebvo_debug_set")
 

@@ -12,7 +12,8 @@
 
 const char *const g_kernel_names[K_NUM] = {
     "toed_conv",   "toed_nms",   "toed_rowscan", "toed_compact", "toed_finalize", "toed_exact_centre", "toed_exact_mags", "cand_boxes", "epi_lines",
-    "cand_count",  "scan",       "cand_fill",    "edge_patches", "ncc_pairs",     "ncc_stored", "misc", "sobel", "gn_refine", "sift"};
+    "cand_count",  "scan",       "cand_fill",    "edge_patches", "ncc_pairs",     "ncc_stored", "misc", "sobel", "gn_refine", "sift",
+    "gt_misc",     "gt_pool",    "gt_census",    "gt_rows"};
 
 // ------------------------------------------------------------------------------------------
 int ebvo_fail_hip(ebvo_ctx *ctx, hipError_t e, const char *what, const char *file, int line)
@@ -173,7 +174,9 @@ static void slot_destroy(Slot *s)
                        &s->keep,         &s->patches_raw,  &s->patches_norm,   &s->patches_flag,   &s->patches_norm_r,
                        &s->patches_flag_r, &s->pair_left,  &s->sincos,         &s->scratch_b,      &s->scratch_c,
                        &s->scratch_d,    &s->fetch_pack,   &s->pose_in,        &s->pose_geom,      &s->pose_order,
-                       &s->pose_draw,    &s->pose_hyp};
+                       &s->pose_draw,    &s->pose_hyp,       &s->gt_disp,        &s->gt_geom,        &s->gt_flags,
+                       &s->gt_boxes,     &s->gt_pool_i32,  &s->gt_pool_idx,    &s->gt_rows,        &s->gt_tot,
+                       &s->gt_up};
     for (GrowBuf *b : bufs)
         free_buf(*b);
     (void)hipFree(s->d_total);
@@ -485,6 +488,7 @@ static int host_slot(ebvo_ctx *ctx, Slot **out)
         return rc;
     s.fetch_pending = false;
     s.have_pair = s.have_run = s.have_refined = s.have_final = false;
+    s.gt_armed = false; // the ground truth was given for the pair that ran
     s.sift_left_valid = false;
     s.undist_pair = false;
     s.fetch_what = 0;
@@ -1156,6 +1160,7 @@ extern "C" int ebvo_stereo_upload_slot(ebvo_ctx *ctx, int slot, const uint8_t *i
         return EBVO_ERR_STATE;
     EBVO_HIP(ctx, hipSetDevice(ctx->device));
     s.have_pair = s.have_run = s.have_refined = s.have_final = false; // results of the previous pair are gone
+    s.gt_armed = false; // the ground truth was given for the pair that ran
     s.have_push = false;
     if (slot == 0)
         ctx->sw_tag[0] = ctx->sw_tag[1] = 0; // ... and so are the TOED results of the resident stage-wise calls
@@ -1203,6 +1208,7 @@ extern "C" int ebvo_stereo_upload_async(ebvo_ctx *ctx, int slot, const uint8_t *
     if (s.in_flight || s.fin_in_flight || s.tq_in_flight)
         return EBVO_ERR_STATE;
     s.have_pair = s.have_run = s.have_refined = s.have_final = false;
+    s.gt_armed = false; // the ground truth was given for the pair that ran
     if (slot == 0)
         ctx->sw_tag[0] = ctx->sw_tag[1] = 0;
     s.tq_n = -1;
@@ -1750,6 +1756,7 @@ extern "C" int ebvo_stereo_submit(ebvo_ctx *ctx, int slot, const ebvo_stereo_par
     EBVO_HIP(ctx, hipSetDevice(ctx->device));
     int rc;
     s.have_run = s.have_refined = s.have_final = false;
+    s.gt_armed = false; // the ground truth was given for the pair that ran
     const bool fetch_was_pending = s.fetch_pending;
     s.fetch_pending = false; // stream order (or the event below): the kernels run after any copy still enqueued
     s.fetch_what = 0;
@@ -2740,6 +2747,16 @@ static int finalize_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_finalize_params *
     enum { T_SIFT = 0, T_NCC, T_BNB, T_CLUSTERS, T_NCC2, T_FINAL };
     const uint8_t *keep1 = (const uint8_t *)s.keep.p;
     const double *conf0 = nullptr; // SIFT distance per pair of the run (refine_confidences, :757)
+    // Evaluate_Stereo_Edge_Correspondences after a stage (:1419-1521) when, and only when, the slot is armed
+    // (ebvo_stereo_set_gt): the (n, tp) of every row of the stage's list and its integer totals; reads the lists only
+    const bool gt_on = s.gt_armed;
+    auto gt_eval = [&](int stage, const int32_t *rp, const ebvo_edge *cand, const uint8_t *flags) -> int {
+        if (!gt_on)
+            return EBVO_OK;
+        return gt_rows_enqueue(ctx, s, rp, cand, cand ? nullptr : (const int32_t *)s.col_idx.p, s.im[1].edges, flags,
+                               (const double *)s.gt_geom.p, (const uint8_t *)s.gt_flags.p + s.gt_nL, nL, s.gt_params.tp_dist,
+                               (int32_t *)s.gt_rows.p + (size_t)stage * 2 * nL, (unsigned long long *)s.gt_tot.p + (size_t)stage * 8);
+    };
     if (p->use_sift)
     {
         // 0. augment_Edge_Data (:1410) + apply_SIFT_filtering (:1414): descriptors of every left and right TOED edge on the
@@ -2773,7 +2790,8 @@ static int finalize_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_finalize_params *
                                          p->sift_thr, dist, ok)) ||
             (rc = sift_and_flags_enqueue(ctx, s, ok, (const uint8_t *)s.keep.p, n0, both)))
             return rc;
-        if ((rc = glue_rows_from_flags_enqueue(ctx, s, rp0, nL, ok, cnt, order)) || (rc = scan_counts(rpA, T_SIFT)))
+        if ((rc = glue_rows_from_flags_enqueue(ctx, s, rp0, nL, ok, cnt, order)) || (rc = scan_counts(rpA, T_SIFT)) ||
+            (rc = gt_eval(EBVO_GT_SIFT, rp0, nullptr, ok)))
             return rc;
         keep1 = both;
         conf0 = dist;
@@ -2783,12 +2801,14 @@ static int finalize_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_finalize_params *
     if ((rc = glue_rows_from_flags_enqueue(ctx, s, rp0, nL, keep1, cnt, order)) || (rc = scan_counts(rpA, T_NCC)) ||
         (rc = glue_gather_rows_enqueue(ctx, s, rp0, cnt, order, rpA, nL, s.im[1].edges, (const int32_t *)s.col_idx.p, candA,
                                        (const double *)s.best.p, scoreA)) ||
-        (conf0 && (rc = glue_gather_rows_enqueue(ctx, s, rp0, cnt, order, rpA, nL, nullptr, nullptr, nullptr, conf0, confA))))
+        (conf0 && (rc = glue_gather_rows_enqueue(ctx, s, rp0, cnt, order, rpA, nL, nullptr, nullptr, nullptr, conf0, confA))) ||
+        (rc = gt_eval(EBVO_GT_NCC, rp0, nullptr, keep1)))
         return rc;
     // 2. Best-Nearly-Best test on the NCC scores (:1440) ...
     if ((rc = glue_bnb_enqueue(ctx, s, rpA, nL, scoreA, p->bnb_ratio, 1, cnt, order)) || (rc = scan_counts(rpB, T_BNB)) ||
         (rc = glue_gather_rows_enqueue(ctx, s, rpA, cnt, order, rpB, nL, candA, nullptr, candB, scoreA, scoreB)) ||
-        (conf0 && (rc = glue_gather_rows_enqueue(ctx, s, rpA, cnt, order, rpB, nL, nullptr, nullptr, nullptr, confA, confB))))
+        (conf0 && (rc = glue_gather_rows_enqueue(ctx, s, rpA, cnt, order, rpB, nL, nullptr, nullptr, nullptr, confA, confB))) ||
+        (rc = gt_eval(EBVO_GT_BNB_NCC, rpB, candB, nullptr)))
         return rc;
     if (conf0)
     {
@@ -2800,6 +2820,8 @@ static int finalize_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_finalize_params *
         std::swap(rpA, rpB);
         std::swap(candA, candB);
         std::swap(scoreA, scoreB);
+        if ((rc = gt_eval(EBVO_GT_BNB_SIFT, rpB, candB, nullptr)))
+            return rc;
     }
     const int32_t *d_nB = rpB + nL; // pairs that enter the refinement: a subset of the run's kept NCC matches
     const int64_t n_ref = s.result.n_matches < n0 ? (s.result.n_matches > 0 ? s.result.n_matches : 1) : n0;
@@ -2813,7 +2835,8 @@ static int finalize_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_finalize_params *
                                            (const double *)s.lines.p, left_of, (const double *)s.gn_xy.p, nullptr, nullptr,
                                            nullptr, n_ref, p->gn.max_iter, p->gn.tol, p->gn.huber_delta, out, out + nz,
                                            out + 2 * nz, (uint8_t *)s.gn_valid.p, (int32_t *)s.gn_iters.p, out + 3 * nz, d_nB)) ||
-            (rc = glue_xy_enqueue(ctx, s, candC, out + 3 * nz, n0, true, d_nB)))
+            (rc = glue_xy_enqueue(ctx, s, candC, out + 3 * nz, n0, true, d_nB)) ||
+            (rc = gt_eval(EBVO_GT_REFINE, rpB, candC, nullptr)))
             return rc;
         // 5. consolidate_redundant_edge_hypothesis(pairs, false, true) (:1483).  Against the signature (pairs, frame_idx,
         // b_do_epipolar_shift = true, b_do_clustering = true) this binds frame_idx = 0, shift = true, cluster = true: the
@@ -2823,7 +2846,8 @@ static int finalize_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_finalize_params *
         if ((rc = glue_shift_enqueue(ctx, s, candC, (const double *)s.lines.p, left_of, n0, candA, d_nB)) ||
             (rc = glue_cluster_enqueue(ctx, s, candA, rpB, nL, 1, 0, cnt, candB, cluster_of)) ||
             (rc = scan_counts(rpA, T_CLUSTERS)) ||
-            (rc = glue_gather_rows_enqueue(ctx, s, rpB, cnt, nullptr, rpA, nL, candB, nullptr, candA, nullptr, nullptr)))
+            (rc = glue_gather_rows_enqueue(ctx, s, rpB, cnt, nullptr, rpA, nL, candB, nullptr, candA, nullptr, nullptr)) ||
+            (rc = gt_eval(EBVO_GT_CLUSTER, rpA, candA, nullptr)))
             return rc;
     }
     {
@@ -2835,11 +2859,13 @@ static int finalize_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_finalize_params *
                                           (const uint8_t *)s.patches_flag.p, p->ncc_thr, nullptr, best2, keep2, ncc_left,
                                           sincos2, rpA + nL)) ||
             (rc = glue_rows_from_flags_enqueue(ctx, s, rpA, nL, keep2, cnt, order)) || (rc = scan_counts(rpB, T_NCC2)) ||
-            (rc = glue_gather_rows_enqueue(ctx, s, rpA, cnt, order, rpB, nL, candA, nullptr, candC, best2, scoreB)))
+            (rc = glue_gather_rows_enqueue(ctx, s, rpA, cnt, order, rpB, nL, candA, nullptr, candC, best2, scoreB)) ||
+            (rc = gt_eval(EBVO_GT_NCC2, rpB, candC, nullptr)))
             return rc;
         if ((rc = glue_keep_best_enqueue(ctx, s, rpB, nL, scoreB, cnt, order)) || (rc = scan_counts(rpA, T_FINAL)) ||
             (rc = glue_final_pairs_enqueue(ctx, s, rpB, cnt, order, rpA, nL, s.im[0].edges, candC, scoreB, final_left,
-                                           fin_l, fin_r, fin_score)))
+                                           fin_l, fin_r, fin_score)) ||
+            (rc = gt_eval(EBVO_GT_BEST, rpA, fin_r, nullptr)))
             return rc;
     }
     // 8. the rows of the output file (at most one final pair per left edge)
@@ -2869,9 +2895,22 @@ extern "C" int ebvo_stereo_finalize_submit(ebvo_ctx *ctx, int slot, const ebvo_f
     s.sift_left_valid = false;
     s.n_final = 0;
     s.final_has_rows = calib != nullptr;
+    s.gt_fin_enq = s.gt_armed;
+    s.gt_fin_sift = p->use_sift != 0;
+    s.gt_fin_done = false;
     memset(s.h_fin_tot, 0, sizeof(int32_t) * 8);
     if (s.result.n_left == 0 || s.result.n_pairs == 0)
     {
+        // armed: every stage of the chain holds an empty list on every row; (n, tp) = 0 and the totals of that (rows = the
+        // focused rows), so that the record of a stage says what Evaluate_Stereo_Edge_Correspondences would (:332-335)
+        for (int k = EBVO_GT_SIFT; s.gt_armed && s.gt_nL > 0 && k <= EBVO_GT_BEST; ++k)
+        {
+            int32_t *rows = (int32_t *)s.gt_rows.p + (size_t)k * 2 * s.gt_nL;
+            EBVO_HIP(ctx, hipMemsetAsync(rows, 0, sizeof(int32_t) * 2 * (size_t)s.gt_nL, s.stream));
+            if (int rc_g = gt_totals_enqueue(ctx, s, rows, (const uint8_t *)s.gt_flags.p + s.gt_nL, s.gt_nL,
+                                             (unsigned long long *)s.gt_tot.p + (size_t)k * 8))
+                return rc_g;
+        }
         EBVO_HIP(ctx, hipEventRecord(s.ev_fin, s.stream)); // nothing to do: the wait returns zero counts
         s.fin_in_flight = true;
         return EBVO_OK;
@@ -2907,6 +2946,7 @@ extern "C" int ebvo_stereo_finalize_wait(ebvo_ctx *ctx, int slot, ebvo_finalize_
     counts->n_final = t[5];
     s.n_final = t[5];
     s.have_final = true;
+    s.gt_fin_done = s.gt_fin_enq;
     return EBVO_OK;
 }
 
@@ -3121,7 +3161,7 @@ extern "C" int ebvo_stereo_set_undistort(ebvo_ctx *ctx, const ebvo_undistort_par
     ctx->undist = *p;
     ctx->undist_on = true;
     for (Slot *s : ctx->slots) // pairs uploaded before the switch went to img: they must be uploaded again
-        s->have_pair = s->have_run = s->have_refined = s->have_final = false;
+        s->have_pair = s->have_run = s->have_refined = s->have_final = s->gt_armed = false;
     return EBVO_OK;
 }
 
@@ -4183,6 +4223,432 @@ extern "C" int ebvo_profile_get(ebvo_ctx *ctx, ebvo_kernel_time *out, int *n)
     return rc;
 }
 
+// ---- ground-truth evaluation from a disparity map (gt_kernels.hip) ------------------------------------------------------
+extern "C" void ebvo_gt_default_params(ebvo_gt_params *p)
+{
+    if (!p)
+        return;
+    p->orient_gate_deg = 4.0; // src/Stereo_Matches.cpp:146
+    p->pool_epi_thr = 0.5;    // :227
+    p->pool_dist = 1.0;       // :228
+    p->pool_orient_deg = 5.0; // :228
+    p->tp_dist = 1.0;         // DIST_TO_GT_THRESH, include/definitions.h:42
+}
+
+static bool gt_params_ok(const ebvo_gt_params *p)
+{
+    return p->orient_gate_deg >= 0 && p->pool_epi_thr >= 0 && p->pool_dist >= 0 && p->pool_orient_deg >= 0 && p->tp_dist >= 0; // (false for NaN)
+}
+
+// ebvo_grow without the generation bump: no captured pair chain ever holds a ground-truth buffer
+static int gt_grow(ebvo_ctx *ctx, Slot &s, GrowBuf &b, size_t bytes)
+{
+    if (bytes <= b.bytes && b.p)
+        return EBVO_OK;
+    EBVO_HIP(ctx, hipStreamSynchronize(s.stream));
+    if (b.p)
+        (void)hipFree(b.p);
+    b.p = nullptr;
+    b.bytes = 0;
+    const size_t want = bytes + bytes / 4 + 256;
+    if (hipMalloc(&b.p, want) != hipSuccess)
+    {
+        (void)hipGetLastError();
+        ctx->last_error = "hipMalloc failed (out of device memory)";
+        return EBVO_ERR_NOMEM;
+    }
+    b.bytes = want;
+    return EBVO_OK;
+}
+
+// The four doubles of a stage (:365-368) from the per-row (n, tp): plain sequential sums in row order, as std::accumulate
+// forms them.  drop_empty: the rows of remove_empty_clusters (:1526).  The integer fields are filled too (host values).
+static void gt_stage_doubles(const int32_t *rows, const uint8_t *focused, int nL, bool drop_empty, ebvo_gt_stage *st)
+{
+    int64_t n_rows = 0, nonempty = 0, with_tp = 0, sum_tp = 0, sum_n = 0;
+    double acc_precision = 0.0, acc_pair = 0.0, acc_n = 0.0;
+    for (int i = 0; i < nL; ++i)
+    {
+        if (!focused[i])
+            continue;
+        const int32_t n = rows[(size_t)i * 2], tp = rows[(size_t)i * 2 + 1];
+        if (drop_empty && n == 0)
+            continue;
+        ++n_rows;
+        if (n > 0)
+        {
+            ++nonempty;
+            with_tp += tp > 0;
+            sum_tp += tp;
+            sum_n += n;
+            const double q = static_cast<double>(tp) / static_cast<double>(n);
+            acc_precision = acc_precision + q;
+            acc_pair = acc_pair + q;
+            acc_n = acc_n + static_cast<double>(n);
+        }
+        else
+            acc_precision = acc_precision + 0.0;
+    }
+    st->rows = n_rows;
+    st->nonempty = nonempty;
+    st->rows_with_tp = with_tp;
+    st->sum_tp = sum_tp;
+    st->sum_n = sum_n;
+    st->recall = static_cast<double>(with_tp) / static_cast<double>(n_rows);
+    st->precision = acc_precision / static_cast<double>(n_rows);
+    st->precision_pair = acc_pair / static_cast<double>(nonempty);
+    st->ambiguity = acc_n / static_cast<double>(nonempty);
+}
+
+static int32_t *gt_stage_rows(Slot &s, int stage) { return (int32_t *)s.gt_rows.p + (size_t)stage * 2 * s.gt_nL; }
+static unsigned long long *gt_stage_tot(Slot &s, int stage) { return (unsigned long long *)s.gt_tot.p + (size_t)stage * 8; }
+
+extern "C" int ebvo_stereo_set_gt(ebvo_ctx *ctx, int slot, const float *disp, int h, int w, ptrdiff_t stride_elems,
+                                  const ebvo_stereo_calib *calib, const ebvo_gt_params *params)
+{
+    Slot *sp;
+    ebvo_gt_params P;
+    ebvo_gt_default_params(&P);
+    if (params)
+        P = *params;
+    // every argument and the slot's state are checked before anything of the slot changes
+    if (!disp || !calib || !gt_params_ok(&P) || get_slot(ctx, slot, &sp))
+        return EBVO_ERR_ARG;
+    Slot &s = *sp;
+    if (!s.have_run || s.in_flight || s.fin_in_flight || s.tq_in_flight)
+        return EBVO_ERR_STATE;
+    if (h != s.cur_h || w != s.cur_w || stride_elems < w)
+        return EBVO_ERR_ARG;
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = drain_fetch(ctx, s)))
+        return rc;
+    const int nL = s.result.n_left, nR = s.result.n_right;
+    const size_t nLz = (size_t)nL;
+    s.gt_armed = false;
+    s.gt_fin_enq = s.gt_fin_done = false;
+    if ((rc = gt_grow(ctx, s, s.gt_disp, sizeof(float) * (size_t)h * w)) || (rc = gt_grow(ctx, s, s.gt_geom, sizeof(double) * 8 * (nLz + 1))) ||
+        (rc = gt_grow(ctx, s, s.gt_flags, 2 * (nLz + 1))) || (rc = gt_grow(ctx, s, s.gt_boxes, gt_boxes_bytes(nR))) ||
+        (rc = gt_grow(ctx, s, s.gt_pool_i32, sizeof(int32_t) * 2 * (nLz + 1))) ||
+        (rc = gt_grow(ctx, s, s.gt_rows, sizeof(int32_t) * 2 * (nLz + 1) * EBVO_GT_NUM_STAGES)) ||
+        (rc = gt_grow(ctx, s, s.gt_tot, sizeof(unsigned long long) * 8 * EBVO_GT_NUM_STAGES)))
+        return rc;
+    hipStream_t st = s.stream;
+    s.gt_nL = nL;
+    s.gt_params = P;
+    s.gt_n_valid = s.gt_n_focused = 0;
+    s.gt_n_pool = 0;
+    s.gt_h_focused.assign(nLz, 0);
+    s.gt_h_pool_rp.assign(nLz + 1, 0);
+    double *gt_xy = (double *)s.gt_geom.p, *gl = gt_xy + 2 * nLz, *gr = gl + 3 * nLz;
+    uint8_t *valid = (uint8_t *)s.gt_flags.p, *focused = valid + nLz;
+    int32_t *cnt = (int32_t *)s.gt_pool_i32.p, *prp = cnt + nLz + 1;
+    EBVO_HIP(ctx, hipMemsetAsync(s.gt_rows.p, 0, sizeof(int32_t) * 2 * (nLz + 1) * EBVO_GT_NUM_STAGES, st));
+    EBVO_HIP(ctx, hipMemsetAsync(s.gt_tot.p, 0, sizeof(unsigned long long) * 8 * EBVO_GT_NUM_STAGES, st));
+    if (nL > 0)
+    {
+        EBVO_HIP(ctx, hipMemcpy2DAsync(s.gt_disp.p, sizeof(float) * (size_t)w, disp, sizeof(float) * (size_t)stride_elems,
+                                       sizeof(float) * (size_t)w, (size_t)h, hipMemcpyHostToDevice, st));
+        std::vector<uint8_t> h_valid(nLz);
+        if ((rc = gt_locate_enqueue(ctx, s, s.im[0].edges, nL, (const float *)s.gt_disp.p, h, w, w, calib, P.orient_gate_deg, valid,
+                                    gt_xy, gl, gr)) ||
+            (rc = gt_boxes_enqueue(ctx, s, s.im[1].edges, nR, s.gt_boxes.p)) ||
+            (rc = gt_pool_enqueue(ctx, s, false, s.im[0].edges, nL, s.im[1].edges, nR, (const double *)s.lines.p, gt_xy, valid,
+                                  s.gt_boxes.p, &P, cnt, nullptr, nullptr, nullptr)) ||
+            (rc = ebvo_device_scan(ctx, s, cnt, prp, nL, nullptr, 1, nL + 1)))
+            return rc;
+        EBVO_HIP(ctx, hipMemcpyAsync(s.gt_h_pool_rp.data(), prp, sizeof(int32_t) * (nLz + 1), hipMemcpyDeviceToHost, st));
+        EBVO_HIP(ctx, hipMemcpyAsync(h_valid.data(), valid, nLz, hipMemcpyDeviceToHost, st));
+        EBVO_HIP(ctx, hipStreamSynchronize(st));
+        const int64_t n_pool = s.gt_h_pool_rp[nLz];
+        if ((rc = gt_grow(ctx, s, s.gt_pool_idx, sizeof(int32_t) * ((size_t)n_pool + 1))))
+            return rc;
+        if ((rc = gt_pool_enqueue(ctx, s, true, s.im[0].edges, nL, s.im[1].edges, nR, (const double *)s.lines.p, gt_xy, valid,
+                                  s.gt_boxes.p, &P, cnt, prp, (int32_t *)s.gt_pool_idx.p, focused)) ||
+            (rc = gt_census_enqueue(ctx, s, s.im[0].edges, nL, s.im[1].edges, nR, (const double *)s.lines.p, gt_xy, focused,
+                                    s.gt_boxes.p, &s.params, P.tp_dist, gt_stage_rows(s, EBVO_GT_EPIPOLAR),
+                                    gt_stage_rows(s, EBVO_GT_DISPARITY), gt_stage_rows(s, EBVO_GT_ORIENTATION))))
+            return rc;
+        for (int k = EBVO_GT_EPIPOLAR; k <= EBVO_GT_ORIENTATION; ++k)
+            if ((rc = gt_totals_enqueue(ctx, s, gt_stage_rows(s, k), focused, nL, gt_stage_tot(s, k))))
+                return rc;
+        // the NCC stage of a chain without SIFT (:1427): the resident CSR with the run's keep flags
+        if ((rc = gt_rows_enqueue(ctx, s, (const int32_t *)s.row_ptr.p, nullptr, (const int32_t *)s.col_idx.p, s.im[1].edges,
+                                  (const uint8_t *)s.keep.p, gt_xy, focused, nL, P.tp_dist, gt_stage_rows(s, EBVO_GT_NCC),
+                                  gt_stage_tot(s, EBVO_GT_NCC))))
+            return rc;
+        EBVO_HIP(ctx, hipMemcpyAsync(s.gt_h_focused.data(), focused, nLz, hipMemcpyDeviceToHost, st));
+        EBVO_HIP(ctx, hipStreamSynchronize(st));
+        for (size_t i = 0; i < nLz; ++i)
+        {
+            s.gt_n_valid += h_valid[i] != 0;
+            s.gt_n_focused += s.gt_h_focused[i] != 0;
+        }
+        s.gt_n_pool = n_pool;
+    }
+    else
+        EBVO_HIP(ctx, hipStreamSynchronize(st));
+    s.gt_armed = true;
+    return EBVO_OK;
+}
+
+static int gt_armed_slot(ebvo_ctx *ctx, int slot, Slot **out)
+{
+    if (get_slot(ctx, slot, out))
+        return EBVO_ERR_ARG;
+    Slot &s = **out;
+    if (!s.gt_armed || !s.have_run || s.in_flight || s.fin_in_flight || s.tq_in_flight)
+        return EBVO_ERR_STATE;
+    return EBVO_OK;
+}
+
+extern "C" int ebvo_stereo_gt_size(ebvo_ctx *ctx, int slot, int32_t *n_valid, int32_t *n_focused, int64_t *n_pool)
+{
+    Slot *sp;
+    if (int rc = gt_armed_slot(ctx, slot, &sp))
+        return rc;
+    if (n_valid)
+        *n_valid = sp->gt_n_valid;
+    if (n_focused)
+        *n_focused = sp->gt_n_focused;
+    if (n_pool)
+        *n_pool = sp->gt_n_pool;
+    return EBVO_OK;
+}
+
+extern "C" int ebvo_stereo_gt_fetch(ebvo_ctx *ctx, int slot, int32_t *focused_index, double *gt_xy, double *gamma_left,
+                                    double *gamma_right, int32_t *pool_row_ptr, int32_t *pool_idx)
+{
+    Slot *sp;
+    if (int rc = gt_armed_slot(ctx, slot, &sp))
+        return rc;
+    Slot &s = *sp;
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nLz = (size_t)s.gt_nL;
+    std::vector<double> geom;
+    if ((gt_xy || gamma_left || gamma_right) && nLz)
+    {
+        geom.resize(8 * nLz);
+        EBVO_HIP(ctx, hipMemcpyAsync(geom.data(), s.gt_geom.p, sizeof(double) * 8 * nLz, hipMemcpyDeviceToHost, s.stream));
+    }
+    if (pool_idx && s.gt_n_pool > 0) // rows that are not focused have an empty pool: the list is compact as it stands
+        EBVO_HIP(ctx, hipMemcpyAsync(pool_idx, s.gt_pool_idx.p, sizeof(int32_t) * (size_t)s.gt_n_pool, hipMemcpyDeviceToHost, s.stream));
+    EBVO_HIP(ctx, hipStreamSynchronize(s.stream));
+    size_t q = 0;
+    for (size_t i = 0; i < nLz; ++i)
+    {
+        if (!s.gt_h_focused[i])
+            continue;
+        if (focused_index)
+            focused_index[q] = (int32_t)i;
+        if (pool_row_ptr)
+            pool_row_ptr[q] = s.gt_h_pool_rp[i];
+        if (gt_xy)
+            for (int k = 0; k < 2; ++k)
+                gt_xy[q * 2 + k] = geom[i * 2 + k];
+        if (gamma_left)
+            for (int k = 0; k < 3; ++k)
+                gamma_left[q * 3 + k] = geom[2 * nLz + i * 3 + k];
+        if (gamma_right)
+            for (int k = 0; k < 3; ++k)
+                gamma_right[q * 3 + k] = geom[5 * nLz + i * 3 + k];
+        ++q;
+    }
+    if (pool_row_ptr)
+        pool_row_ptr[q] = (int32_t)s.gt_n_pool;
+    return EBVO_OK;
+}
+
+static bool gt_stage_present(const Slot &s, int stage)
+{
+    switch (stage)
+    {
+    case EBVO_GT_EPIPOLAR: case EBVO_GT_DISPARITY: case EBVO_GT_ORIENTATION: case EBVO_GT_NCC:
+        return true;
+    case EBVO_GT_SIFT: case EBVO_GT_BNB_SIFT:
+        return s.gt_fin_done && s.gt_fin_sift;
+    default:
+        return s.gt_fin_done;
+    }
+}
+
+extern "C" int ebvo_stereo_gt_stage_rows(ebvo_ctx *ctx, int slot, int stage, int32_t *rows_n_tp, int32_t cap_rows)
+{
+    Slot *sp;
+    if (!rows_n_tp || stage < 0 || stage >= EBVO_GT_NUM_STAGES || cap_rows < 0)
+        return EBVO_ERR_ARG;
+    if (int rc = gt_armed_slot(ctx, slot, &sp))
+        return rc;
+    Slot &s = *sp;
+    if (!gt_stage_present(s, stage))
+        return EBVO_ERR_STATE;
+    if (cap_rows < s.gt_nL)
+    {
+        ctx->last_error = "ebvo_stereo_gt_stage_rows: the slot has " + std::to_string(s.gt_nL) + " left edges";
+        return EBVO_ERR_CAPACITY;
+    }
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nLz = (size_t)s.gt_nL;
+    if (!nLz)
+        return EBVO_OK;
+    EBVO_HIP(ctx, hipMemcpyAsync(rows_n_tp, gt_stage_rows(s, stage == EBVO_GT_FINAL ? EBVO_GT_BEST : stage), sizeof(int32_t) * 2 * nLz,
+                                 hipMemcpyDeviceToHost, s.stream));
+    EBVO_HIP(ctx, hipStreamSynchronize(s.stream));
+    return EBVO_OK;
+}
+
+// One number, one source: a stage's integer totals are the device's reductions (gt_totals_kernel); the host walk that
+// forms the four doubles counts the same rows, and a record is only returned when the two agree.  drop_empty: the rows
+// of Final are Best's non-empty rows.
+static int gt_totals_agree(ebvo_ctx *ctx, const ebvo_gt_stage &g, const unsigned long long *t, bool drop_empty)
+{
+    const int64_t dev[5] = {(int64_t)(drop_empty ? t[1] : t[0]), (int64_t)t[1], (int64_t)t[2], (int64_t)t[3], (int64_t)t[4]};
+    if (dev[0] == g.rows && dev[1] == g.nonempty && dev[2] == g.rows_with_tp && dev[3] == g.sum_tp && dev[4] == g.sum_n)
+        return EBVO_OK;
+    ctx->last_error = "ground-truth stage " + std::to_string(g.stage) + ": the device totals differ from the per-row counts";
+    return EBVO_ERR_HIP;
+}
+
+extern "C" int ebvo_stereo_gt_metrics(ebvo_ctx *ctx, int slot, ebvo_gt_stage *stages)
+{
+    Slot *sp;
+    if (!stages)
+        return EBVO_ERR_ARG;
+    if (int rc = gt_armed_slot(ctx, slot, &sp))
+        return rc;
+    Slot &s = *sp;
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nLz = (size_t)s.gt_nL;
+    std::vector<int32_t> rows(2 * nLz * EBVO_GT_NUM_STAGES + 1);
+    std::vector<unsigned long long> tot(8 * EBVO_GT_NUM_STAGES);
+    if (nLz)
+        EBVO_HIP(ctx, hipMemcpyAsync(rows.data(), s.gt_rows.p, sizeof(int32_t) * 2 * nLz * EBVO_GT_NUM_STAGES, hipMemcpyDeviceToHost, s.stream));
+    EBVO_HIP(ctx, hipMemcpyAsync(tot.data(), s.gt_tot.p, sizeof(unsigned long long) * 8 * EBVO_GT_NUM_STAGES, hipMemcpyDeviceToHost, s.stream));
+    EBVO_HIP(ctx, hipStreamSynchronize(s.stream));
+    for (int k = 0; k < EBVO_GT_NUM_STAGES; ++k)
+    {
+        ebvo_gt_stage &g = stages[k];
+        memset(&g, 0, sizeof g);
+        g.stage = k;
+        if (!gt_stage_present(s, k))
+            continue;
+        g.present = 1;
+        const int src = k == EBVO_GT_FINAL ? EBVO_GT_BEST : k; // Final = Best without its empty rows (:1526)
+        gt_stage_doubles(rows.data() + 2 * nLz * src, s.gt_h_focused.data(), s.gt_nL, k == EBVO_GT_FINAL, &g);
+        if (int rc = gt_totals_agree(ctx, g, tot.data() + 8 * src, k == EBVO_GT_FINAL))
+            return rc;
+    }
+    return EBVO_GT_NUM_STAGES;
+}
+
+// The host-array calls run on slot 0's stream with a buffer of their own (gt_up): the slot's pair, its results and its
+// armed state stay as they are (unlike host_slot(), whose callers reuse the pair's buffers).
+static int gt_host_slot(ebvo_ctx *ctx, Slot **out)
+{
+    Slot &s = *ctx->slots[0];
+    if (s.in_flight || s.fin_in_flight || s.tq_in_flight)
+    {
+        ctx->last_error = "slot 0 has submitted work in flight; call ebvo_stereo_wait / ebvo_stereo_finalize_wait / ebvo_temporal_match_wait first";
+        return EBVO_ERR_STATE;
+    }
+    *out = &s;
+    return EBVO_OK;
+}
+
+extern "C" int ebvo_gt_locate(ebvo_ctx *ctx, const ebvo_edge *edges, int n, const float *disp, int h, int w, ptrdiff_t stride_elems,
+                              const ebvo_stereo_calib *calib, const ebvo_gt_params *params, uint8_t *valid, double *gt_xy,
+                              double *gamma_left, double *gamma_right)
+{
+    ebvo_gt_params P;
+    ebvo_gt_default_params(&P);
+    if (params)
+        P = *params;
+    if (!ctx || n < 0 || !disp || !calib || h <= 0 || w <= 0 || stride_elems < w || !gt_params_ok(&P) || (n > 0 && (!edges || !valid)))
+        return EBVO_ERR_ARG;
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    int rc;
+    Slot *sp;
+    if ((rc = gt_host_slot(ctx, &sp)))
+        return rc;
+    Slot &s = *sp;
+    if (n == 0)
+        return EBVO_OK;
+    const size_t nz = (size_t)n;
+    // one buffer of the call's own: edges, the eight doubles per edge, the map, the valid flags
+    const size_t o_geom = sizeof(ebvo_edge) * nz, o_disp = o_geom + sizeof(double) * 8 * nz,
+                 o_valid = o_disp + sizeof(float) * (size_t)h * w;
+    if ((rc = gt_grow(ctx, s, s.gt_up, o_valid + nz)))
+        return rc;
+    hipStream_t st = s.stream;
+    char *base = (char *)s.gt_up.p;
+    double *d_xy = (double *)(base + o_geom), *d_gl = d_xy + 2 * nz, *d_gr = d_gl + 3 * nz;
+    EBVO_HIP(ctx, hipMemcpy2DAsync(base + o_disp, sizeof(float) * (size_t)w, disp, sizeof(float) * (size_t)stride_elems,
+                                   sizeof(float) * (size_t)w, (size_t)h, hipMemcpyHostToDevice, st));
+    EBVO_HIP(ctx, hipMemcpyAsync(base, edges, sizeof(ebvo_edge) * nz, hipMemcpyHostToDevice, st));
+    if ((rc = gt_locate_enqueue(ctx, s, (const ebvo_edge *)base, n, (const float *)(base + o_disp), h, w, w, calib, P.orient_gate_deg,
+                                (uint8_t *)(base + o_valid), d_xy, d_gl, d_gr)))
+        return rc;
+    EBVO_HIP(ctx, hipMemcpyAsync(valid, base + o_valid, nz, hipMemcpyDeviceToHost, st));
+    if (gt_xy)
+        EBVO_HIP(ctx, hipMemcpyAsync(gt_xy, d_xy, sizeof(double) * 2 * nz, hipMemcpyDeviceToHost, st));
+    if (gamma_left)
+        EBVO_HIP(ctx, hipMemcpyAsync(gamma_left, d_gl, sizeof(double) * 3 * nz, hipMemcpyDeviceToHost, st));
+    if (gamma_right)
+        EBVO_HIP(ctx, hipMemcpyAsync(gamma_right, d_gr, sizeof(double) * 3 * nz, hipMemcpyDeviceToHost, st));
+    EBVO_HIP(ctx, hipStreamSynchronize(st));
+    return EBVO_OK;
+}
+
+extern "C" int ebvo_gt_evaluate_rows(ebvo_ctx *ctx, const int32_t *row_ptr, const ebvo_edge *cand_edges, int nL, const uint8_t *focused,
+                                     const double *gt_xy, double tp_dist, int32_t *n_tp, ebvo_gt_stage *stage_out)
+{
+    int64_t np = 0;
+    if (!ctx || !stage_out || !(tp_dist >= 0) || check_csr(row_ptr, nL, &np) || (nL > 0 && (!focused || !gt_xy)) || (np > 0 && !cand_edges))
+        return EBVO_ERR_ARG;
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    int rc;
+    Slot *sp;
+    if ((rc = gt_host_slot(ctx, &sp)))
+        return rc;
+    Slot &s = *sp;
+    memset(stage_out, 0, sizeof *stage_out);
+    stage_out->present = 1;
+    const size_t nLz = (size_t)nL, npz = (size_t)np;
+    // one buffer of the call's own: candidates, gt_xy, the five totals, the (n, tp) rows, row_ptr, focused
+    const size_t o_xy = sizeof(ebvo_edge) * (npz + 1), o_tot = o_xy + sizeof(double) * 2 * (nLz + 1),
+                 o_rows = o_tot + sizeof(unsigned long long) * 8, o_rp = o_rows + sizeof(int32_t) * 2 * (nLz + 1),
+                 o_f = o_rp + sizeof(int32_t) * (nLz + 2), total = o_f + nLz + 8;
+    if ((rc = gt_grow(ctx, s, s.gt_up, total)))
+        return rc;
+    hipStream_t st = s.stream;
+    char *base = (char *)s.gt_up.p;
+    int32_t *d_rows = (int32_t *)(base + o_rows);
+    unsigned long long *d_tot = (unsigned long long *)(base + o_tot);
+    if (np)
+        EBVO_HIP(ctx, hipMemcpyAsync(base, cand_edges, sizeof(ebvo_edge) * npz, hipMemcpyHostToDevice, st));
+    EBVO_HIP(ctx, hipMemcpyAsync(base + o_rp, row_ptr, sizeof(int32_t) * (nLz + 1), hipMemcpyHostToDevice, st));
+    if (nL)
+    {
+        EBVO_HIP(ctx, hipMemcpyAsync(base + o_xy, gt_xy, sizeof(double) * 2 * nLz, hipMemcpyHostToDevice, st));
+        EBVO_HIP(ctx, hipMemcpyAsync(base + o_f, focused, nLz, hipMemcpyHostToDevice, st));
+    }
+    if ((rc = gt_rows_enqueue(ctx, s, (const int32_t *)(base + o_rp), (const ebvo_edge *)base, nullptr, nullptr, nullptr,
+                              (const double *)(base + o_xy), (const uint8_t *)(base + o_f), nL, tp_dist, d_rows, d_tot)))
+        return rc;
+    std::vector<int32_t> rows(2 * nLz + 1);
+    unsigned long long tot[5] = {0, 0, 0, 0, 0};
+    if (nL)
+        EBVO_HIP(ctx, hipMemcpyAsync(rows.data(), d_rows, sizeof(int32_t) * 2 * nLz, hipMemcpyDeviceToHost, st));
+    EBVO_HIP(ctx, hipMemcpyAsync(tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, st));
+    EBVO_HIP(ctx, hipStreamSynchronize(st));
+    gt_stage_doubles(rows.data(), focused, nL, false, stage_out);
+    if ((rc = gt_totals_agree(ctx, *stage_out, tot, false)))
+        return rc;
+    if (n_tp && nL)
+        memcpy(n_tp, rows.data(), sizeof(int32_t) * 2 * nLz);
+    return EBVO_OK;
+}
+
 // the values each developer key accepts; anything else is refused before the context changes at all
 static bool debug_value_ok(int key, int value)
 {
@@ -4204,6 +4670,8 @@ static bool debug_value_ok(int key, int value)
         return value <= EBVO_TOTAL_PARTS;
     case 20:
         return value <= 1 << 20;
+    case 21:
+        return value <= EBVO_DEBUG_MAX_GT_BLOCKS;
     case 0: case 1: case 2: case 3: case 5: case 15: case 16: case 17:
         return true;
     default:
@@ -4234,6 +4702,8 @@ extern "C" int ebvo_debug_set(ebvo_ctx *ctx, int key, int value)
         ctx->cand_blocks = value;
     else if (key == 20)
         ctx->pose_batch = value; // draws per batch of the pose search (same bits for any value)
+    else if (key == 21)
+        ctx->gt_blocks = value; // grid of the ground-truth kernels (same bits for any value)
     else if (key == 13)
         ctx->ingest_stream = value;
     else if (key == 0)

@@ -32,6 +32,10 @@ enum KernelId
     K_SOBEL,
     K_GN_REFINE,
     K_SIFT,
+    K_GT_MISC,   // gt_locate, gt_boxes, gt_totals
+    K_GT_POOL,   // gt_pool<count> and <fill>
+    K_GT_CENSUS,
+    K_GT_ROWS,
     K_NUM
 };
 static_assert(K_NUM <= EBVO_MAX_KERNELS, "grow EBVO_MAX_KERNELS");
@@ -161,6 +165,17 @@ struct Slot
     uint64_t tq_kf_gen = 0;                            // the keyframe (ebvo_ctx::kf_gen) the quads were matched against
     GrowBuf pose_in, pose_geom, pose_order, pose_draw, pose_hyp; // pose search (pose_kernels.hip): uploaded quads, geometry, rank
                                                                  // order, one batch of draws, its hypotheses
+    // ground-truth evaluation (gt_kernels.hip, ebvo_stereo_set_gt): armed = the buffers below describe the resident pair
+    GrowBuf gt_disp, gt_geom, gt_flags, gt_boxes, gt_pool_i32, gt_pool_idx, gt_rows, gt_tot;
+    GrowBuf gt_up; // everything ebvo_gt_locate / ebvo_gt_evaluate_rows need (host-array calls: they touch nothing else of slot 0)
+    bool gt_armed = false;
+    bool gt_fin_enq = false, gt_fin_done = false, gt_fin_sift = false; // the finalisation chain ran (with SIFT) while armed
+    int gt_nL = 0;
+    int32_t gt_n_valid = 0, gt_n_focused = 0;
+    int64_t gt_n_pool = 0;
+    ebvo_gt_params gt_params{};
+    std::vector<uint8_t> gt_h_focused;  // host copy of focused[]
+    std::vector<int32_t> gt_h_pool_rp;  // host copy of the pool's row_ptr
     bool sift_left_valid = false;                      // sift_desc holds the descriptors of every left TOED edge of this pair
     struct TqFinal                                     // the quads that leave the chain (pointers into tq_chain)
     {
@@ -311,6 +326,7 @@ struct ebvo_ctx
     int ingest_stream = 0;      // developer key (ebvo_debug_set 13): 1 = ebvo_stereo_upload_async copies on the upload stream (A/B)
     PoseRng pose_rng;           // ebvo_pose_params::continue_stream continues it across pose calls
     int pose_batch = 0;         // developer key (ebvo_debug_set 20): index pairs per batch of the pose search, 0 = 4096
+    int gt_blocks = 0;          // developer key (ebvo_debug_set 21): most blocks of every ground-truth kernel (0 = 8192; same bits for any value)
     bool screen_audit = false;  // ebvo_toed_screen_audit is running: the screen keeps its gx, gy, |g| (toed_kernels.hip)
     int64_t toed_fallbacks = 0; // hybrid TOED runs repeated on the strict path (more screened candidates than cap_edges)
 
@@ -531,6 +547,25 @@ int sift_distances_enqueue(ebvo_ctx *ctx, Slot &s, const uint8_t *d_left, const 
 int sift_and_flags_enqueue(ebvo_ctx *ctx, Slot &s, const uint8_t *d_a, const uint8_t *d_b, int64_t n, uint8_t *d_out);
 int match_expand_rows_enqueue(ebvo_ctx *ctx, Slot &s, const int32_t *d_row_ptr, int nL, int64_t n_pairs, int32_t *d_pair_left);
 int match_ncc_stored_enqueue(ebvo_ctx *ctx, Slot &s, const float *d_A, const float *d_B, int n, double *d_sim);
+// gt_kernels.hip
+constexpr int EBVO_DEBUG_MAX_GT_BLOCKS = 65536; // most blocks developer key 21 accepts
+int gt_locate_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_E, int n, const float *d_disp, int h, int w, int stride,
+                      const ebvo_stereo_calib *calib, double gate_deg, uint8_t *d_valid, double *d_gt_xy, double *d_gl, double *d_gr);
+size_t gt_boxes_bytes(int nR);
+int gt_boxes_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_R, int nR, void *d_boxes);
+// veridical pool: fill = false counts into d_cnt, fill = true writes d_pool_idx at d_row_ptr and d_focused
+int gt_pool_enqueue(ebvo_ctx *ctx, Slot &s, bool fill, const ebvo_edge *d_L, int nL, const ebvo_edge *d_R, int nR,
+                    const double *d_lines, const double *d_gt_xy, const uint8_t *d_valid, const void *d_boxes,
+                    const ebvo_gt_params *p, int32_t *d_cnt, const int32_t *d_row_ptr, int32_t *d_pool_idx, uint8_t *d_focused);
+// (n, tp) per row under epi / epi & disp / epi & disp & orient (the stages enabled in sp->stage_mask)
+int gt_census_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_L, int nL, const ebvo_edge *d_R, int nR, const double *d_lines,
+                      const double *d_gt_xy, const uint8_t *d_focused, const void *d_boxes, const ebvo_stereo_params *sp,
+                      double tp_dist, int32_t *d_rows0, int32_t *d_rows1, int32_t *d_rows2);
+// (n, tp) per row of a CSR list (candidates d_cand[k], or d_R[d_col_idx[k]]; d_flags optional) and its five integer totals
+int gt_rows_enqueue(ebvo_ctx *ctx, Slot &s, const int32_t *d_row_ptr, const ebvo_edge *d_cand, const int32_t *d_col_idx,
+                    const ebvo_edge *d_R, const uint8_t *d_flags, const double *d_gt_xy, const uint8_t *d_focused, int nL,
+                    double tp_dist, int32_t *d_rows, unsigned long long *d_tot);
+int gt_totals_enqueue(ebvo_ctx *ctx, Slot &s, const int32_t *d_rows, const uint8_t *d_focused, int nL, unsigned long long *d_tot);
 int pose_run(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, const int32_t *d_rp, int n_kf,
              const ebvo_edge *d_cfL, const ebvo_edge *d_cfR, int n, const ebvo_stereo_calib *cal, const ebvo_pose_params *p,
              ebvo_pose_result *res, uint8_t *inlier, double *quad_geom, int32_t *rank_order);

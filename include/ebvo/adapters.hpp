@@ -874,6 +874,58 @@ class MotionTrackerHIP
     ebvo_stereo_calib calib_;
 };
 
+// Frame_Evaluation_Metrics (include/Stereo_Matches.h): what get_Stereo_Edge_Pairs returns on a dataset with ground truth --
+// one (name, recall / precision / pair precision / ambiguity) entry per stage the chain ran, in pipeline order.
+struct StageMetrics
+{
+    double recall = 0.0, precision = 0.0, precision_pair = 0.0, ambiguity = 0.0;
+};
+struct FrameEvaluationMetrics
+{
+    std::vector<std::pair<std::string, StageMetrics>> stages; // preserves pipeline order
+    std::vector<ebvo_gt_stage> totals;                        // the same stages with their integer totals
+    int status = EBVO_OK;
+};
+
+// Find_Stereo_GT_Locations + get_Stereo_Edge_GT_Pairs (src/Stereo_Matches.cpp:133-268) on the pair that ran in `slot`:
+// arms the slot with the CV_32F left disparity map (disp0GT.pfm; step in floats).  Call it before
+// ebvo_stereo_finalize / get_Stereo_Edge_Pairs_resident so that every stage is evaluated, then evaluate() below.
+inline bool set_ground_truth(const Context &c, int slot, const float *disparity, int rows, int cols, ptrdiff_t step_elems,
+                             const ebvo_stereo_calib &calib, const ebvo_gt_params *params = nullptr)
+{
+    return report(c, ebvo_stereo_set_gt(c.get(), slot, disparity, rows, cols, step_elems, &calib, params), "ebvo_stereo_set_gt");
+}
+
+// Evaluate_Stereo_Edge_Correspondences after every stage (:1377-1536) of the armed slot, under the reference's stage names
+// ("NCC" twice, as there); stages the chain did not run are left out.
+inline FrameEvaluationMetrics evaluate(const Context &c, int slot)
+{
+    static const char *const names[EBVO_GT_NUM_STAGES] = {"Epipolar Proximity", "Location Proximity", "Orientation", "SIFT", "NCC",
+                                                          "BNB-NCC", "BNB-SIFT", "Photometric Refinement", "Edge Clustering", "NCC",
+                                                          "Best", "Final"};
+    FrameEvaluationMetrics out;
+    ebvo_gt_stage st[EBVO_GT_NUM_STAGES];
+    const int n = ebvo_stereo_gt_metrics(c.get(), slot, st);
+    if (n < 0)
+    {
+        out.status = n;
+        report(c, n, "ebvo_stereo_gt_metrics");
+        return out;
+    }
+    for (int k = 0; k < n; ++k)
+        if (st[k].present)
+        {
+            StageMetrics m;
+            m.recall = st[k].recall;
+            m.precision = st[k].precision;
+            m.precision_pair = st[k].precision_pair;
+            m.ambiguity = st[k].ambiguity;
+            out.stages.emplace_back(names[st[k].stage], m);
+            out.totals.push_back(st[k]);
+        }
+    return out;
+}
+
 // cv::undistort(src, dst, K, dist) of src/Pipeline.cpp:78-79 on a CV_8UC1 image (K = fx fy cx cy, dist = k1 k2 p1 p2 [k3])
 inline std::vector<uint8_t> undistort(const Context &c, const uint8_t *img, int rows, int cols, ptrdiff_t step, const double K[4],
                                       const std::vector<double> &dist)

@@ -638,6 +638,77 @@ int ebvo_pose_from_quads(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edg
                          const ebvo_pose_params *p, ebvo_pose_result *res, uint8_t *inlier, double *quad_geom,
                          int32_t *rank_order);
 
+/* ---- ground-truth evaluation from a disparity map (the reference's has_gt() == true branch, is_left = true) ------- */
+/* Find_Stereo_GT_Locations (src/Stereo_Matches.cpp:133-200), get_Stereo_Edge_GT_Pairs (:202-268) and
+ * Evaluate_Stereo_Edge_Correspondences (:270-379) after every stage of get_Stereo_Edge_Pairs (:1377-1536).
+ * Two quirks of the reference are kept: Bilinear_Interpolation<float> (include/utility.h:81-104) divides 0 by 0 at an
+ * integer x or y, so such an edge has a NaN disparity and is skipped; and both rays of the GT 3-D point use the LEFT
+ * calibration inverse (:179-180).  The pool tests are strict (< pool_dist, :120), the true-positive test is not
+ * (<= tp_dist, :305).  Accepted ranges: every tolerance >= 0 and not NaN (+inf allowed); anything else EBVO_ERR_ARG. */
+typedef struct ebvo_gt_params
+{
+    double orient_gate_deg; /* 4.0: edges within it of 0, 180 or -180 degrees are skipped (:146) */
+    double pool_epi_thr;    /* 0.5 px to the epipolar line (:227) */
+    double pool_dist;       /* 1.0 px to the GT location (:228) */
+    double pool_orient_deg; /* 5.0 degrees between the orientations, no wrap-around (:124) */
+    double tp_dist;         /* DIST_TO_GT_THRESH 1.0 (include/definitions.h:42) */
+} ebvo_gt_params;
+void ebvo_gt_default_params(ebvo_gt_params *p);
+
+/* the stages in the reference's order (:1382-1535) with the names it gives them in Frame_Evaluation_Metrics */
+enum
+{
+    EBVO_GT_EPIPOLAR = 0, /* "Epipolar Proximity" */
+    EBVO_GT_DISPARITY,    /* "Location Proximity" */
+    EBVO_GT_ORIENTATION,  /* "Orientation" */
+    EBVO_GT_SIFT,         /* "SIFT" */
+    EBVO_GT_NCC,          /* "NCC" */
+    EBVO_GT_BNB_NCC,      /* "BNB-NCC" */
+    EBVO_GT_BNB_SIFT,     /* "BNB-SIFT" */
+    EBVO_GT_REFINE,       /* "Photometric Refinement" */
+    EBVO_GT_CLUSTER,      /* "Edge Clustering" */
+    EBVO_GT_NCC2,         /* "NCC" (post-clustering) */
+    EBVO_GT_BEST,         /* "Best" */
+    EBVO_GT_FINAL,        /* "Final": Best after remove_empty_clusters (:1526) */
+    EBVO_GT_NUM_STAGES
+};
+typedef struct ebvo_gt_stage
+{
+    int32_t stage, present;   /* present = 0: the chain did not run this stage (or not since arming); the rest is zero */
+    int64_t rows, nonempty, rows_with_tp, sum_tp, sum_n; /* exact integer totals over the focused rows */
+    /* :365-368, summed in row order like std::accumulate; 0 / 0 is reported as the NaN it is */
+    double recall, precision, precision_pair, ambiguity;
+} ebvo_gt_stage;
+
+/* Arms `slot` (its pair has run and nothing of it is in flight): uploads the float32 disparity map (h x w as the pair,
+ * stride_elems >= w floats per row), finds the GT locations of all left edges, builds the veridical pool, counts the three
+ * geometric stages and the NCC stage of a chain without SIFT.  ebvo_stereo_finalize on an armed slot evaluates every
+ * later stage as well; the chain's own results do not change.  A new upload or run of the slot disarms it.  Every
+ * argument is checked before any state changes (EBVO_ERR_ARG / EBVO_ERR_STATE leave the slot as it was). */
+int ebvo_stereo_set_gt(ebvo_ctx *ctx, int slot, const float *disp, int h, int w, ptrdiff_t stride_elems,
+                       const ebvo_stereo_calib *calib, const ebvo_gt_params *params);
+int ebvo_stereo_gt_size(ebvo_ctx *ctx, int slot, int32_t *n_valid, int32_t *n_focused, int64_t *n_pool);
+/* What Stereo_Edge_Pairs holds after :253-267, compacted to the focused rows in left-index order: focused_index
+ * [n_focused], gt_xy [n_focused][2], gamma_left / gamma_right [n_focused][3], pool_row_ptr [n_focused + 1], pool_idx
+ * [n_pool] (right edge indices, ascending per row).  Any pointer may be NULL. */
+int ebvo_stereo_gt_fetch(ebvo_ctx *ctx, int slot, int32_t *focused_index, double *gt_xy, double *gamma_left,
+                         double *gamma_right, int32_t *pool_row_ptr, int32_t *pool_idx);
+/* stages[EBVO_GT_NUM_STAGES], indexed by stage id; returns the stage count (> 0) or a negative status */
+int ebvo_stereo_gt_metrics(ebvo_ctx *ctx, int slot, ebvo_gt_stage *stages);
+/* per-row (n, tp) of a stage of the armed slot: rows_n_tp [n_left][2], zero on rows that are not focused.  cap_rows: the
+ * rows the caller's array holds; fewer than the slot's left edges: EBVO_ERR_CAPACITY, nothing written. */
+int ebvo_stereo_gt_stage_rows(ebvo_ctx *ctx, int slot, int stage, int32_t *rows_n_tp, int32_t cap_rows);
+/* The kernels behind it on host arrays.  ebvo_gt_locate: per edge valid [n], gt_xy [n][2] ((-1, -1) when skipped),
+ * gamma_left / gamma_right [n][3].  ebvo_gt_evaluate_rows: a CSR list of candidate edges per left edge, focused [nL]
+ * bytes, gt_xy [nL][2]; n_tp [nL][2] (may be NULL) and the stage record.  Both run on slot 0's stream (EBVO_ERR_STATE
+ * while work of slot 0 is in flight) with a buffer of their own: slot 0's pair, its results and its armed state are not
+ * touched. */
+int ebvo_gt_locate(ebvo_ctx *ctx, const ebvo_edge *edges, int n, const float *disp, int h, int w, ptrdiff_t stride_elems,
+                   const ebvo_stereo_calib *calib, const ebvo_gt_params *params, uint8_t *valid, double *gt_xy,
+                   double *gamma_left, double *gamma_right);
+int ebvo_gt_evaluate_rows(ebvo_ctx *ctx, const int32_t *row_ptr, const ebvo_edge *cand_edges, int nL, const uint8_t *focused,
+                          const double *gt_xy, double tp_dist, int32_t *n_tp, ebvo_gt_stage *stage_out);
+
 /* ---------------------------------------------------------------------------------------- */
 /* Device-resident stereo pipeline: TOED(left) + TOED(right) + candidates + NCC of one pair,  */
 /* images and every intermediate in HBM.  This is what bench.py times.                        */
