@@ -3227,6 +3227,14 @@ extern "C" int ebvo_temporal_set_keyframe(ebvo_ctx *ctx, int slot)
     Slot &s = *sp;
     if (!s.have_final || s.in_flight || s.tq_in_flight)
         return EBVO_ERR_STATE;
+    // a match in flight in ANY slot reads the stored keyframe (ctx->kf_*) on its own stream, and its wait runs the chain
+    // against it: the store is neither overwritten nor re-allocated under it
+    for (const Slot *o : ctx->slots)
+        if (o->tq_in_flight)
+        {
+            ctx->last_error = "a temporal match is in flight in another slot (ebvo_temporal_match_wait first): the keyframe stays";
+            return EBVO_ERR_STATE;
+        }
     EBVO_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc_f = drain_fetch(ctx, s))
         return rc_f;
@@ -3276,6 +3284,8 @@ extern "C" int ebvo_temporal_set_keyframe(ebvo_ctx *ctx, int slot)
         }
         EBVO_HIP(ctx, hipMemcpyAsync(ctx->kf_imgL, s.im[0].img, bytes, hipMemcpyDeviceToDevice, s.stream));
         EBVO_HIP(ctx, hipMemcpyAsync(ctx->kf_imgR, s.im[1].img, bytes, hipMemcpyDeviceToDevice, s.stream));
+        ctx->kf_h = s.cur_h;
+        ctx->kf_w = s.cur_w;
     }
     if (n == 0)
     {
@@ -3302,6 +3312,15 @@ extern "C" int ebvo_temporal_set_keyframe(ebvo_ctx *ctx, int slot)
     return EBVO_OK;
 }
 
+// developer key 22 holds for the launches of temporal_stage0_enqueue and temporal_chain only: the helpers they share with
+// the stereo chain (patches, glue, SIFT, refinement) read Slot::tq_blocks, which is zero outside this scope
+struct TemporalGridScope
+{
+    Slot &s;
+    TemporalGridScope(const ebvo_ctx *ctx, Slot &slot) : s(slot) { s.tq_blocks = ctx->temporal_blocks; }
+    ~TemporalGridScope() { s.tq_blocks = 0; }
+};
+
 // get_Temporal_Edge_Pairs_from_Quads after the NCC filter (src/Temporal_Matches.cpp:196-215) on the candidate quads of the
 // slot's pair: rp / col / quad_kf / sim_l / keep are the CSR candidate lists, the current-frame mate and the keyframe mate
 // of every candidate, its left NCC maximum and the NCC keep flag, as ebvo_temporal_match left them on the device.
@@ -3313,6 +3332,7 @@ static int temporal_chain(ebvo_ctx *ctx, Slot &s, const ebvo_temporal_params &P,
     const size_t nk1 = (size_t)n_kf + 1, nK = (size_t)(n_kept > 0 ? n_kept : 1), ncz = (size_t)n_cf;
     hipStream_t st = s.stream;
     int rc;
+    const TemporalGridScope grid_scope(ctx, s);
     // one buffer, carved: two quad sets (ping-pong), row bookkeeping, refinement and clustering arrays, the final lists
     struct QuadSet
     {
@@ -3513,6 +3533,7 @@ static int temporal_stage0_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_temporal_p
 {
     const int n_kf = ctx->kf_n, n_cf = s.n_final, h = s.cur_h, w = s.cur_w;
     int rc;
+    const TemporalGridScope grid_scope(ctx, s);
     const size_t nk1 = (size_t)n_kf + 1;
     if ((rc = ebvo_grow(ctx, s, s.tq_i32, sizeof(int32_t) * (2 * nk1 + 2) + 16)))
         return rc;
@@ -3586,6 +3607,13 @@ extern "C" int ebvo_temporal_match_submit(ebvo_ctx *ctx, int slot, const ebvo_te
                                           : "the slot has work in flight (wait for it first)";
         return EBVO_ERR_STATE;
     }
+    if (p->stages && (s.cur_h != ctx->kf_h || s.cur_w != ctx->kf_w))
+    {
+        // the refinement of the quads samples the keyframe's images with the current frame's shape: refused before the slot's
+        // earlier quads are dropped (stages = 0 reads stored patches only and works across sizes)
+        ctx->last_error = "stages != 0 needs a current frame of the keyframe's size (the refinement samples both images with one shape)";
+        return EBVO_ERR_STATE;
+    }
     EBVO_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc_f = drain_fetch(ctx, s))
         return rc_f;
@@ -3634,6 +3662,13 @@ extern "C" int ebvo_temporal_match_wait(ebvo_ctx *ctx, int slot, ebvo_temporal_c
     counts->n_kf = n_kf;
     counts->n_cf = n_cf;
     EBVO_HIP(ctx, hipEventSynchronize(s.ev_tq));
+    if (s.tq_kf_gen != ctx->kf_gen)
+    {
+        // second line of defence (ebvo_temporal_set_keyframe refuses while a match is in flight): the lists were formed against
+        // a keyframe that is gone, and the chain below would read the new one's descriptors and images with them
+        ctx->last_error = "the keyframe was replaced while the match was in flight";
+        return EBVO_ERR_STATE;
+    }
     const size_t nk1 = (size_t)n_kf + 1;
     int32_t *rp = (int32_t *)s.tq_i32.p + nk1;
     if (s.tq_empty)
@@ -4672,6 +4707,8 @@ static bool debug_value_ok(int key, int value)
         return value <= 1 << 20;
     case 21:
         return value <= EBVO_DEBUG_MAX_GT_BLOCKS;
+    case 22:
+        return value <= EBVO_DEBUG_MAX_TEMPORAL_BLOCKS;
     case 0: case 1: case 2: case 3: case 5: case 15: case 16: case 17:
         return true;
     default:
@@ -4704,6 +4741,8 @@ extern "C" int ebvo_debug_set(ebvo_ctx *ctx, int key, int value)
         ctx->pose_batch = value; // draws per batch of the pose search (same bits for any value)
     else if (key == 21)
         ctx->gt_blocks = value; // grid of the ground-truth kernels (same bits for any value)
+    else if (key == 22)
+        ctx->temporal_blocks = value; // cap on the temporal path's grids (same bits for any value)
     else if (key == 13)
         ctx->ingest_stream = value;
     else if (key == 0)

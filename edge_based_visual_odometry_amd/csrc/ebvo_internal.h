@@ -108,6 +108,7 @@ constexpr int EBVO_TOTAL_PARTS = 4096;  // most blocks the counting pass of the 
 constexpr int EBVO_MATCH_PARTS = 4096; // most blocks ncc_tile_kernel is launched with
 constexpr int EBVO_DEBUG_MAX_EXACT_BLOCKS = 65536; // most blocks developer keys 11 / 12 accept (exact centre / mags grids)
 constexpr int EBVO_DEBUG_MAX_GN_BLOCKS = 1 << 20; // most workgroups developer key 9 accepts (persistent refinement launch)
+constexpr int EBVO_DEBUG_MAX_TEMPORAL_BLOCKS = 65536; // most blocks developer key 22 accepts (cap on the temporal path's grids)
 
 // Everything that belongs to one HIP stream: a stereo pair in flight (or the workspace of a host-buffer call).
 // What a captured pair chain (ebvo_stereo_submit) depends on besides the slot's buffers: every value a launch carries as an
@@ -193,6 +194,7 @@ struct Slot
     unsigned long long *d_tq_tot = nullptr, *h_tq_tot = nullptr; // [2] device / page-locked: candidate quads, kept quads
     hipEvent_t ev_tq = nullptr;
     bool tq_in_flight = false, tq_empty = false;
+    int tq_blocks = 0; // developer key (ebvo_debug_set 22) while temporal_stage0_enqueue / temporal_chain enqueue on this slot, 0 otherwise
     ebvo_temporal_params tq_params{};
     GrowBuf sift_used; // [2] list lengths, then the lists of the left / right edges that appear in a candidate pair, then nR flag bytes
     GrowBuf sift_img, sift_desc, sift_f32, sift_dist; // SIFT: blurred levels, descriptor banks, per-pair distances (sift_kernels.hip)
@@ -244,6 +246,11 @@ struct Slot
 
 // the image the NCC passes sample: the RAW one (src/Stereo_Matches.cpp:562-563)
 inline const uint8_t *ncc_img(const Slot &s, int k) { return s.undist_pair ? s.im[k].raw : s.im[k].img; }
+// the grid of a grid-stride launch under developer key 22: untouched outside the temporal path (tq_blocks == 0 there)
+inline unsigned temporal_grid_cap(const Slot &s, unsigned blocks)
+{
+    return s.tq_blocks > 0 && blocks > (unsigned)s.tq_blocks ? (unsigned)s.tq_blocks : blocks;
+}
 
 // page-locked host memory owned by the context (results of the resident stage-wise calls), grown on demand
 struct PinnedBuf
@@ -277,6 +284,7 @@ struct ebvo_ctx
     uint8_t *kf_Ld = nullptr, *kf_Rd = nullptr; // [n][2][128] SIFT descriptors of the mates (left TOED edge / final right edge)
     uint8_t *kf_imgL = nullptr, *kf_imgR = nullptr; // the keyframe's undistorted images (photometric refinement of the quads)
     size_t kf_img_bytes = 0;
+    int kf_h = 0, kf_w = 0;    // shape of kf_imgL / kf_imgR: the refinement of the quads takes one shape for both frames
     size_t kf_cap = 0;
     bool undist_on = false;    // ebvo_stereo_set_undistort
     ebvo_undistort_params undist{};
@@ -327,6 +335,8 @@ struct ebvo_ctx
     PoseRng pose_rng;           // ebvo_pose_params::continue_stream continues it across pose calls
     int pose_batch = 0;         // developer key (ebvo_debug_set 20): index pairs per batch of the pose search, 0 = 4096
     int gt_blocks = 0;          // developer key (ebvo_debug_set 21): most blocks of every ground-truth kernel (0 = 8192; same bits for any value)
+    int temporal_blocks = 0;    // developer key (ebvo_debug_set 22): most blocks of every grid-stride launch of the temporal path (0 = each
+                                // launch's own cap; same bits for any value).  Slot::tq_blocks carries it while that path enqueues.
     bool screen_audit = false;  // ebvo_toed_screen_audit is running: the screen keeps its gx, gy, |g| (toed_kernels.hip)
     int64_t toed_fallbacks = 0; // hybrid TOED runs repeated on the strict path (more screened candidates than cap_edges)
 

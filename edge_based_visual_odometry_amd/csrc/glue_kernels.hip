@@ -813,7 +813,7 @@ int glue_row_index_enqueue(ebvo_ctx *ctx, Slot &s, const int32_t *d_rp_in, const
     if (nL <= 0)
         return EBVO_OK;
     ProfScope ps(ctx, s, K_MISC);
-    hipLaunchKernelGGL(row_index_kernel, dim3(grid_for(nL)), dim3(256), 0, s.stream, d_rp_in, d_cnt, d_order, d_rp_out, nL, d_idx);
+    hipLaunchKernelGGL(row_index_kernel, dim3(temporal_grid_cap(s, grid_for(nL))), dim3(256), 0, s.stream, d_rp_in, d_cnt, d_order, d_rp_out, nL, d_idx);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
 }
@@ -832,7 +832,7 @@ int glue_gather_enqueue(ebvo_ctx *ctx, Slot &s, const int32_t *d_idx, int64_t n,
     for (int a = 0; a < 2 && g.e_src[a]; ++a, ++G.ne)
         G.e_src[a] = g.e_src[a], G.e_dst[a] = g.e_dst[a];
     ProfScope ps(ctx, s, K_MISC);
-    hipLaunchKernelGGL(gather_kernel, dim3(grid_for(n)), dim3(256), 0, s.stream, G, d_idx, n);
+    hipLaunchKernelGGL(gather_kernel, dim3(temporal_grid_cap(s, grid_for(n))), dim3(256), 0, s.stream, G, d_idx, n);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
 }
@@ -844,7 +844,7 @@ int glue_quad_refine_inputs_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_k
     if (n <= 0)
         return EBVO_OK;
     ProfScope ps(ctx, s, K_MISC);
-    hipLaunchKernelGGL(quad_refine_inputs_kernel, dim3(grid_for(n)), dim3(256), 0, s.stream, d_kfE, d_quad_kf, d_cfE, d_quad_cf, n,
+    hipLaunchKernelGGL(quad_refine_inputs_kernel, dim3(temporal_grid_cap(s, grid_for(n))), dim3(256), 0, s.stream, d_kfE, d_quad_kf, d_cfE, d_quad_cf, n,
                        d_kf_out, d_cf_out, d_init);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
@@ -858,7 +858,7 @@ int glue_quad_apply_refine_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kf
     if (n <= 0)
         return EBVO_OK;
     ProfScope ps(ctx, s, K_MISC);
-    hipLaunchKernelGGL(quad_apply_refine_kernel, dim3(grid_for(n)), dim3(256), 0, s.stream, d_kfL, d_cfL, d_dispL, d_validL, d_kfR,
+    hipLaunchKernelGGL(quad_apply_refine_kernel, dim3(temporal_grid_cap(s, grid_for(n))), dim3(256), 0, s.stream, d_kfL, d_cfL, d_dispL, d_validL, d_kfR,
                        d_cfR, d_dispR, d_validR, n, d_cenL, d_cenR, d_valid);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
@@ -872,7 +872,7 @@ int glue_quad_cluster_post_enqueue(ebvo_ctx *ctx, Slot &s, const int32_t *d_rp_i
     if (nL <= 0)
         return EBVO_OK;
     ProfScope ps(ctx, s, K_MISC);
-    hipLaunchKernelGGL(quad_cluster_post_kernel, dim3(grid_for(nL)), dim3(256), 0, s.stream, d_rp_in, nL, d_new_count,
+    hipLaunchKernelGGL(quad_cluster_post_kernel, dim3(temporal_grid_cap(s, grid_for(nL))), dim3(256), 0, s.stream, d_rp_in, nL, d_new_count,
                        d_cluster_of, d_centres, d_cenL, d_cenR, d_rp_out, d_outL, d_outR, d_src);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
@@ -884,7 +884,7 @@ int glue_bnb_enqueue(ebvo_ctx *ctx, Slot &s, const int32_t *d_row_ptr, int nL, c
     if (nL <= 0)
         return EBVO_OK;
     ProfScope ps(ctx, s, K_MISC);
-    hipLaunchKernelGGL(bnb_kernel, dim3(grid_for(nL)), dim3(256), 0, s.stream, d_row_ptr, nL, d_scores, thr, higher_is_better,
+    hipLaunchKernelGGL(bnb_kernel, dim3(temporal_grid_cap(s, grid_for(nL))), dim3(256), 0, s.stream, d_row_ptr, nL, d_scores, thr, higher_is_better,
                        d_new_count, d_order);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
@@ -921,7 +921,7 @@ int glue_cluster_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_cand, const 
     if (nL <= 0)
         return EBVO_OK;
     ProfScope ps(ctx, s, K_MISC);
-    hipLaunchKernelGGL(cluster_kernel, dim3(grid_for((int64_t)nL * 16)), dim3(256), 0, s.stream, d_cand, d_row_ptr, nL, by_orientation,
+    hipLaunchKernelGGL(cluster_kernel, dim3(temporal_grid_cap(s, grid_for((int64_t)nL * 16))), dim3(256), 0, s.stream, d_cand, d_row_ptr, nL, by_orientation,
                        skip_single, d_new_count, d_centres, d_cluster_of);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
@@ -932,7 +932,7 @@ int glue_rows_from_flags_enqueue(ebvo_ctx *ctx, Slot &s, const int32_t *d_row_pt
 {
     if (nL <= 0)
         return EBVO_OK;
-    hipLaunchKernelGGL(rows_from_flags_kernel, dim3(grid_for(nL)), dim3(256), 0, s.stream, d_row_ptr, nL, d_flags,
+    hipLaunchKernelGGL(rows_from_flags_kernel, dim3(temporal_grid_cap(s, grid_for(nL))), dim3(256), 0, s.stream, d_row_ptr, nL, d_flags,
                        d_new_count, d_order);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;

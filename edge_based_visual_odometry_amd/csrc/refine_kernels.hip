@@ -1456,7 +1456,7 @@ int refine_gn_temporal_enqueue(ebvo_ctx *ctx, Slot &s, const uint8_t *d_imgK, co
     A.counts = A.list[1] + np;
     ProfScope ps(ctx, s, K_GN_REFINE);
     EBVO_HIP(ctx, hipMemsetAsync(A.counts, 0, sizeof(int32_t) * ((size_t)max_iter + 2), s.stream));
-    const unsigned blocks = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    const unsigned blocks = temporal_grid_cap(s, (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096));
     {
         // the current-frame images as packed corner records (intensity + Sobel gradients): one load per sample point
         const dim3 pg((w + 63) / 64, (h + 3) / 4);
@@ -1464,9 +1464,9 @@ int refine_gn_temporal_enqueue(ebvo_ctx *ctx, Slot &s, const uint8_t *d_imgK, co
         if (two)
             hipLaunchKernelGGL(gn_pack_kernel, pg, dim3(256), 0, s.stream, d_imgC2, h, w, w, (uint32_t *)nullptr, rec + npx);
     }
-    hipLaunchKernelGGL(gn2_init_kernel, dim3((unsigned)((n + 31) / 32 < 8192 ? (n + 31) / 32 : 8192)), dim3(256), 0, s.stream, A);
+    const unsigned rblocks = temporal_grid_cap(s, (unsigned)((n + 31) / 32 < 8192 ? (n + 31) / 32 : 8192)); // (developer key 22 caps it on the temporal path)
+    hipLaunchKernelGGL(gn2_init_kernel, dim3(rblocks), dim3(256), 0, s.stream, A);
     const bool rows = n <= GN_ROWS_MAX_PAIRS && !ctx->gn_no_rows; // small batch: eight lanes per item
-    const unsigned rblocks = (unsigned)((n + 31) / 32 < 8192 ? (n + 31) / 32 : 8192);
     if (rows && !ctx->gn_per_iteration_rows) // (developer key 7: the row layout as a launch per iteration, the form before)
         hipLaunchKernelGGL(gn2_rows_persistent_kernel, dim3(rblocks < 1024 ? rblocks : 1024), dim3(256), 0, s.stream, A);
     else

@@ -500,7 +500,7 @@ int sift_descriptors_enqueue(ebvo_ctx *ctx, Slot &s, const float *d_base, int h,
     if (n <= 0)
         return EBVO_OK;
     ProfScope ps(ctx, s, K_SIFT);
-    hipLaunchKernelGGL(sift_desc_kernel, dim3(grid1d((int64_t)n * 2, 64, 1 << 20)), dim3(64), 0, s.stream, d_base, h, w, d_edges,
+    hipLaunchKernelGGL(sift_desc_kernel, dim3(temporal_grid_cap(s, grid1d((int64_t)n * 2, 64, 1 << 20))), dim3(64), 0, s.stream, d_base, h, w, d_edges,
                        n, d_desc_f, d_desc_u8, (const int32_t *)nullptr, (const int32_t *)nullptr);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
@@ -627,7 +627,7 @@ int sift_gather_enqueue(ebvo_ctx *ctx, Slot &s, const uint8_t *d_src, const int3
     if (n <= 0)
         return EBVO_OK;
     ProfScope ps(ctx, s, K_SIFT);
-    hipLaunchKernelGGL(sift_gather_kernel, dim3(grid1d((int64_t)n * 16, 256, 4096)), dim3(256), 0, s.stream, d_src, d_index, n, d_dst);
+    hipLaunchKernelGGL(sift_gather_kernel, dim3(temporal_grid_cap(s, grid1d((int64_t)n * 16, 256, 4096))), dim3(256), 0, s.stream, d_src, d_index, n, d_dst);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
 }
@@ -638,7 +638,7 @@ int sift_distances_enqueue(ebvo_ctx *ctx, Slot &s, const uint8_t *d_left, const 
     if (n_pairs <= 0)
         return EBVO_OK;
     ProfScope ps(ctx, s, K_SIFT);
-    hipLaunchKernelGGL(sift_dist_kernel, dim3(grid1d(n_pairs * 16, 256, 4096)), dim3(256), 0, s.stream, d_left, d_cand,
+    hipLaunchKernelGGL(sift_dist_kernel, dim3(temporal_grid_cap(s, grid1d(n_pairs * 16, 256, 4096))), dim3(256), 0, s.stream, d_left, d_cand,
                        d_pair_left, d_cand_index, n_pairs, thr, d_dist, d_ok);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
@@ -648,7 +648,7 @@ int sift_and_flags_enqueue(ebvo_ctx *ctx, Slot &s, const uint8_t *d_a, const uin
 {
     if (n <= 0)
         return EBVO_OK;
-    hipLaunchKernelGGL(and_flags_kernel, dim3(grid1d(n, 256, 4096)), dim3(256), 0, s.stream, d_a, d_b, n, d_out);
+    hipLaunchKernelGGL(and_flags_kernel, dim3(temporal_grid_cap(s, grid1d(n, 256, 4096))), dim3(256), 0, s.stream, d_a, d_b, n, d_out);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
 }

@@ -544,9 +544,15 @@ typedef struct ebvo_temporal_counts
     int64_t n_final;                       /* quads after the edge clustering */
 } ebvo_temporal_counts;
 void ebvo_temporal_default_params(ebvo_temporal_params *p);
-/* the final mates of `slot` (after ebvo_stereo_finalize) become the keyframe (src/Pipeline.cpp:133-138: frame 0) */
+/* the final mates of `slot` (after ebvo_stereo_finalize) become the keyframe (src/Pipeline.cpp:133-138: frame 0).
+ * The context holds ONE keyframe, and a submitted match reads it until its _wait has returned: while ANY slot of the
+ * context has a temporal match in flight the call returns EBVO_ERR_STATE and the stored keyframe stays as it is. */
 int ebvo_temporal_set_keyframe(ebvo_ctx *ctx, int slot);
-/* quads of the keyframe against the final mates of `slot` */
+/* quads of the keyframe against the final mates of `slot`.
+ * The keyframe and the current frame may differ in size with stages = 0 (the candidate search runs on the current frame's
+ * grid, the NCC on stored patches).  stages = 1 refines every quad on the keyframe's and the current frame's images with
+ * one shape: a current frame of another size than the keyframe's is refused with EBVO_ERR_STATE (ebvo_last_error says
+ * so) before anything of the slot changes -- its earlier quads and final list stay fetchable. */
 int ebvo_temporal_match(ebvo_ctx *ctx, int slot, const ebvo_temporal_params *p, ebvo_temporal_counts *counts);
 /* The same without blocking the caller (see ebvo_stereo_finalize_submit): _submit enqueues the candidate search and the NCC
  * of the stored patches on the slot's stream and returns, _wait returns the counts (and, for stages = 1, runs the rest of
@@ -893,6 +899,9 @@ int ebvo_profile_get(ebvo_ctx *ctx, ebvo_kernel_time *out /* EBVO_MAX_KERNELS */
  *        (tools/gpu_prefix_chain.py).  Measurement only.
  * key 20: index pairs per batch of the pose search (ebvo_temporal_estimate_pose / ebvo_pose_from_quads; 0 = the default,
  *        4096; at most 1 << 20).  Same bits for any value.
+ * key 22: most blocks of every grid-stride launch of ebvo_temporal_match(_submit / _wait) -- grid, candidates, NCC, SIFT,
+ *        glue, refinement, clustering (0 = each launch's own cap; at most 65536).  Same bits for any value; the stereo
+ *        pair's launches are not touched.
  * A negative value, an unknown key or a value outside the key's range returns EBVO_ERR_ARG and changes nothing. */
 int ebvo_debug_set(ebvo_ctx *ctx, int key, int value);
 

@@ -226,8 +226,9 @@ def test_arming_state_and_arguments(ctx):
     with pytest.raises(EbvoError) as ei:
         ctx.debug_set(21, 65537)
     assert ei.value.status == EBVO_ERR_ARG
-    with pytest.raises(EbvoError):
-        ctx.debug_set(22, 1)
+    with pytest.raises(EbvoError) as ei:
+        ctx.debug_set(23, 1)                                      # the first key that does not exist (22 caps the temporal grids)
+    assert ei.value.status == EBVO_ERR_ARG
 
 
 def test_context_destroy_and_recreate_with_gt_buffers():

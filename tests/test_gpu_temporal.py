@@ -103,8 +103,10 @@ def test_temporal_chain_equals_oracle_chain(ctx, undist):
     und = (lambda img, k, d: orc.undistort(img, k, d)) if undist else (lambda img, k, d: img)
     kf_imgs = (und(l0, K, ce["dist"]), und(r0, Kr, ce["dist_right"]))
     cf_imgs = (und(l3, K, ce["dist"]), und(r3, Kr, ce["dist_right"]))
-    ref = oracle_chain.temporal_edge_pairs(kfL, kfR, cfL, cfR, kf_imgs, cf_imgs, q["row_ptr"], q["col_idx"], q["sim_left"],
-                                           q["keep"])
+    # the reference from the mates and the images alone (left patches from the RAW left image): no device output goes in
+    whole = oracle_chain.temporal_reference(kfL, kfR, cfL, cfR, (l0,) + kf_imgs, (l3,) + cf_imgs, w, h)
+    assert oracle_chain.temporal_problems(counts, q, whole) == []
+    ref = whole["final"]
     got = {k: counts[k] for k in ref["counts"]}
     assert got == ref["counts"] and counts["n_final"] > 300 and counts["n_sift"] < counts["n_kept"]
     fin = q["final"]
