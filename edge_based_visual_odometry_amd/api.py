@@ -847,7 +847,8 @@ class Context:
         of the refinements (1 = one thread per pair always / threshold of the eight-lanes layout); 10 = pair chain as a
         hipGraph; 11 / 12 / 17 = grids of the exact centre / mags / NCC tile kernels in blocks; 13 / 14 / 18 = A/B switches;
         15 = bit mask of kernels launched twice, 16 = the chain ends after stage N (measurement only), 20 = draws per batch
-        of the pose search, 21 = most blocks of the ground-truth kernels (same bits for any value): include/ebvo_hip.h.
+        of the pose search, 21 = most blocks of the ground-truth kernels, 22 / 23 = most blocks of every grid-stride launch
+        of the temporal path / of the stereo finalize chain (same bits for any value): include/ebvo_hip.h.
         A value outside the key's range raises EbvoError(EBVO_ERR_ARG) and changes nothing."""
         self._check(self.lib.ebvo_debug_set(self._ctx, key, value), "ebvo_debug_set")
 

@@ -2711,6 +2711,15 @@ static int read_i32(ebvo_ctx *ctx, Slot &s, const int32_t *d, int32_t *h)
     return EBVO_OK;
 }
 
+// developer key 23 holds for the launches ebvo_stereo_finalize_submit enqueues only: the helpers this chain shares with the
+// pair chain, the temporal chain and the host-buffer calls read Slot::fin_blocks, which is zero outside this scope
+struct FinalizeGridScope
+{
+    Slot &s;
+    FinalizeGridScope(const ebvo_ctx *ctx, Slot &slot) : s(slot) { s.fin_blocks = ctx->finalize_blocks; }
+    ~FinalizeGridScope() { s.fin_blocks = 0; }
+};
+
 static int finalize_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_finalize_params *p, const ebvo_stereo_calib *calib)
 {
     const int nL = s.result.n_left, h = s.cur_h, w = s.cur_w;
@@ -2889,6 +2898,7 @@ extern "C" int ebvo_stereo_finalize_submit(ebvo_ctx *ctx, int slot, const ebvo_f
     EBVO_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc_f = drain_fetch(ctx, s))
         return rc_f;
+    const FinalizeGridScope grid_scope(ctx, s);
     s.have_final = s.have_refined = false; // the refinement buffers are reused
     s.tq_n = -1;
     s.tq_final.n = -1;
@@ -4709,6 +4719,8 @@ static bool debug_value_ok(int key, int value)
         return value <= EBVO_DEBUG_MAX_GT_BLOCKS;
     case 22:
         return value <= EBVO_DEBUG_MAX_TEMPORAL_BLOCKS;
+    case EBVO_DEBUG_KEY_FINALIZE_BLOCKS:
+        return value <= EBVO_DEBUG_MAX_FINALIZE_BLOCKS;
     case 0: case 1: case 2: case 3: case 5: case 15: case 16: case 17:
         return true;
     default:
@@ -4743,6 +4755,8 @@ extern "C" int ebvo_debug_set(ebvo_ctx *ctx, int key, int value)
         ctx->gt_blocks = value; // grid of the ground-truth kernels (same bits for any value)
     else if (key == 22)
         ctx->temporal_blocks = value; // cap on the temporal path's grids (same bits for any value)
+    else if (key == EBVO_DEBUG_KEY_FINALIZE_BLOCKS)
+        ctx->finalize_blocks = value; // cap on the stereo finalize chain's grids (same bits for any value)
     else if (key == 13)
         ctx->ingest_stream = value;
     else if (key == 0)

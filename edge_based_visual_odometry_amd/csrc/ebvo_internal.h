@@ -109,6 +109,8 @@ constexpr int EBVO_MATCH_PARTS = 4096; // most blocks ncc_tile_kernel is launche
 constexpr int EBVO_DEBUG_MAX_EXACT_BLOCKS = 65536; // most blocks developer keys 11 / 12 accept (exact centre / mags grids)
 constexpr int EBVO_DEBUG_MAX_GN_BLOCKS = 1 << 20; // most workgroups developer key 9 accepts (persistent refinement launch)
 constexpr int EBVO_DEBUG_MAX_TEMPORAL_BLOCKS = 65536; // most blocks developer key 22 accepts (cap on the temporal path's grids)
+constexpr int EBVO_DEBUG_KEY_FINALIZE_BLOCKS = 23;    // developer key: cap on the grids of the stereo finalize chain
+constexpr int EBVO_DEBUG_MAX_FINALIZE_BLOCKS = 65536; // most blocks developer key 23 accepts
 
 // Everything that belongs to one HIP stream: a stereo pair in flight (or the workspace of a host-buffer call).
 // What a captured pair chain (ebvo_stereo_submit) depends on besides the slot's buffers: every value a launch carries as an
@@ -195,6 +197,7 @@ struct Slot
     hipEvent_t ev_tq = nullptr;
     bool tq_in_flight = false, tq_empty = false;
     int tq_blocks = 0; // developer key (ebvo_debug_set 22) while temporal_stage0_enqueue / temporal_chain enqueue on this slot, 0 otherwise
+    int fin_blocks = 0; // developer key (ebvo_debug_set 23) while ebvo_stereo_finalize_submit enqueues on this slot, 0 otherwise
     ebvo_temporal_params tq_params{};
     GrowBuf sift_used; // [2] list lengths, then the lists of the left / right edges that appear in a candidate pair, then nR flag bytes
     GrowBuf sift_img, sift_desc, sift_f32, sift_dist; // SIFT: blurred levels, descriptor banks, per-pair distances (sift_kernels.hip)
@@ -246,10 +249,12 @@ struct Slot
 
 // the image the NCC passes sample: the RAW one (src/Stereo_Matches.cpp:562-563)
 inline const uint8_t *ncc_img(const Slot &s, int k) { return s.undist_pair ? s.im[k].raw : s.im[k].img; }
-// the grid of a grid-stride launch under developer key 22: untouched outside the temporal path (tq_blocks == 0 there)
-inline unsigned temporal_grid_cap(const Slot &s, unsigned blocks)
+// the grid of a grid-stride launch under developer key 22 (temporal path) or 23 (stereo finalize chain): at most one of the
+// two is non-zero, while its own path enqueues on the slot; everywhere else both are zero and the grid is untouched
+inline unsigned chain_grid_cap(const Slot &s, unsigned blocks)
 {
-    return s.tq_blocks > 0 && blocks > (unsigned)s.tq_blocks ? (unsigned)s.tq_blocks : blocks;
+    const unsigned cap = (unsigned)(s.tq_blocks > 0 ? s.tq_blocks : s.fin_blocks);
+    return cap > 0 && blocks > cap ? cap : blocks;
 }
 
 // page-locked host memory owned by the context (results of the resident stage-wise calls), grown on demand
@@ -337,6 +342,8 @@ struct ebvo_ctx
     int gt_blocks = 0;          // developer key (ebvo_debug_set 21): most blocks of every ground-truth kernel (0 = 8192; same bits for any value)
     int temporal_blocks = 0;    // developer key (ebvo_debug_set 22): most blocks of every grid-stride launch of the temporal path (0 = each
                                 // launch's own cap; same bits for any value).  Slot::tq_blocks carries it while that path enqueues.
+    int finalize_blocks = 0;    // developer key (ebvo_debug_set 23): the same for every grid-stride launch ebvo_stereo_finalize_submit
+                                // enqueues (Slot::fin_blocks); independent of key 22
     bool screen_audit = false;  // ebvo_toed_screen_audit is running: the screen keeps its gx, gy, |g| (toed_kernels.hip)
     int64_t toed_fallbacks = 0; // hybrid TOED runs repeated on the strict path (more screened candidates than cap_edges)
 

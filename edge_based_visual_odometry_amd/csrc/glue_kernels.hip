@@ -813,7 +813,7 @@ int glue_row_index_enqueue(ebvo_ctx *ctx, Slot &s, const int32_t *d_rp_in, const
     if (nL <= 0)
         return EBVO_OK;
     ProfScope ps(ctx, s, K_MISC);
-    hipLaunchKernelGGL(row_index_kernel, dim3(temporal_grid_cap(s, grid_for(nL))), dim3(256), 0, s.stream, d_rp_in, d_cnt, d_order, d_rp_out, nL, d_idx);
+    hipLaunchKernelGGL(row_index_kernel, dim3(chain_grid_cap(s, grid_for(nL))), dim3(256), 0, s.stream, d_rp_in, d_cnt, d_order, d_rp_out, nL, d_idx);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
 }
@@ -832,7 +832,7 @@ int glue_gather_enqueue(ebvo_ctx *ctx, Slot &s, const int32_t *d_idx, int64_t n,
     for (int a = 0; a < 2 && g.e_src[a]; ++a, ++G.ne)
         G.e_src[a] = g.e_src[a], G.e_dst[a] = g.e_dst[a];
     ProfScope ps(ctx, s, K_MISC);
-    hipLaunchKernelGGL(gather_kernel, dim3(temporal_grid_cap(s, grid_for(n))), dim3(256), 0, s.stream, G, d_idx, n);
+    hipLaunchKernelGGL(gather_kernel, dim3(chain_grid_cap(s, grid_for(n))), dim3(256), 0, s.stream, G, d_idx, n);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
 }
@@ -844,7 +844,7 @@ int glue_quad_refine_inputs_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_k
     if (n <= 0)
         return EBVO_OK;
     ProfScope ps(ctx, s, K_MISC);
-    hipLaunchKernelGGL(quad_refine_inputs_kernel, dim3(temporal_grid_cap(s, grid_for(n))), dim3(256), 0, s.stream, d_kfE, d_quad_kf, d_cfE, d_quad_cf, n,
+    hipLaunchKernelGGL(quad_refine_inputs_kernel, dim3(chain_grid_cap(s, grid_for(n))), dim3(256), 0, s.stream, d_kfE, d_quad_kf, d_cfE, d_quad_cf, n,
                        d_kf_out, d_cf_out, d_init);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
@@ -858,7 +858,7 @@ int glue_quad_apply_refine_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kf
     if (n <= 0)
         return EBVO_OK;
     ProfScope ps(ctx, s, K_MISC);
-    hipLaunchKernelGGL(quad_apply_refine_kernel, dim3(temporal_grid_cap(s, grid_for(n))), dim3(256), 0, s.stream, d_kfL, d_cfL, d_dispL, d_validL, d_kfR,
+    hipLaunchKernelGGL(quad_apply_refine_kernel, dim3(chain_grid_cap(s, grid_for(n))), dim3(256), 0, s.stream, d_kfL, d_cfL, d_dispL, d_validL, d_kfR,
                        d_cfR, d_dispR, d_validR, n, d_cenL, d_cenR, d_valid);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
@@ -872,7 +872,7 @@ int glue_quad_cluster_post_enqueue(ebvo_ctx *ctx, Slot &s, const int32_t *d_rp_i
     if (nL <= 0)
         return EBVO_OK;
     ProfScope ps(ctx, s, K_MISC);
-    hipLaunchKernelGGL(quad_cluster_post_kernel, dim3(temporal_grid_cap(s, grid_for(nL))), dim3(256), 0, s.stream, d_rp_in, nL, d_new_count,
+    hipLaunchKernelGGL(quad_cluster_post_kernel, dim3(chain_grid_cap(s, grid_for(nL))), dim3(256), 0, s.stream, d_rp_in, nL, d_new_count,
                        d_cluster_of, d_centres, d_cenL, d_cenR, d_rp_out, d_outL, d_outR, d_src);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
@@ -884,7 +884,7 @@ int glue_bnb_enqueue(ebvo_ctx *ctx, Slot &s, const int32_t *d_row_ptr, int nL, c
     if (nL <= 0)
         return EBVO_OK;
     ProfScope ps(ctx, s, K_MISC);
-    hipLaunchKernelGGL(bnb_kernel, dim3(temporal_grid_cap(s, grid_for(nL))), dim3(256), 0, s.stream, d_row_ptr, nL, d_scores, thr, higher_is_better,
+    hipLaunchKernelGGL(bnb_kernel, dim3(chain_grid_cap(s, grid_for(nL))), dim3(256), 0, s.stream, d_row_ptr, nL, d_scores, thr, higher_is_better,
                        d_new_count, d_order);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
@@ -896,7 +896,7 @@ int glue_keep_best_enqueue(ebvo_ctx *ctx, Slot &s, const int32_t *d_row_ptr, int
     if (nL <= 0)
         return EBVO_OK;
     ProfScope ps(ctx, s, K_MISC);
-    hipLaunchKernelGGL(keep_best_kernel, dim3(grid_for(nL)), dim3(256), 0, s.stream, d_row_ptr, nL, d_scores, d_new_count,
+    hipLaunchKernelGGL(keep_best_kernel, dim3(chain_grid_cap(s, grid_for(nL))), dim3(256), 0, s.stream, d_row_ptr, nL, d_scores, d_new_count,
                        d_order);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
@@ -908,7 +908,7 @@ int glue_shift_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_cand, const do
     if (n <= 0)
         return EBVO_OK;
     ProfScope ps(ctx, s, K_MISC);
-    hipLaunchKernelGGL(shift_kernel, dim3(grid_for(n)), dim3(256), 0, s.stream, d_cand, d_lines, d_pair_left, DevCount{n, d_n},
+    hipLaunchKernelGGL(shift_kernel, dim3(chain_grid_cap(s, grid_for(n))), dim3(256), 0, s.stream, d_cand, d_lines, d_pair_left, DevCount{n, d_n},
                        d_out);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
@@ -921,7 +921,7 @@ int glue_cluster_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_cand, const 
     if (nL <= 0)
         return EBVO_OK;
     ProfScope ps(ctx, s, K_MISC);
-    hipLaunchKernelGGL(cluster_kernel, dim3(temporal_grid_cap(s, grid_for((int64_t)nL * 16))), dim3(256), 0, s.stream, d_cand, d_row_ptr, nL, by_orientation,
+    hipLaunchKernelGGL(cluster_kernel, dim3(chain_grid_cap(s, grid_for((int64_t)nL * 16))), dim3(256), 0, s.stream, d_cand, d_row_ptr, nL, by_orientation,
                        skip_single, d_new_count, d_centres, d_cluster_of);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
@@ -932,7 +932,7 @@ int glue_rows_from_flags_enqueue(ebvo_ctx *ctx, Slot &s, const int32_t *d_row_pt
 {
     if (nL <= 0)
         return EBVO_OK;
-    hipLaunchKernelGGL(rows_from_flags_kernel, dim3(temporal_grid_cap(s, grid_for(nL))), dim3(256), 0, s.stream, d_row_ptr, nL, d_flags,
+    hipLaunchKernelGGL(rows_from_flags_kernel, dim3(chain_grid_cap(s, grid_for(nL))), dim3(256), 0, s.stream, d_row_ptr, nL, d_flags,
                        d_new_count, d_order);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
@@ -944,7 +944,7 @@ int glue_gather_rows_enqueue(ebvo_ctx *ctx, Slot &s, const int32_t *d_rp_in, con
 {
     if (nL <= 0)
         return EBVO_OK;
-    hipLaunchKernelGGL(gather_rows_kernel, dim3(grid_for(nL)), dim3(256), 0, s.stream, d_rp_in, d_cnt, d_order, d_rp_out, nL,
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(chain_grid_cap(s, grid_for(nL))), dim3(256), 0, s.stream, d_rp_in, d_cnt, d_order, d_rp_out, nL,
                        d_E_src, d_emap, d_E_dst, d_D_src, d_D_dst);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
@@ -955,10 +955,10 @@ int glue_xy_enqueue(ebvo_ctx *ctx, Slot &s, ebvo_edge *d_edges, double *d_xy, in
     if (n <= 0)
         return EBVO_OK;
     if (to_edges)
-        hipLaunchKernelGGL(xy_to_edges_kernel, dim3(grid_for(n)), dim3(256), 0, s.stream, (const double *)d_xy, DevCount{n, d_n},
+        hipLaunchKernelGGL(xy_to_edges_kernel, dim3(chain_grid_cap(s, grid_for(n))), dim3(256), 0, s.stream, (const double *)d_xy, DevCount{n, d_n},
                            d_edges);
     else
-        hipLaunchKernelGGL(edges_to_xy_kernel, dim3(grid_for(n)), dim3(256), 0, s.stream, (const ebvo_edge *)d_edges,
+        hipLaunchKernelGGL(edges_to_xy_kernel, dim3(chain_grid_cap(s, grid_for(n))), dim3(256), 0, s.stream, (const ebvo_edge *)d_edges,
                            DevCount{n, d_n}, d_xy);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
@@ -971,7 +971,7 @@ int glue_final_pairs_enqueue(ebvo_ctx *ctx, Slot &s, const int32_t *d_rp_in, con
 {
     if (nL <= 0)
         return EBVO_OK;
-    hipLaunchKernelGGL(final_pairs_kernel, dim3(grid_for(nL)), dim3(256), 0, s.stream, d_rp_in, d_cnt, d_order, d_rp_out, nL,
+    hipLaunchKernelGGL(final_pairs_kernel, dim3(chain_grid_cap(s, grid_for(nL))), dim3(256), 0, s.stream, d_rp_in, d_cnt, d_order, d_rp_out, nL,
                        d_L, d_cand, d_score, d_left_index, d_left_edge, d_right_edge, d_final_score);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;

@@ -437,7 +437,7 @@ int gt_rows_enqueue(ebvo_ctx *ctx, Slot &s, const int32_t *d_row_ptr, const ebvo
         return EBVO_OK;
     {
         ProfScope ps(ctx, s, K_GT_ROWS);
-        hipLaunchKernelGGL(gt_rows_kernel, dim3(gt_grid(ctx, nL, 32)), dim3(256), 0, s.stream, d_row_ptr, d_cand, d_col_idx, d_R,
+        hipLaunchKernelGGL(gt_rows_kernel, dim3(chain_grid_cap(s, gt_grid(ctx, nL, 32))), dim3(256), 0, s.stream, d_row_ptr, d_cand, d_col_idx, d_R,
                            d_flags, d_gt_xy, d_focused, nL, tp_dist, d_rows);
         EBVO_HIP(ctx, hipGetLastError());
     }
@@ -451,7 +451,7 @@ int gt_totals_enqueue(ebvo_ctx *ctx, Slot &s, const int32_t *d_rows, const uint8
         return EBVO_OK;
     ProfScope ps(ctx, s, K_GT_MISC);
     // sixteen rows per thread: the five integer atomics of a wave land on the same five words, so few waves
-    hipLaunchKernelGGL(gt_totals_kernel, dim3(gt_grid(ctx, nL, 256 * 16)), dim3(256), 0, s.stream, d_rows, d_focused, nL, d_tot);
+    hipLaunchKernelGGL(gt_totals_kernel, dim3(chain_grid_cap(s, gt_grid(ctx, nL, 256 * 16))), dim3(256), 0, s.stream, d_rows, d_focused, nL, d_tot);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
 }

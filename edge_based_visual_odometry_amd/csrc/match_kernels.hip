@@ -2013,8 +2013,8 @@ int match_patches_enqueue(ebvo_ctx *ctx, Slot &s, const uint8_t *d_img, int h, i
     B.norm[0] = d_norm;
     B.flag[0] = d_flag;
     ProfScope ps(ctx, s, K_PATCHES);
-    hipLaunchKernelGGL(sincos_batch_kernel, dim3(temporal_grid_cap(s, blocks_for(cap, 256, 1024)), 1), dim3(256), 0, s.stream, B);
-    hipLaunchKernelGGL(patches_kernel, dim3(temporal_grid_cap(s, blocks_for((int64_t)cap * 16, 256, 4096)), 1), dim3(256), 0, s.stream, B, h, w,
+    hipLaunchKernelGGL(sincos_batch_kernel, dim3(chain_grid_cap(s, blocks_for(cap, 256, 1024)), 1), dim3(256), 0, s.stream, B);
+    hipLaunchKernelGGL(patches_kernel, dim3(chain_grid_cap(s, blocks_for((int64_t)cap * 16, 256, 4096)), 1), dim3(256), 0, s.stream, B, h, w,
                        pitch);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
@@ -2037,9 +2037,9 @@ int match_ncc_pairs_enqueue(ebvo_ctx *ctx, Slot &s, const uint8_t *d_imgR, int h
     double2 *sc = d_sincos_scratch ? (double2 *)d_sincos_scratch : (double2 *)s.sincos.p;
     {
         ProfScope ps(ctx, s, K_MISC);
-        hipLaunchKernelGGL(expand_rows_kernel, dim3(blocks_for(nL, 256, 512)), dim3(256), 0, s.stream, d_row_ptr,
+        hipLaunchKernelGGL(expand_rows_kernel, dim3(chain_grid_cap(s, blocks_for(nL, 256, 512))), dim3(256), 0, s.stream, d_row_ptr,
                            DevN{nL, nullptr}, pair_left, n_pairs);
-        hipLaunchKernelGGL(sincos_edges_kernel, dim3(blocks_for(n_pairs, 256, 1024)), dim3(256), 0, s.stream, d_Rc,
+        hipLaunchKernelGGL(sincos_edges_kernel, dim3(chain_grid_cap(s, blocks_for(n_pairs, 256, 1024))), dim3(256), 0, s.stream, d_Rc,
                            DevN{(int)n_pairs, d_n_pairs}, sc);
     }
     {
@@ -2171,11 +2171,11 @@ int match_temporal_cells_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_cfL,
     const int n_cells = gw * gh;
     const TemporalGrid g = temporal_grid(d_grid, n_cf, n_cells);
     EBVO_HIP(ctx, hipMemsetAsync(g.cnt, 0, sizeof(int32_t) * 2 * (size_t)n_cells, s.stream)); // cnt and fill
-    const unsigned nb = temporal_grid_cap(s, blocks_for(n_cf, 256, 2048));
+    const unsigned nb = chain_grid_cap(s, blocks_for(n_cf, 256, 2048));
     hipLaunchKernelGGL(mate_cells_kernel, dim3(nb), dim3(256), 0, s.stream, d_cfL, d_cfR, n_cf, cell, gw, gh, g.cells, g.cnt);
     hipLaunchKernelGGL(cell_scan_kernel, dim3(1), dim3(256), 0, s.stream, g.cnt, n_cells, g.start);
     hipLaunchKernelGGL(cell_scatter_kernel, dim3(nb), dim3(256), 0, s.stream, g.cells, n_cf, gw, g.start, g.fill, g.list);
-    hipLaunchKernelGGL(cell_sort_kernel, dim3(temporal_grid_cap(s, blocks_for(n_cells, 4, 2048))), dim3(256), 0, s.stream, g.start, n_cells, g.list,
+    hipLaunchKernelGGL(cell_sort_kernel, dim3(chain_grid_cap(s, blocks_for(n_cells, 4, 2048))), dim3(256), 0, s.stream, g.start, n_cells, g.list,
                        g.sorted);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
@@ -2190,7 +2190,7 @@ int match_temporal_candidates_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d
         return EBVO_OK;
     ProfScope ps(ctx, s, d_row_ptr ? K_CAND_FILL : K_CAND_COUNT);
     const TemporalGrid g = temporal_grid(const_cast<void *>(d_grid), n_cf, gw * gh);
-    const unsigned nb = temporal_grid_cap(s, blocks_for(n_kf, 16, 8192)); // 16 mates per block of 256 threads
+    const unsigned nb = chain_grid_cap(s, blocks_for(n_kf, 16, 8192)); // 16 mates per block of 256 threads
     if (d_row_ptr)
         hipLaunchKernelGGL(temporal_candidates_kernel<true>, dim3(nb), dim3(256), 0, s.stream, d_kfL, d_kfR, n_kf, d_cfL, d_cfR,
                            g.cells, g.start, g.sorted, cell, sr, gw, gh, orient_thr, d_cnt, d_row_ptr, d_col_idx, cap);
@@ -2206,7 +2206,7 @@ int match_count_flags_enqueue(ebvo_ctx *ctx, Slot &s, const uint8_t *d_flags, in
 {
     EBVO_HIP(ctx, hipMemsetAsync(d_out, 0, sizeof(unsigned long long), s.stream));
     if (n > 0)
-        hipLaunchKernelGGL(count_flags_kernel, dim3(temporal_grid_cap(s, blocks_for(n, 256, 1024))), dim3(256), 0, s.stream, d_flags, DevCount{n, d_n},
+        hipLaunchKernelGGL(count_flags_kernel, dim3(chain_grid_cap(s, blocks_for(n, 256, 1024))), dim3(256), 0, s.stream, d_flags, DevCount{n, d_n},
                            d_out);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
@@ -2220,7 +2220,7 @@ int match_ncc_quads_indexed_enqueue(ebvo_ctx *ctx, Slot &s, const float *kfLn, c
     if (n_quads <= 0)
         return EBVO_OK;
     ProfScope ps(ctx, s, K_NCC_STORED);
-    hipLaunchKernelGGL(ncc_quads_indexed_kernel, dim3(temporal_grid_cap(s, blocks_for(n_quads * 16, 256, 8192))), dim3(256), 0, s.stream, kfLn, kfLf, kfRn,
+    hipLaunchKernelGGL(ncc_quads_indexed_kernel, dim3(chain_grid_cap(s, blocks_for(n_quads * 16, 256, 8192))), dim3(256), 0, s.stream, kfLn, kfLf, kfRn,
                        kfRf, cfLn, cfLf, cfRn, cfRf, d_quad_kf, d_quad_cf, DevCount{n_quads, d_n_quads}, thr, d_sim_left, d_sim_right,
                        d_keep);
     EBVO_HIP(ctx, hipGetLastError());
@@ -2243,7 +2243,7 @@ int match_expand_rows_enqueue(ebvo_ctx *ctx, Slot &s, const int32_t *d_row_ptr, 
     if (nL <= 0 || n_pairs <= 0)
         return EBVO_OK;
     ProfScope ps(ctx, s, K_MISC);
-    hipLaunchKernelGGL(expand_rows_kernel, dim3(temporal_grid_cap(s, blocks_for(nL, 256, 512))), dim3(256), 0, s.stream, d_row_ptr,
+    hipLaunchKernelGGL(expand_rows_kernel, dim3(chain_grid_cap(s, blocks_for(nL, 256, 512))), dim3(256), 0, s.stream, d_row_ptr,
                        DevN{nL, nullptr}, d_pair_left, n_pairs);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;

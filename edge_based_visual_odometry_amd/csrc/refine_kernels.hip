@@ -1362,13 +1362,13 @@ int refine_gn_stereo_enqueue(ebvo_ctx *ctx, Slot &s, const uint8_t *d_imgL, cons
     A.counts = A.list[1] + np;
     ProfScope ps(ctx, s, K_GN_REFINE);
     EBVO_HIP(ctx, hipMemsetAsync(A.counts, 0, sizeof(int32_t) * ((size_t)max_iter + 2), s.stream));
-    const unsigned blocks = (unsigned)((n_pairs + 255) / 256 < 4096 ? (n_pairs + 255) / 256 : 4096);
+    const unsigned blocks = chain_grid_cap(s, (unsigned)((n_pairs + 255) / 256 < 4096 ? (n_pairs + 255) / 256 : 4096));
     {
         const dim3 pg((w + 63) / 64, (h + 3) / 4);
         hipLaunchKernelGGL(gn_pack_kernel, pg, dim3(256), 0, s.stream, d_imgL, h, w, w, pix4L, (uint4 *)nullptr);
         hipLaunchKernelGGL(gn_pack_kernel, pg, dim3(256), 0, s.stream, d_imgR, h, w, w, (uint32_t *)nullptr, recR);
     }
-    hipLaunchKernelGGL(gn_left_kernel, dim3((unsigned)((nL + 31) / 32 < 8192 ? (nL + 31) / 32 : 8192)), dim3(256), 0,
+    hipLaunchKernelGGL(gn_left_kernel, dim3(chain_grid_cap(s, (unsigned)((nL + 31) / 32 < 8192 ? (nL + 31) / 32 : 8192))), dim3(256), 0,
                        s.stream, A);
     hipLaunchKernelGGL(gn_init_kernel, dim3(blocks), dim3(256), 0, s.stream, A);
     const bool no_rows = ctx->gn_no_rows != 0;                                  // developer keys (ebvo_debug_set 4 / 5)
@@ -1391,7 +1391,7 @@ int refine_gn_stereo_enqueue(ebvo_ctx *ctx, Slot &s, const uint8_t *d_imgL, cons
         // refinement stage at 256 / 512 / 1024 / 8192 blocks: 0.477 / 0.405 / 0.391 / 0.390 ms (EuRoC size), 1.10 / 0.99 / 1.00 / 1.02
         // (KITTI size); with the cursor 256 had been the optimum
         const int64_t bcap = ctx->gn_persist_blocks > 0 ? ctx->gn_persist_blocks : 1024;
-        const unsigned pblocks = (unsigned)((most + 31) / 32 < bcap ? (most + 31) / 32 : bcap);
+        const unsigned pblocks = chain_grid_cap(s, (unsigned)((most + 31) / 32 < bcap ? (most + 31) / 32 : bcap)); // (developer key 23 on the finalize chain)
         if (ctx->gn_per_iteration_rows) // developer key: the row layout as a launch per iteration (the form before the persistent kernel)
             for (int it = 0; it < max_iter; ++it)
                 hipLaunchKernelGGL(gn_iter_rows_kernel, dim3(pblocks), dim3(256), 0, s.stream, A, it, n_pairs > A.rows_below ? 2 : 0);
@@ -1456,7 +1456,7 @@ int refine_gn_temporal_enqueue(ebvo_ctx *ctx, Slot &s, const uint8_t *d_imgK, co
     A.counts = A.list[1] + np;
     ProfScope ps(ctx, s, K_GN_REFINE);
     EBVO_HIP(ctx, hipMemsetAsync(A.counts, 0, sizeof(int32_t) * ((size_t)max_iter + 2), s.stream));
-    const unsigned blocks = temporal_grid_cap(s, (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096));
+    const unsigned blocks = chain_grid_cap(s, (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096));
     {
         // the current-frame images as packed corner records (intensity + Sobel gradients): one load per sample point
         const dim3 pg((w + 63) / 64, (h + 3) / 4);
@@ -1464,7 +1464,7 @@ int refine_gn_temporal_enqueue(ebvo_ctx *ctx, Slot &s, const uint8_t *d_imgK, co
         if (two)
             hipLaunchKernelGGL(gn_pack_kernel, pg, dim3(256), 0, s.stream, d_imgC2, h, w, w, (uint32_t *)nullptr, rec + npx);
     }
-    const unsigned rblocks = temporal_grid_cap(s, (unsigned)((n + 31) / 32 < 8192 ? (n + 31) / 32 : 8192)); // (developer key 22 caps it on the temporal path)
+    const unsigned rblocks = chain_grid_cap(s, (unsigned)((n + 31) / 32 < 8192 ? (n + 31) / 32 : 8192)); // (developer key 22 caps it on the temporal path)
     hipLaunchKernelGGL(gn2_init_kernel, dim3(rblocks), dim3(256), 0, s.stream, A);
     const bool rows = n <= GN_ROWS_MAX_PAIRS && !ctx->gn_no_rows; // small batch: eight lanes per item
     if (rows && !ctx->gn_per_iteration_rows) // (developer key 7: the row layout as a launch per iteration, the form before)
@@ -1487,7 +1487,7 @@ int refine_finalize_pairs_enqueue(ebvo_ctx *ctx, Slot &s, const double *K_left, 
         return EBVO_OK;
     const FinalCalib C = final_calib_host(K_left, K_right, R21, T21);
     ProfScope ps(ctx, s, K_MISC);
-    const unsigned blocks = (unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
+    const unsigned blocks = chain_grid_cap(s, (unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048));
     hipLaunchKernelGGL(finalize_pairs_kernel, dim3(blocks), dim3(256), 0, s.stream, C, d_L, d_R, DevCount{n, d_n}, d_out);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;

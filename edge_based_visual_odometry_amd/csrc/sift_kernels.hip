@@ -500,7 +500,7 @@ int sift_descriptors_enqueue(ebvo_ctx *ctx, Slot &s, const float *d_base, int h,
     if (n <= 0)
         return EBVO_OK;
     ProfScope ps(ctx, s, K_SIFT);
-    hipLaunchKernelGGL(sift_desc_kernel, dim3(temporal_grid_cap(s, grid1d((int64_t)n * 2, 64, 1 << 20))), dim3(64), 0, s.stream, d_base, h, w, d_edges,
+    hipLaunchKernelGGL(sift_desc_kernel, dim3(chain_grid_cap(s, grid1d((int64_t)n * 2, 64, 1 << 20))), dim3(64), 0, s.stream, d_base, h, w, d_edges,
                        n, d_desc_f, d_desc_u8, (const int32_t *)nullptr, (const int32_t *)nullptr);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
@@ -535,7 +535,7 @@ int sift_descriptors_listed_pair_enqueue(ebvo_ctx *ctx, Slot &s, const float *d_
     A.n_list[0] = d_n, A.n_list[1] = d_n + 1;
     A.desc_u8[0] = d_desc0, A.desc_u8[1] = d_desc1;
     A.n_max[0] = n_max0, A.n_max[1] = n_max1;
-    hipLaunchKernelGGL(sift_desc_pair_kernel, dim3(grid1d((int64_t)nm * 2, 64, 4096), 2), dim3(64), 0, s.stream, A, h, w);
+    hipLaunchKernelGGL(sift_desc_pair_kernel, dim3(chain_grid_cap(s, grid1d((int64_t)nm * 2, 64, 4096)), 2), dim3(64), 0, s.stream, A, h, w);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
 }
@@ -593,10 +593,10 @@ int sift_used_edges_enqueue(ebvo_ctx *ctx, Slot &s, const int32_t *d_row_ptr, in
     if (nR > 0)
         EBVO_HIP(ctx, hipMemsetAsync(d_flags, 0, (size_t)nR, s.stream));
     if (n_pairs > 0)
-        hipLaunchKernelGGL(sift_mark_right_kernel, dim3(grid1d(n_pairs, 256, 1024)), dim3(256), 0, s.stream, d_col_idx, n_pairs, d_flags);
+        hipLaunchKernelGGL(sift_mark_right_kernel, dim3(chain_grid_cap(s, grid1d(n_pairs, 256, 1024))), dim3(256), 0, s.stream, d_col_idx, n_pairs, d_flags);
     const int nmax = nL > nR ? nL : nR;
     if (nmax > 0)
-        hipLaunchKernelGGL(sift_used_lists_kernel, dim3(grid1d(nmax, 256, 256), 2), dim3(256), 0, s.stream, d_row_ptr, nL,
+        hipLaunchKernelGGL(sift_used_lists_kernel, dim3(chain_grid_cap(s, grid1d(nmax, 256, 256)), 2), dim3(256), 0, s.stream, d_row_ptr, nL,
                            (const uint8_t *)d_flags, nR, d_counts, d_list_left, d_list_right);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
@@ -627,7 +627,7 @@ int sift_gather_enqueue(ebvo_ctx *ctx, Slot &s, const uint8_t *d_src, const int3
     if (n <= 0)
         return EBVO_OK;
     ProfScope ps(ctx, s, K_SIFT);
-    hipLaunchKernelGGL(sift_gather_kernel, dim3(temporal_grid_cap(s, grid1d((int64_t)n * 16, 256, 4096))), dim3(256), 0, s.stream, d_src, d_index, n, d_dst);
+    hipLaunchKernelGGL(sift_gather_kernel, dim3(chain_grid_cap(s, grid1d((int64_t)n * 16, 256, 4096))), dim3(256), 0, s.stream, d_src, d_index, n, d_dst);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
 }
@@ -638,7 +638,7 @@ int sift_distances_enqueue(ebvo_ctx *ctx, Slot &s, const uint8_t *d_left, const 
     if (n_pairs <= 0)
         return EBVO_OK;
     ProfScope ps(ctx, s, K_SIFT);
-    hipLaunchKernelGGL(sift_dist_kernel, dim3(temporal_grid_cap(s, grid1d(n_pairs * 16, 256, 4096))), dim3(256), 0, s.stream, d_left, d_cand,
+    hipLaunchKernelGGL(sift_dist_kernel, dim3(chain_grid_cap(s, grid1d(n_pairs * 16, 256, 4096))), dim3(256), 0, s.stream, d_left, d_cand,
                        d_pair_left, d_cand_index, n_pairs, thr, d_dist, d_ok);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
@@ -648,7 +648,7 @@ int sift_and_flags_enqueue(ebvo_ctx *ctx, Slot &s, const uint8_t *d_a, const uin
 {
     if (n <= 0)
         return EBVO_OK;
-    hipLaunchKernelGGL(and_flags_kernel, dim3(temporal_grid_cap(s, grid1d(n, 256, 4096))), dim3(256), 0, s.stream, d_a, d_b, n, d_out);
+    hipLaunchKernelGGL(and_flags_kernel, dim3(chain_grid_cap(s, grid1d(n, 256, 4096))), dim3(256), 0, s.stream, d_a, d_b, n, d_out);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
 }

@@ -902,6 +902,12 @@ int ebvo_profile_get(ebvo_ctx *ctx, ebvo_kernel_time *out /* EBVO_MAX_KERNELS */
  * key 22: most blocks of every grid-stride launch of ebvo_temporal_match(_submit / _wait) -- grid, candidates, NCC, SIFT,
  *        glue, refinement, clustering (0 = each launch's own cap; at most 65536).  Same bits for any value; the stereo
  *        pair's launches are not touched.
+ * key 23: most blocks of every grid-stride launch ebvo_stereo_finalize(_submit) enqueues -- SIFT filter, row glue, both
+ *        Best-Nearly-Best tests, shift, the refinement (its persistent launch included), clustering, patches, the final
+ *        lists and output rows, the ground-truth rows of an armed slot (0 = each launch's own cap; at most 65536).  The
+ *        tiled scans and the second NCC pass launch one block per tile / one thread per item and keep their grids.  Same
+ *        bits for any value; the pair chain, the temporal chain and the host-buffer calls are not touched, and keys 22
+ *        and 23 do not see each other.
  * A negative value, an unknown key or a value outside the key's range returns EBVO_ERR_ARG and changes nothing. */
 int ebvo_debug_set(ebvo_ctx *ctx, int key, int value);
 

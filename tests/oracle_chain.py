@@ -45,7 +45,9 @@ def stereo_edge_pairs(left_img, right_img, F, calib=None, bnb_ratio=0.9, ncc_thr
     results of TOED + candidates + first NCC pass if the caller already has them (they are oracle outputs too); ncc_thr is
     then the threshold of the second NCC pass only.  max_iter / tol / huber_delta: the refinement's (ebvo_gn_params).
     left/right_img_undist: the undistorted images TOED and the refinement run on (None: the same as the raw ones, which
-    is the KITTI / ETH3D case: zero distortion)."""
+    is the KITTI / ETH3D case: zero distortion).
+    The result's stage_rows holds the row lengths (np.diff of the row offsets) of every intermediate list, keyed by the
+    EBVO_GT_* stage it is: SIFT and BNB_SIFT (with sift only), NCC, BNB_NCC, REFINE, CLUSTER, NCC2, BEST."""
     lu = left_img if left_img_undist is None else left_img_undist
     ru = right_img if right_img_undist is None else right_img_undist
     if stage1 is None:
@@ -59,6 +61,7 @@ def stereo_edge_pairs(left_img, right_img, F, calib=None, bnb_ratio=0.9, ncc_thr
         lines = orc.epipolar_lines(F, L)
     nL = len(L)
     counts = {}
+    stage_rows = {}
     conf = None
     if sift:
         # augment_Edge_Data (:1410) + apply_SIFT_filtering (:1414), on the UNDISTORTED images: pairs whose smallest
@@ -68,6 +71,7 @@ def stereo_edge_pairs(left_img, right_img, F, calib=None, bnb_ratio=0.9, ncc_thr
         d = orc.sift_min_distances(dl, dr[ci], rp)
         ok = d < sift_thr
         counts["n_sift"] = int(ok.sum())
+        stage_rows["SIFT"] = np.diff(filter_rows(rp, ok))
         keep = (keep.astype(bool) & ok).astype(np.uint8)
         conf = d
     k = keep.astype(bool)
@@ -78,16 +82,20 @@ def stereo_edge_pairs(left_img, right_img, F, calib=None, bnb_ratio=0.9, ncc_thr
     if conf is not None:
         conf = conf[k]
     counts["n_ncc"] = len(cand)
+    stage_rows["NCC"] = np.diff(rp)
     # Best-Nearly-Best on NCC (:1440), then on the SIFT distances (:1452)
     cnt, order = orc.bnb_test(rp, score, bnb_ratio, True)
     idx, rp = csr_select(rp, cnt, order)
     cand, score = cand[idx], score[idx]
+    stage_rows["BNB_NCC"] = np.diff(rp)
     if conf is not None:
         conf = conf[idx]
         cnt, order = orc.bnb_test(rp, conf, bnb_sift, False)
         idx, rp = csr_select(rp, cnt, order)
         cand, score, conf = cand[idx], score[idx], conf[idx]
+        stage_rows["BNB_SIFT"] = np.diff(rp)
     counts["n_bnb"] = len(cand)
+    stage_rows["REFINE"] = np.diff(rp)                                   # the refinement moves candidates, it drops none
     # shift to the epipolar line (:1465), refine along it (:1468)
     cand = orc.epipolar_shift(cand, lines, rp)
     ref = orc.gn_refine_stereo(lu, ru, L, lines, rp, np.stack([cand["x"], cand["y"]], 1), max_iter, tol, huber_delta)
@@ -102,20 +110,23 @@ def stereo_edge_pairs(left_img, right_img, F, calib=None, bnb_ratio=0.9, ncc_thr
     idx, rp = csr_select(rp, cnt, None)
     cand = centres[idx]
     counts["n_clusters"] = len(cand)
+    stage_rows["CLUSTER"] = np.diff(rp)
     # second NCC pass on the cluster centres (:1500), best survivor per row (:1513), rows with a match (:1526)
     _, best2, keep2, _ = orc.ncc_pairs(left_img, right_img, L, cand, rp, ncc_thr)
     k2 = keep2.astype(bool)
     rp = filter_rows(rp, k2)
     cand, best2 = cand[k2], best2[k2]
     counts["n_ncc2"] = len(cand)
+    stage_rows["NCC2"] = np.diff(rp)
     cnt, order = orc.keep_best(rp, best2)
+    stage_rows["BEST"] = np.asarray(cnt, dtype=np.int32).copy()
     idx, _ = csr_select(rp, cnt, order)
     left_index = np.flatnonzero(np.asarray(cnt) > 0).astype(np.int32)
     right, fscore = cand[idx], best2[idx]
     counts["n_final"] = len(right)
     rows16 = orc.finalize_pairs(*calib, L[left_index], right) if calib is not None else None
     return dict(counts=counts, left_index=left_index, right=right, score=fscore, rows=rows16, left=L, right_edges=R,
-                lines=lines)
+                lines=lines, stage_rows={k: np.asarray(v, dtype=np.int32) for k, v in stage_rows.items()})
 
 
 def _select_rows(row_ptr, cnt, order):

@@ -227,7 +227,7 @@ def test_arming_state_and_arguments(ctx):
         ctx.debug_set(21, 65537)
     assert ei.value.status == EBVO_ERR_ARG
     with pytest.raises(EbvoError) as ei:
-        ctx.debug_set(23, 1)                                      # the first key that does not exist (22 caps the temporal grids)
+        ctx.debug_set(24, 1)                                      # the first key that does not exist (22 / 23 cap the chains' grids)
     assert ei.value.status == EBVO_ERR_ARG
 
 
