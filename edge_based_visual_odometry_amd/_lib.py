@@ -28,7 +28,7 @@ STAGE_DISPARITY = 2
 STAGE_ORIENTATION = 4
 STAGE_ALL = 7
 
-MAX_KERNELS = 24
+MAX_KERNELS = 32
 TOED_STRICT, TOED_HYBRID = 0, 1
 
 # every symbol include/ebvo_hip.h declares (checked by tests/test_abi_symbols.py)
@@ -50,6 +50,8 @@ ABI_SYMBOLS = (
     "ebvo_pose_default_params", "ebvo_temporal_estimate_pose", "ebvo_pose_from_quads", "ebvo_temporal_final_size",
     "ebvo_gt_default_params", "ebvo_stereo_set_gt", "ebvo_stereo_gt_size", "ebvo_stereo_gt_fetch", "ebvo_stereo_gt_metrics",
     "ebvo_stereo_gt_stage_rows", "ebvo_gt_locate", "ebvo_gt_evaluate_rows",
+    "ebvo_tgt_default_params", "ebvo_temporal_set_gt", "ebvo_temporal_gt_size", "ebvo_temporal_gt_fetch", "ebvo_temporal_gt_metrics",
+    "ebvo_temporal_gt_flags", "ebvo_tgt_veridical", "ebvo_tgt_evaluate_rows",
 )
 
 
@@ -139,6 +141,17 @@ GT_STAGE_NAMES = ("Epipolar Proximity", "Location Proximity", "Orientation", "SI
 (GT_EPIPOLAR, GT_DISPARITY, GT_ORIENTATION, GT_SIFT, GT_NCC, GT_BNB_NCC, GT_BNB_SIFT, GT_REFINE, GT_CLUSTER, GT_NCC2, GT_BEST,
  GT_FINAL) = range(12)
 GT_NUM_STAGES = 12
+
+
+class TgtParams(C.Structure):
+    _fields_ = [("orient_thr_deg", C.c_double), ("tp_dist", C.c_double), ("search_radius", C.c_double), ("img_margin", C.c_double)]
+
+
+# stage ids (ebvo_hip.h EBVO_TGT_*) and the names of src/Temporal_Matches.cpp:186-215
+TGT_STAGE_NAMES = ("Location Proximity", "Orientation", "NCC", "SIFT", "BNB-NCC", "BNB-SIFT", "Photometric Refinement",
+                   "Edge Clustering")
+(TGT_GRID, TGT_ORIENTATION, TGT_NCC, TGT_SIFT, TGT_BNB_NCC, TGT_BNB_SIFT, TGT_REFINE, TGT_CLUSTER) = range(8)
+TGT_NUM_STAGES = 8
 
 
 class StereoView(C.Structure):
@@ -295,6 +308,16 @@ def load_library() -> C.CDLL:
     lib.ebvo_stereo_gt_stage_rows.argtypes = [vp, i32, i32, vp, i32]
     lib.ebvo_gt_locate.argtypes = [vp, vp, i32, vp, i32, i32, ssz, C.POINTER(StereoCalib), C.POINTER(GtParams), vp, vp, vp, vp]
     lib.ebvo_gt_evaluate_rows.argtypes = [vp, vp, vp, i32, vp, vp, dbl, vp, C.POINTER(GtStage)]
+    lib.ebvo_tgt_default_params.restype = None
+    lib.ebvo_tgt_default_params.argtypes = [C.POINTER(TgtParams)]
+    lib.ebvo_temporal_set_gt.argtypes = [vp, i32, vp, vp, C.POINTER(StereoCalib), C.POINTER(TgtParams), vp, vp]
+    lib.ebvo_temporal_gt_size.argtypes = [vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(i64)]
+    lib.ebvo_temporal_gt_fetch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.ebvo_temporal_gt_metrics.argtypes = [vp, i32, C.POINTER(GtStage)]
+    lib.ebvo_temporal_gt_flags.argtypes = [vp, i32, i32, vp]
+    lib.ebvo_tgt_veridical.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, vp, vp, C.POINTER(StereoCalib),
+                                       C.POINTER(TgtParams), vp, vp, vp, vp, vp, vp, vp, i64, C.POINTER(i64)]
+    lib.ebvo_tgt_evaluate_rows.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, dbl, vp, vp, C.POINTER(GtStage)]
     lib.ebvo_undistort.argtypes = [vp, vp, i32, i32, ssz, vp, vp, i32, vp, ssz]
     lib.ebvo_stereo_set_undistort.argtypes = [vp, C.POINTER(UndistortParams)]
     lib.ebvo_stereo_fetch_end.argtypes = [vp, i32, C.POINTER(StereoView)]

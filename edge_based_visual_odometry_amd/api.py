@@ -46,6 +46,7 @@ class Context:
         if rc != 0:
             raise EbvoError(rc, "ebvo_ctx_create", self.lib.ebvo_strerror(rc).decode())
         self.max_h, self.max_w, self.device = max_h, max_w, device
+        self._tq_n_kf = {}      # slot -> keyframe mates of its completed temporal match (temporal_set_gt sizes its arrays by it)
         if toed_mode is not None:
             self.set_toed_mode(toed_mode)
 
@@ -586,6 +587,7 @@ class Context:
                 setattr(p, k, v)
             else:
                 raise TypeError(f"temporal_match: unknown parameter {k!r}")
+        self._tq_n_kf.pop(slot, None)
         self._check(self.lib.ebvo_temporal_match_submit(self._ctx, slot, C.byref(p)), "ebvo_temporal_match_submit")
         self._tq_stages = getattr(self, "_tq_stages", {})
         self._tq_stages[slot] = int(p.stages)
@@ -593,6 +595,7 @@ class Context:
     def temporal_match_wait(self, slot: int = 0, fetch: bool = True):
         c = _lib.TemporalCounts()
         self._check(self.lib.ebvo_temporal_match_wait(self._ctx, slot, C.byref(c)), "ebvo_temporal_match_wait")
+        self._tq_n_kf[slot] = int(c.n_kf)
         return self._temporal_results(slot, c, self._tq_stages.get(slot, 0), fetch)
 
     def temporal_match(self, slot: int = 0, fetch: bool = True, **kw):
@@ -784,6 +787,131 @@ class Context:
         d = self._gt_stage_dict(g)
         d.pop("name")
         return n_tp, d
+
+    # -- temporal ground truth from a relative pose (build_Veridical_Quads, Evaluate_Temporal_Edge_Pairs_on_Quads) -------
+    def tgt_params(self, **kw) -> _lib.TgtParams:
+        """ebvo_tgt_params: the reference's constants (10 degrees, 2 px, 20 px, 10 px) with `kw` applied."""
+        p = _lib.TgtParams()
+        self.lib.ebvo_tgt_default_params(C.byref(p))
+        fields = {name for name, _ in p._fields_}
+        for k, v in kw.items():
+            if k not in fields:
+                raise TypeError(f"tgt: unknown parameter {k!r}")
+            setattr(p, k, v)
+        return p
+
+    @staticmethod
+    def _pose(R, t):
+        return np.ascontiguousarray(R, dtype=np.float64).reshape(9), np.ascontiguousarray(t, dtype=np.float64).reshape(3)
+
+    def temporal_set_gt(self, R, t, calib, slot: int = 0, kf_gamma=None, kf_is_tp=None, **params) -> dict:
+        """Arm `slot` (its temporal match has completed) with the relative pose keyframe -> current frame
+        (ebvo_temporal_set_gt).  kf_gamma: n_kf x 3 GT points of the keyframe mates or None (their triangulated points);
+        kf_is_tp: n_kf flags or None (all true).  Returns dict(n_kf, n_rows, n_veridical)."""
+        R, t = self._pose(R, t)
+        p, cal = self.tgt_params(**params), self._calib(calib)
+        if kf_gamma is not None:
+            kf_gamma = np.ascontiguousarray(kf_gamma, dtype=np.float64).reshape(-1, 3)
+        if kf_is_tp is not None:
+            kf_is_tp = np.ascontiguousarray(kf_is_tp, dtype=np.uint8)
+        for a in (kf_gamma, kf_is_tp):
+            # every match of this context goes through temporal_match_wait, so a slot without a count has no match to arm
+            if a is not None and len(a) != self._tq_n_kf.get(slot, -1):
+                raise ValueError("temporal_set_gt: kf_gamma / kf_is_tp need one entry per keyframe mate of the slot's "
+                                 "completed temporal match")
+        self._check(self.lib.ebvo_temporal_set_gt(self._ctx, slot, ptr(R), ptr(t), C.byref(cal), C.byref(p), ptr(kf_gamma),
+                                                  ptr(kf_is_tp)), "ebvo_temporal_set_gt")
+        return self.temporal_gt_size(slot)
+
+    def temporal_gt_size(self, slot: int = 0) -> dict:
+        n_kf, n_rows, n_ver = C.c_int32(), C.c_int32(), C.c_int64()
+        self._check(self.lib.ebvo_temporal_gt_size(self._ctx, slot, C.byref(n_kf), C.byref(n_rows), C.byref(n_ver)),
+                    "ebvo_temporal_gt_size")
+        return dict(n_kf=n_kf.value, n_rows=n_rows.value, n_veridical=n_ver.value)
+
+    def temporal_gt_fetch(self, slot: int = 0) -> dict:
+        """Per keyframe mate: in_image, proj_left / proj_right, orient_left / orient_right, and the veridical quads as a CSR
+        (ver_row_ptr, ver_idx: current-frame mate indices)."""
+        sz = self.temporal_gt_size(slot)
+        n, m = sz["n_kf"], sz["n_veridical"]
+        out = dict(in_image=np.zeros(n, dtype=np.uint8), proj_left=np.zeros((n, 2)), proj_right=np.zeros((n, 2)),
+                   orient_left=np.zeros(n), orient_right=np.zeros(n), ver_row_ptr=np.zeros(n + 1, dtype=np.int32),
+                   ver_idx=np.zeros(m, dtype=np.int32))
+        self._check(self.lib.ebvo_temporal_gt_fetch(self._ctx, slot, *(ptr(out[k]) for k in (
+            "in_image", "proj_left", "proj_right", "orient_left", "orient_right", "ver_row_ptr", "ver_idx"))),
+            "ebvo_temporal_gt_fetch")
+        out.update(sz)
+        return out
+
+    @staticmethod
+    def _tgt_stage_dict(g) -> dict:
+        d = {k: getattr(g, k) for k in ("stage", "rows", "nonempty", "rows_with_tp", "sum_tp", "sum_n", "recall", "precision",
+                                        "precision_pair", "ambiguity")}
+        d["name"] = _lib.TGT_STAGE_NAMES[g.stage]
+        d["present"] = bool(g.present)
+        return d
+
+    def temporal_gt_metrics(self, slot: int = 0) -> list:
+        """One dict per stage of get_Temporal_Edge_Pairs_from_Quads under the reference's names; `present` only for
+        Orientation, NCC and (after stages = 1) Edge Clustering."""
+        arr = (_lib.GtStage * _lib.TGT_NUM_STAGES)()
+        rc = self.lib.ebvo_temporal_gt_metrics(self._ctx, slot, arr)
+        if rc < 0:
+            self._check(rc, "ebvo_temporal_gt_metrics")
+        return [self._tgt_stage_dict(arr[k]) for k in range(rc)]
+
+    def temporal_gt_flags(self, stage: int, n: int, slot: int = 0) -> np.ndarray:
+        """b_is_TP per quad of a present stage, in the stage's CSR order; n: the stage's quad count (n_candidates, n_kept
+        or n_final of the match)."""
+        out = np.zeros(n, dtype=np.uint8)
+        self._check(self.lib.ebvo_temporal_gt_flags(self._ctx, slot, stage, ptr(out)), "ebvo_temporal_gt_flags")
+        return out
+
+    def tgt_veridical(self, kf_left, kf_right, cf_left, cf_right, img_w, img_h, R, t, calib, kf_gamma=None, cell_size=15,
+                      **params) -> dict:
+        """build_Veridical_Quads on host arrays (ebvo_tgt_veridical): the arrays of temporal_gt_fetch."""
+        kf_left, kf_right, cf_left, cf_right = (_edges(a) for a in (kf_left, kf_right, cf_left, cf_right))
+        assert len(kf_left) == len(kf_right) and len(cf_left) == len(cf_right)
+        R, t = self._pose(R, t)
+        p, cal = self.tgt_params(**params), self._calib(calib)
+        n, n_cf = len(kf_left), len(cf_left)
+        if kf_gamma is not None:
+            kf_gamma = np.ascontiguousarray(kf_gamma, dtype=np.float64).reshape(-1, 3)
+            assert len(kf_gamma) == n
+        out = dict(in_image=np.zeros(n, dtype=np.uint8), proj_left=np.zeros((n, 2)), proj_right=np.zeros((n, 2)),
+                   orient_left=np.zeros(n), orient_right=np.zeros(n), ver_row_ptr=np.zeros(n + 1, dtype=np.int32))
+        names = ("in_image", "proj_left", "proj_right", "orient_left", "orient_right", "ver_row_ptr")
+        head = (self._ctx, ptr(kf_left), ptr(kf_right), ptr(kf_gamma), n, ptr(cf_left), ptr(cf_right), n_cf, img_w, img_h, cell_size,
+                ptr(R), ptr(t), C.byref(cal), C.byref(p))
+        n_ver = C.c_int64()
+        self._check(self.lib.ebvo_tgt_veridical(*head, *(ptr(out[k]) for k in names), None, 0, C.byref(n_ver)), "ebvo_tgt_veridical")
+        out["ver_idx"] = np.zeros(n_ver.value, dtype=np.int32)
+        if n_ver.value:
+            self._check(self.lib.ebvo_tgt_veridical(*head, *(ptr(out[k]) for k in names), ptr(out["ver_idx"]), n_ver.value,
+                                                    C.byref(n_ver)), "ebvo_tgt_veridical")
+        out["n_veridical"] = n_ver.value
+        return out
+
+    def tgt_evaluate_rows(self, row_ptr, left_centres, right_centres, row_on, proj_left, proj_right, tp_dist: float = 2.0):
+        """Evaluate_Temporal_Edge_Pairs_on_Quads on a CSR list of quad centres per keyframe mate (ebvo_tgt_evaluate_rows).
+        Returns (n_tp [n_kf, 2] int32, is_tp per quad, stage dict)."""
+        row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int32)
+        n_kf = len(row_ptr) - 1
+        L, Rr = _edges(left_centres), _edges(right_centres)
+        pl = np.ascontiguousarray(proj_left, dtype=np.float64).reshape(-1, 2)
+        pr = np.ascontiguousarray(proj_right, dtype=np.float64).reshape(-1, 2)
+        if row_on is not None:
+            row_on = np.ascontiguousarray(row_on, dtype=np.uint8)
+        if n_kf < 0 or len(pl) != n_kf or len(pr) != n_kf or len(L) != int(row_ptr[-1]) or len(Rr) != len(L) or \
+                (row_on is not None and len(row_on) != n_kf):
+            raise ValueError("tgt_evaluate_rows: the arrays do not describe the same rows")
+        n_tp, is_tp, g = np.zeros((n_kf, 2), dtype=np.int32), np.zeros(len(L), dtype=np.uint8), _lib.GtStage()
+        self._check(self.lib.ebvo_tgt_evaluate_rows(self._ctx, ptr(row_ptr), ptr(L), ptr(Rr), n_kf, ptr(row_on), ptr(pl), ptr(pr),
+                                                    float(tp_dist), ptr(n_tp), ptr(is_tp), C.byref(g)), "ebvo_tgt_evaluate_rows")
+        d = {k: getattr(g, k) for k in ("rows", "nonempty", "rows_with_tp", "sum_tp", "sum_n", "recall", "precision",
+                                        "precision_pair", "ambiguity")}
+        d["present"] = bool(g.present)
+        return n_tp, is_tp, d
 
     def stereo_fetch_begin(self, slot: int = 0, what: int = _lib.FETCH_DEFAULT):
         """Enqueue the device-to-host copies of a finished pair's results into the slot's page-locked staging."""

@@ -13,7 +13,7 @@
 const char *const g_kernel_names[K_NUM] = {
     "toed_conv",   "toed_nms",   "toed_rowscan", "toed_compact", "toed_finalize", "toed_exact_centre", "toed_exact_mags", "cand_boxes", "epi_lines",
     "cand_count",  "scan",       "cand_fill",    "edge_patches", "ncc_pairs",     "ncc_stored", "misc", "sobel", "gn_refine", "sift",
-    "gt_misc",     "gt_pool",    "gt_census",    "gt_rows"};
+    "gt_misc",     "gt_pool",    "gt_census",    "gt_rows",      "tgt_project",   "tgt_veridical", "tgt_rows"};
 
 // ------------------------------------------------------------------------------------------
 int ebvo_fail_hip(ebvo_ctx *ctx, hipError_t e, const char *what, const char *file, int line)
@@ -176,7 +176,8 @@ static void slot_destroy(Slot *s)
                        &s->scratch_d,    &s->fetch_pack,   &s->pose_in,        &s->pose_geom,      &s->pose_order,
                        &s->pose_draw,    &s->pose_hyp,       &s->gt_disp,        &s->gt_geom,        &s->gt_flags,
                        &s->gt_boxes,     &s->gt_pool_i32,  &s->gt_pool_idx,    &s->gt_rows,        &s->gt_tot,
-                       &s->gt_up};
+                       &s->gt_up,        &s->tgt_geom,     &s->tgt_i32,        &s->tgt_idx,        &s->tgt_u8,
+                       &s->tgt_rows,     &s->tgt_flags,    &s->tgt_tot,        &s->tgt_up};
     for (GrowBuf *b : bufs)
         free_buf(*b);
     (void)hipFree(s->d_total);
@@ -3628,6 +3629,7 @@ extern "C" int ebvo_temporal_match_submit(ebvo_ctx *ctx, int slot, const ebvo_te
     if (int rc_f = drain_fetch(ctx, s))
         return rc_f;
     s.tq_n = -1;
+    s.tgt_armed = false; // the ground truth was given for the match that is replaced here
     s.tq_n_kf = ctx->kf_n;
     s.tq_kf_gen = ctx->kf_gen;
     s.tq_final = Slot::TqFinal();
@@ -4691,6 +4693,543 @@ extern "C" int ebvo_gt_evaluate_rows(ebvo_ctx *ctx, const int32_t *row_ptr, cons
         return rc;
     if (n_tp && nL)
         memcpy(n_tp, rows.data(), sizeof(int32_t) * 2 * nLz);
+    return EBVO_OK;
+}
+
+// ---- temporal ground truth from a relative pose (tgt_kernels.hip) -------------------------------------------------------
+extern "C" void ebvo_tgt_default_params(ebvo_tgt_params *p)
+{
+    if (!p)
+        return;
+    p->orient_thr_deg = 10.0; // src/Temporal_Matches.cpp:67
+    p->tp_dist = 2.0;         // DIST_TO_GT_THRESH_QUADS, include/definitions.h:43
+    p->search_radius = 20.0;  // 15.0 + DIST_TO_GT_THRESH_QUADS + 3.0, :68
+    p->img_margin = 10.0;     // :69
+}
+
+static bool tgt_params_ok(const ebvo_tgt_params *p)
+{
+    return p->orient_thr_deg >= 0 && p->tp_dist >= 0 && p->search_radius >= 0 && p->img_margin >= 0; // (false for NaN)
+}
+
+// static_cast<int>(std::ceil(radius / cell_size)) (include/Dataset.h:97), saturated as the temporal stage saturates its own
+static int tgt_cell_radius(double radius, int cell)
+{
+    const double sr_d = ceil(radius / cell);
+    return sr_d < (double)(1 << 30) ? (int)sr_d : (1 << 30);
+}
+
+// The four doubles of a stage (:259-282) from the per-row (n, tp), in KEYFRAME INDEX ORDER (the reference's order is that
+// of its `out` vector, which OpenMP scheduling decides; this is its one-thread order).  No rows or no non-empty row: the
+// four zeros of :274-278.
+static void tgt_stage_doubles(const int32_t *rows, const uint8_t *on, int n_kf, ebvo_gt_stage *st)
+{
+    double recall_sum = 0.0, precision_sum = 0.0, ambiguity_sum = 0.0;
+    int64_t n_rows = 0, matched = 0, with_tp = 0, sum_tp = 0, sum_n = 0;
+    for (int i = 0; i < n_kf; ++i)
+    {
+        if (on && !on[i])
+            continue;
+        const int32_t n = rows[(size_t)i * 2], tp = rows[(size_t)i * 2 + 1];
+        recall_sum += (tp >= 1) ? 1.0 : 0.0;
+        precision_sum += (n == 0) ? 0.0 : (static_cast<double>(tp) / static_cast<double>(n));
+        ambiguity_sum += static_cast<double>(n);
+        ++n_rows;
+        matched += n > 0;
+        with_tp += tp > 0;
+        sum_tp += tp;
+        sum_n += n;
+    }
+    st->rows = n_rows;
+    st->nonempty = matched;
+    st->rows_with_tp = with_tp;
+    st->sum_tp = sum_tp;
+    st->sum_n = sum_n;
+    st->recall = st->precision = st->precision_pair = st->ambiguity = 0.0;
+    if (n_rows == 0 || matched == 0)
+        return;
+    st->recall = recall_sum / static_cast<double>(n_rows);
+    st->precision = precision_sum / static_cast<double>(matched);
+    st->precision_pair = st->precision;
+    st->ambiguity = (ambiguity_sum / static_cast<double>(matched)) - 1.0;
+}
+
+// the slot's temporal match is complete, idle and still belongs to the stored keyframe
+static int tgt_matched_slot(ebvo_ctx *ctx, int slot, Slot **out)
+{
+    Slot *sp;
+    if (get_slot(ctx, slot, &sp))
+        return EBVO_ERR_ARG;
+    Slot &s = *sp;
+    if (s.tq_n < 0 || !s.have_final || s.in_flight || s.fin_in_flight || s.tq_in_flight || s.tq_kf_gen != ctx->kf_gen)
+    {
+        ctx->last_error = s.in_flight || s.fin_in_flight || s.tq_in_flight ? "the slot has work in flight (wait for it first)"
+                          : s.tq_n < 0 || !s.have_final                    ? "the slot holds no temporal match (ebvo_temporal_match first)"
+                                                         : "the keyframe was replaced since the slot's quads were matched";
+        return EBVO_ERR_STATE;
+    }
+    *out = sp;
+    return EBVO_OK;
+}
+
+static int tgt_armed_slot(ebvo_ctx *ctx, int slot, Slot **out)
+{
+    if (int rc = tgt_matched_slot(ctx, slot, out))
+        return rc;
+    if (!(*out)->tgt_armed)
+    {
+        ctx->last_error = "the slot is not armed (ebvo_temporal_set_gt after ebvo_temporal_match)";
+        return EBVO_ERR_STATE;
+    }
+    return EBVO_OK;
+}
+
+// the three stages the slot's match leaves behind: the position of their (n, tp) rows, totals and flag segments
+static int tgt_stage_pos(const Slot &s, int stage)
+{
+    if (stage == EBVO_TGT_ORIENTATION)
+        return 0;
+    if (stage == EBVO_TGT_NCC)
+        return 1;
+    if (stage == EBVO_TGT_CLUSTER && s.tq_final.n >= 0)
+        return 2;
+    return -1;
+}
+
+// host prefix of the per-row counts (they come to the host for the sizes anyway); false: more quads than an int32 row offset holds
+static bool tgt_row_offsets(const std::vector<int32_t> &cnt, int n_kf, std::vector<int32_t> &rp, int32_t *n_rows)
+{
+    int64_t run = 0;
+    int32_t rows = 0;
+    rp.resize((size_t)n_kf + 1);
+    for (int i = 0; i < n_kf; ++i)
+    {
+        rp[i] = (int32_t)run;
+        run += cnt[i];
+        rows += cnt[i] > 0;
+        if (run > INT32_MAX)
+            return false;
+    }
+    rp[n_kf] = (int32_t)run;
+    *n_rows = rows;
+    return true;
+}
+
+static bool tgt_pose_ok(const double *R, const double *t, const ebvo_stereo_calib *calib)
+{
+    if (!R || !t || !calib)
+        return false;
+    for (int k = 0; k < 9; ++k)
+        if (std::isnan(R[k]) || std::isnan(calib->K_left[k]) || std::isnan(calib->K_right[k]) || std::isnan(calib->R21[k]))
+            return false;
+    for (int k = 0; k < 3; ++k)
+        if (std::isnan(t[k]) || std::isnan(calib->T21[k]))
+            return false;
+    return true;
+}
+
+extern "C" int ebvo_temporal_set_gt(ebvo_ctx *ctx, int slot, const double R[9], const double t[3], const ebvo_stereo_calib *calib,
+                                    const ebvo_tgt_params *params, const double *kf_gamma, const uint8_t *kf_is_tp)
+{
+    ebvo_tgt_params P;
+    ebvo_tgt_default_params(&P);
+    if (params)
+        P = *params;
+    if (!ctx || !tgt_pose_ok(R, t, calib) || !tgt_params_ok(&P))
+        return EBVO_ERR_ARG;
+    Slot *sp;
+    if (int rc = tgt_matched_slot(ctx, slot, &sp))
+        return rc;
+    Slot &s = *sp;
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    s.tgt_armed = false;
+    const int n_kf = s.tq_n_kf, n_cf = s.n_final;
+    const size_t nz = (size_t)n_kf, nq = (size_t)s.tq_n, nfin = (size_t)(s.tq_final.n > 0 ? s.tq_final.n : 0);
+    int rc;
+    if ((rc = gt_grow(ctx, s, s.tgt_geom, sizeof(double) * 9 * nz + 64)) || (rc = gt_grow(ctx, s, s.tgt_u8, 3 * nz + 64)) ||
+        (rc = gt_grow(ctx, s, s.tgt_i32, sizeof(int32_t) * 2 * (nz + 1))) || (rc = gt_grow(ctx, s, s.tgt_rows, sizeof(int32_t) * 6 * nz + 64)) ||
+        (rc = gt_grow(ctx, s, s.tgt_flags, 2 * nq + nfin + 64)) || (rc = gt_grow(ctx, s, s.tgt_tot, sizeof(unsigned long long) * 8 * 3)))
+        return rc;
+    hipStream_t st = s.stream;
+    double *pl = (double *)s.tgt_geom.p, *pr = pl + 2 * nz, *ol = pr + 2 * nz, *orr = ol + nz, *gamma = orr + nz;
+    uint8_t *in = (uint8_t *)s.tgt_u8.p, *on = in + nz, *is_tp = on + nz;
+    int32_t *cnt = (int32_t *)s.tgt_i32.p, *rp = cnt + nz + 1;
+    EBVO_HIP(ctx, hipMemsetAsync(s.tgt_tot.p, 0, sizeof(unsigned long long) * 8 * 3, st));
+    EBVO_HIP(ctx, hipMemsetAsync(cnt, 0, sizeof(int32_t) * 2 * (nz + 1), st));
+    if (nz)
+    {
+        EBVO_HIP(ctx, hipMemsetAsync(s.tgt_rows.p, 0, sizeof(int32_t) * 6 * nz, st));
+        EBVO_HIP(ctx, hipMemsetAsync(in, 0, 3 * nz, st));
+        if (kf_gamma)
+            EBVO_HIP(ctx, hipMemcpyAsync(gamma, kf_gamma, sizeof(double) * 3 * nz, hipMemcpyHostToDevice, st));
+        if (kf_is_tp)
+            EBVO_HIP(ctx, hipMemcpyAsync(is_tp, kf_is_tp, nz, hipMemcpyHostToDevice, st));
+    }
+    std::vector<int32_t> h_cnt(nz + 1, 0), h_rp;
+    int32_t n_rows = 0;
+    const ebvo_edge *cfL = nullptr, *cfR = nullptr;
+    const bool walk = n_kf > 0 && n_cf > 0 && !s.tq_empty;
+    if (n_kf > 0 &&
+        (rc = tgt_project_enqueue(ctx, s, ctx->kf_L, ctx->kf_R, kf_gamma ? gamma : nullptr, n_kf, R, t, calib, P.img_margin, s.cur_w,
+                                  s.cur_h, in, pl, pr, ol, orr)))
+        return rc;
+    // the current-frame grid of the slot's own match (temporal_stage0_enqueue built it with tq_params.cell_size and nothing
+    // has written it since): read, never written
+    const int cell = s.tq_params.cell_size, gw = (int)(((int64_t)s.cur_w + cell - 1) / cell), gh = (int)(((int64_t)s.cur_h + cell - 1) / cell);
+    const int sr = tgt_cell_radius(P.search_radius, cell);
+    if (walk)
+    {
+        final_mates(s, &cfL, &cfR);
+        if ((rc = tgt_veridical_enqueue(ctx, s, n_kf, in, pl, pr, ol, orr, cfL, cfR, s.tq_cells.p, n_cf, cell, sr, gw, gh, P.tp_dist,
+                                        P.orient_thr_deg, kf_is_tp ? is_tp : nullptr, cnt, nullptr, nullptr, 0, nullptr)))
+            return rc;
+        EBVO_HIP(ctx, hipMemcpyAsync(h_cnt.data(), cnt, sizeof(int32_t) * nz, hipMemcpyDeviceToHost, st));
+    }
+    EBVO_HIP(ctx, hipStreamSynchronize(st));
+    if (!tgt_row_offsets(h_cnt, n_kf, h_rp, &n_rows))
+    {
+        ctx->last_error = "more veridical quads than a 32-bit row offset holds";
+        return EBVO_ERR_CAPACITY;
+    }
+    const int64_t n_ver = h_rp[n_kf];
+    if ((rc = gt_grow(ctx, s, s.tgt_idx, sizeof(int32_t) * (size_t)(n_ver + 1))))
+        return rc;
+    s.tgt_h_on.assign(nz, 0);
+    if (walk) // otherwise the offsets are the zeros written above; h_rp outlives the copy through the synchronise below
+    {
+        EBVO_HIP(ctx, hipMemcpyAsync(rp, h_rp.data(), sizeof(int32_t) * (nz + 1), hipMemcpyHostToDevice, st));
+        if ((rc = tgt_veridical_enqueue(ctx, s, n_kf, in, pl, pr, ol, orr, cfL, cfR, s.tq_cells.p, n_cf, cell, sr, gw, gh, P.tp_dist,
+                                        P.orient_thr_deg, kf_is_tp ? is_tp : nullptr, nullptr, rp, (int32_t *)s.tgt_idx.p, n_ver, on)))
+            return rc;
+        EBVO_HIP(ctx, hipMemcpyAsync(s.tgt_h_on.data(), on, nz, hipMemcpyDeviceToHost, st));
+        // the three lists the match left behind: candidates, candidates with keep, final quads
+        const size_t nk1 = nz + 1, ncz = (size_t)n_cf;
+        const int32_t *q_rp = (const int32_t *)s.tq_i32.p + nk1, *q_col = (const int32_t *)s.tq_cols.p;
+        const uint8_t *q_keep = (const uint8_t *)s.tq_u8.p + ((2 * ncz + 63) & ~(size_t)63);
+        int32_t *rows = (int32_t *)s.tgt_rows.p;
+        uint8_t *flags = (uint8_t *)s.tgt_flags.p;
+        unsigned long long *tot = (unsigned long long *)s.tgt_tot.p;
+        if (s.tq_n > 0 &&
+            ((rc = tgt_rows_enqueue(ctx, s, q_rp, nullptr, nullptr, q_col, cfL, cfR, nullptr, pl, pr, on, n_kf, s.tq_n, P.tp_dist, rows,
+                                    flags, tot)) ||
+             (rc = tgt_rows_enqueue(ctx, s, q_rp, nullptr, nullptr, q_col, cfL, cfR, q_keep, pl, pr, on, n_kf, s.tq_n, P.tp_dist,
+                                    rows + 2 * nz, flags + nq, tot + 8))))
+            return rc;
+        if (s.tq_n == 0) // empty lists: the rows still count (gt_totals over zeroed (n, tp))
+            if ((rc = gt_totals_enqueue(ctx, s, rows, on, n_kf, tot)) || (rc = gt_totals_enqueue(ctx, s, rows + 2 * nz, on, n_kf, tot + 8)))
+                return rc;
+        if (s.tq_final.n >= 0)
+        {
+            const Slot::TqFinal &F = s.tq_final;
+            if (F.n > 0)
+                rc = tgt_rows_enqueue(ctx, s, F.rp, F.L, F.R, nullptr, nullptr, nullptr, nullptr, pl, pr, on, n_kf, F.n, P.tp_dist,
+                                      rows + 4 * nz, flags + 2 * nq, tot + 16);
+            else
+                rc = gt_totals_enqueue(ctx, s, rows + 4 * nz, on, n_kf, tot + 16);
+            if (rc)
+                return rc;
+        }
+        EBVO_HIP(ctx, hipStreamSynchronize(st));
+    }
+    s.tgt_n_kf = n_kf;
+    s.tgt_n_rows = n_rows;
+    s.tgt_n_ver = n_ver;
+    s.tgt_armed = true;
+    return EBVO_OK;
+}
+
+extern "C" int ebvo_temporal_gt_size(ebvo_ctx *ctx, int slot, int32_t *n_kf, int32_t *n_rows, int64_t *n_veridical)
+{
+    Slot *sp;
+    if (int rc = tgt_armed_slot(ctx, slot, &sp))
+        return rc;
+    if (n_kf)
+        *n_kf = sp->tgt_n_kf;
+    if (n_rows)
+        *n_rows = sp->tgt_n_rows;
+    if (n_veridical)
+        *n_veridical = sp->tgt_n_ver;
+    return EBVO_OK;
+}
+
+extern "C" int ebvo_temporal_gt_fetch(ebvo_ctx *ctx, int slot, uint8_t *in_image, double *proj_left, double *proj_right,
+                                      double *orient_left, double *orient_right, int32_t *ver_row_ptr, int32_t *ver_idx)
+{
+    Slot *sp;
+    if (int rc = tgt_armed_slot(ctx, slot, &sp))
+        return rc;
+    Slot &s = *sp;
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nz = (size_t)s.tgt_n_kf;
+    hipStream_t st = s.stream;
+    const double *pl = (const double *)s.tgt_geom.p, *pr = pl + 2 * nz, *ol = pr + 2 * nz, *orr = ol + nz;
+    if (ver_row_ptr)
+        EBVO_HIP(ctx, hipMemcpyAsync(ver_row_ptr, (const int32_t *)s.tgt_i32.p + nz + 1, sizeof(int32_t) * (nz + 1), hipMemcpyDeviceToHost, st));
+    if (nz)
+    {
+        const struct
+        {
+            void *dst;
+            const void *src;
+            size_t bytes;
+        } copies[] = {{in_image, s.tgt_u8.p, nz}, {proj_left, pl, sizeof(double) * 2 * nz}, {proj_right, pr, sizeof(double) * 2 * nz},
+                      {orient_left, ol, sizeof(double) * nz}, {orient_right, orr, sizeof(double) * nz}};
+        for (const auto &c : copies)
+            if (c.dst)
+                EBVO_HIP(ctx, hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, st));
+    }
+    if (ver_idx && s.tgt_n_ver > 0)
+        EBVO_HIP(ctx, hipMemcpyAsync(ver_idx, s.tgt_idx.p, sizeof(int32_t) * (size_t)s.tgt_n_ver, hipMemcpyDeviceToHost, st));
+    EBVO_HIP(ctx, hipStreamSynchronize(st));
+    return EBVO_OK;
+}
+
+// One number, one source, as gt_totals_agree: the device's integer totals and the host walk count the same rows
+static int tgt_totals_agree(ebvo_ctx *ctx, const ebvo_gt_stage &g, const unsigned long long *t)
+{
+    if ((int64_t)t[0] == g.rows && (int64_t)t[1] == g.nonempty && (int64_t)t[2] == g.rows_with_tp && (int64_t)t[3] == g.sum_tp &&
+        (int64_t)t[4] == g.sum_n)
+        return EBVO_OK;
+    ctx->last_error = "temporal ground-truth stage " + std::to_string(g.stage) + ": the device totals differ from the per-row counts";
+    return EBVO_ERR_HIP;
+}
+
+extern "C" int ebvo_temporal_gt_metrics(ebvo_ctx *ctx, int slot, ebvo_gt_stage *stages)
+{
+    Slot *sp;
+    if (!stages)
+        return EBVO_ERR_ARG;
+    if (int rc = tgt_armed_slot(ctx, slot, &sp))
+        return rc;
+    Slot &s = *sp;
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nz = (size_t)s.tgt_n_kf;
+    std::vector<int32_t> rows(6 * nz + 1);
+    unsigned long long tot[24];
+    if (nz)
+        EBVO_HIP(ctx, hipMemcpyAsync(rows.data(), s.tgt_rows.p, sizeof(int32_t) * 6 * nz, hipMemcpyDeviceToHost, s.stream));
+    EBVO_HIP(ctx, hipMemcpyAsync(tot, s.tgt_tot.p, sizeof tot, hipMemcpyDeviceToHost, s.stream));
+    EBVO_HIP(ctx, hipStreamSynchronize(s.stream));
+    for (int k = 0; k < EBVO_TGT_NUM_STAGES; ++k)
+    {
+        ebvo_gt_stage &g = stages[k];
+        memset(&g, 0, sizeof g);
+        g.stage = k;
+        const int pos = tgt_stage_pos(s, k);
+        if (pos < 0)
+            continue;
+        g.present = 1;
+        tgt_stage_doubles(rows.data() + 2 * nz * pos, s.tgt_h_on.data(), s.tgt_n_kf, &g);
+        if (int rc = tgt_totals_agree(ctx, g, tot + 8 * pos))
+            return rc;
+    }
+    return EBVO_TGT_NUM_STAGES;
+}
+
+extern "C" int ebvo_temporal_gt_flags(ebvo_ctx *ctx, int slot, int stage, uint8_t *is_tp)
+{
+    Slot *sp;
+    if (stage < 0 || stage >= EBVO_TGT_NUM_STAGES)
+        return EBVO_ERR_ARG;
+    if (int rc = tgt_armed_slot(ctx, slot, &sp))
+        return rc;
+    Slot &s = *sp;
+    const int pos = tgt_stage_pos(s, stage);
+    if (pos < 0)
+    {
+        ctx->last_error = "the slot's match did not form this stage";
+        return EBVO_ERR_STATE;
+    }
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nq = (size_t)s.tq_n, nfin = (size_t)(s.tq_final.n > 0 ? s.tq_final.n : 0), n = pos == 2 ? nfin : nq;
+    if (!n || !is_tp)
+        return EBVO_OK;
+    const bool walked = s.tgt_n_kf > 0 && s.n_final > 0 && !s.tq_empty;
+    if (!walked)
+    {
+        memset(is_tp, 0, n);
+        return EBVO_OK;
+    }
+    const uint8_t *flags = (const uint8_t *)s.tgt_flags.p + (size_t)pos * nq;
+    if (stage != EBVO_TGT_NCC)
+    {
+        EBVO_HIP(ctx, hipMemcpyAsync(is_tp, flags, n, hipMemcpyDeviceToHost, s.stream));
+        EBVO_HIP(ctx, hipStreamSynchronize(s.stream));
+        return EBVO_OK;
+    }
+    // the NCC stage's list is the candidates with keep: compacted here, in candidate order
+    std::vector<uint8_t> f(n), keep(n);
+    const uint8_t *q_keep = (const uint8_t *)s.tq_u8.p + ((2 * (size_t)s.n_final + 63) & ~(size_t)63);
+    EBVO_HIP(ctx, hipMemcpyAsync(f.data(), flags, n, hipMemcpyDeviceToHost, s.stream));
+    EBVO_HIP(ctx, hipMemcpyAsync(keep.data(), q_keep, n, hipMemcpyDeviceToHost, s.stream));
+    EBVO_HIP(ctx, hipStreamSynchronize(s.stream));
+    size_t o = 0;
+    for (size_t k = 0; k < n; ++k)
+        if (keep[k])
+            is_tp[o++] = f[k];
+    return EBVO_OK;
+}
+
+extern "C" int ebvo_tgt_veridical(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *kf_right, const double *kf_gamma, int n_kf,
+                                  const ebvo_edge *cf_left, const ebvo_edge *cf_right, int n_cf, int img_w, int img_h, int cell_size,
+                                  const double R[9], const double t[3], const ebvo_stereo_calib *calib, const ebvo_tgt_params *params,
+                                  uint8_t *in_image, double *proj_left, double *proj_right, double *orient_left, double *orient_right,
+                                  int32_t *ver_row_ptr, int32_t *ver_idx, int64_t cap, int64_t *n_veridical)
+{
+    ebvo_tgt_params P;
+    ebvo_tgt_default_params(&P);
+    if (params)
+        P = *params;
+    if (!ctx || n_kf < 0 || n_cf < 0 || img_w < 1 || img_h < 1 || cell_size < 1 || cap < 0 || !tgt_pose_ok(R, t, calib) || !tgt_params_ok(&P) ||
+        (n_kf > 0 && (!kf_left || !kf_right)) || (n_cf > 0 && (!cf_left || !cf_right)))
+        return EBVO_ERR_ARG;
+    const int64_t gw64 = ((int64_t)img_w + cell_size - 1) / cell_size, gh64 = ((int64_t)img_h + cell_size - 1) / cell_size;
+    if (gw64 * gh64 > (1 << 26) || gw64 > 30000 || gh64 > 30000) // the cells of a mate are 16-bit
+        return EBVO_ERR_ARG;
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    int rc;
+    Slot *sp;
+    if ((rc = gt_host_slot(ctx, &sp)))
+        return rc;
+    Slot &s = *sp;
+    if (n_veridical)
+        *n_veridical = 0;
+    const int gw = (int)gw64, gh = (int)gh64;
+    const size_t nz = (size_t)n_kf, ncz = (size_t)n_cf;
+    // pass 1 buffer (the call's own): mates, gamma, the six doubles per keyframe mate, counts and offsets, flags, the grid
+    const size_t o_kfR = sizeof(ebvo_edge) * nz, o_cfL = 2 * sizeof(ebvo_edge) * nz, o_cfR = o_cfL + sizeof(ebvo_edge) * ncz,
+                 o_geom = o_cfR + sizeof(ebvo_edge) * ncz, o_i32 = o_geom + sizeof(double) * 9 * nz,
+                 o_u8 = o_i32 + sizeof(int32_t) * 2 * (nz + 1), o_grid = (o_u8 + 2 * nz + 63) & ~(size_t)63,
+                 o_idx = (o_grid + match_temporal_grid_bytes(n_cf, gw * gh) + 63) & ~(size_t)63;
+    const size_t idx_room = sizeof(int32_t) * (size_t)((cap < (int64_t)nz * ncz ? cap : (int64_t)nz * ncz) + 1);
+    if ((rc = gt_grow(ctx, s, s.tgt_up, o_idx + idx_room)))
+        return rc;
+    hipStream_t st = s.stream;
+    char *base = (char *)s.tgt_up.p;
+    ebvo_edge *kfL = (ebvo_edge *)base, *kfR = (ebvo_edge *)(base + o_kfR), *cfL = (ebvo_edge *)(base + o_cfL), *cfR = (ebvo_edge *)(base + o_cfR);
+    double *pl = (double *)(base + o_geom), *pr = pl + 2 * nz, *ol = pr + 2 * nz, *orr = ol + nz, *gamma = orr + nz;
+    int32_t *cnt = (int32_t *)(base + o_i32), *rp = cnt + nz + 1;
+    uint8_t *in = (uint8_t *)(base + o_u8), *on = in + nz;
+    std::vector<int32_t> h_cnt(nz + 1, 0), h_rp;
+    int32_t n_rows = 0;
+    if (n_kf)
+    {
+        EBVO_HIP(ctx, hipMemcpyAsync(kfL, kf_left, sizeof(ebvo_edge) * nz, hipMemcpyHostToDevice, st));
+        EBVO_HIP(ctx, hipMemcpyAsync(kfR, kf_right, sizeof(ebvo_edge) * nz, hipMemcpyHostToDevice, st));
+        if (kf_gamma)
+            EBVO_HIP(ctx, hipMemcpyAsync(gamma, kf_gamma, sizeof(double) * 3 * nz, hipMemcpyHostToDevice, st));
+        if ((rc = tgt_project_enqueue(ctx, s, kfL, kfR, kf_gamma ? gamma : nullptr, n_kf, R, t, calib, P.img_margin, img_w, img_h, in, pl,
+                                      pr, ol, orr)))
+            return rc;
+    }
+    const bool walk = n_kf > 0 && n_cf > 0;
+    const int sr = tgt_cell_radius(P.search_radius, cell_size);
+    if (walk)
+    {
+        EBVO_HIP(ctx, hipMemcpyAsync(cfL, cf_left, sizeof(ebvo_edge) * ncz, hipMemcpyHostToDevice, st));
+        EBVO_HIP(ctx, hipMemcpyAsync(cfR, cf_right, sizeof(ebvo_edge) * ncz, hipMemcpyHostToDevice, st));
+        if ((rc = match_temporal_cells_enqueue(ctx, s, cfL, cfR, n_cf, cell_size, gw, gh, base + o_grid)) ||
+            (rc = tgt_veridical_enqueue(ctx, s, n_kf, in, pl, pr, ol, orr, cfL, cfR, base + o_grid, n_cf, cell_size, sr, gw, gh, P.tp_dist,
+                                        P.orient_thr_deg, nullptr, cnt, nullptr, nullptr, 0, nullptr)))
+            return rc;
+        EBVO_HIP(ctx, hipMemcpyAsync(h_cnt.data(), cnt, sizeof(int32_t) * nz, hipMemcpyDeviceToHost, st));
+    }
+    EBVO_HIP(ctx, hipStreamSynchronize(st));
+    if (!tgt_row_offsets(h_cnt, n_kf, h_rp, &n_rows))
+        return EBVO_ERR_CAPACITY;
+    const int64_t n_ver = h_rp[n_kf];
+    if (n_veridical)
+        *n_veridical = n_ver;
+    if (ver_idx && n_ver > cap)
+        return EBVO_ERR_CAPACITY;
+    if (walk && ver_idx && n_ver > 0)
+    {
+        EBVO_HIP(ctx, hipMemcpyAsync(rp, h_rp.data(), sizeof(int32_t) * (nz + 1), hipMemcpyHostToDevice, st));
+        if ((rc = tgt_veridical_enqueue(ctx, s, n_kf, in, pl, pr, ol, orr, cfL, cfR, base + o_grid, n_cf, cell_size, sr, gw, gh, P.tp_dist,
+                                        P.orient_thr_deg, nullptr, nullptr, rp, (int32_t *)(base + o_idx), n_ver, on)))
+            return rc;
+        EBVO_HIP(ctx, hipMemcpyAsync(ver_idx, base + o_idx, sizeof(int32_t) * (size_t)n_ver, hipMemcpyDeviceToHost, st));
+    }
+    if (nz)
+    {
+        const struct
+        {
+            void *dst;
+            const void *src;
+            size_t bytes;
+        } copies[] = {{in_image, in, nz}, {proj_left, pl, sizeof(double) * 2 * nz}, {proj_right, pr, sizeof(double) * 2 * nz},
+                      {orient_left, ol, sizeof(double) * nz}, {orient_right, orr, sizeof(double) * nz}};
+        for (const auto &c : copies)
+            if (c.dst)
+                EBVO_HIP(ctx, hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, st));
+    }
+    EBVO_HIP(ctx, hipStreamSynchronize(st));
+    if (ver_row_ptr)
+        memcpy(ver_row_ptr, h_rp.data(), sizeof(int32_t) * (nz + 1));
+    return EBVO_OK;
+}
+
+extern "C" int ebvo_tgt_evaluate_rows(ebvo_ctx *ctx, const int32_t *row_ptr, const ebvo_edge *left_centres, const ebvo_edge *right_centres,
+                                      int n_kf, const uint8_t *row_on, const double *proj_left, const double *proj_right, double tp_dist,
+                                      int32_t *n_tp, uint8_t *is_tp, ebvo_gt_stage *stage_out)
+{
+    int64_t np = 0;
+    if (!ctx || !stage_out || !(tp_dist >= 0) || check_csr(row_ptr, n_kf, &np) || (n_kf > 0 && (!proj_left || !proj_right)) ||
+        (np > 0 && (!left_centres || !right_centres)))
+        return EBVO_ERR_ARG;
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    int rc;
+    Slot *sp;
+    if ((rc = gt_host_slot(ctx, &sp)))
+        return rc;
+    Slot &s = *sp;
+    memset(stage_out, 0, sizeof *stage_out);
+    stage_out->present = 1;
+    const size_t nz = (size_t)n_kf, npz = (size_t)np;
+    // one buffer of the call's own: both centre lists, both projections, the totals, the (n, tp) rows, row_ptr, row_on, is_tp
+    const size_t o_R = sizeof(ebvo_edge) * (npz + 1), o_pl = 2 * o_R, o_pr = o_pl + sizeof(double) * 2 * (nz + 1),
+                 o_tot = o_pr + sizeof(double) * 2 * (nz + 1), o_rows = o_tot + sizeof(unsigned long long) * 8,
+                 o_rp = o_rows + sizeof(int32_t) * 2 * (nz + 1), o_on = o_rp + sizeof(int32_t) * (nz + 2), o_tp = o_on + nz + 8,
+                 total = o_tp + npz + 8;
+    if ((rc = gt_grow(ctx, s, s.tgt_up, total)))
+        return rc;
+    hipStream_t st = s.stream;
+    char *base = (char *)s.tgt_up.p;
+    int32_t *d_rows = (int32_t *)(base + o_rows);
+    unsigned long long *d_tot = (unsigned long long *)(base + o_tot);
+    if (np)
+    {
+        EBVO_HIP(ctx, hipMemcpyAsync(base, left_centres, sizeof(ebvo_edge) * npz, hipMemcpyHostToDevice, st));
+        EBVO_HIP(ctx, hipMemcpyAsync(base + o_R, right_centres, sizeof(ebvo_edge) * npz, hipMemcpyHostToDevice, st));
+    }
+    EBVO_HIP(ctx, hipMemcpyAsync(base + o_rp, row_ptr, sizeof(int32_t) * (nz + 1), hipMemcpyHostToDevice, st));
+    if (n_kf)
+    {
+        EBVO_HIP(ctx, hipMemcpyAsync(base + o_pl, proj_left, sizeof(double) * 2 * nz, hipMemcpyHostToDevice, st));
+        EBVO_HIP(ctx, hipMemcpyAsync(base + o_pr, proj_right, sizeof(double) * 2 * nz, hipMemcpyHostToDevice, st));
+        if (row_on)
+            EBVO_HIP(ctx, hipMemcpyAsync(base + o_on, row_on, nz, hipMemcpyHostToDevice, st));
+        else
+            EBVO_HIP(ctx, hipMemsetAsync(base + o_on, 1, nz, st));
+        EBVO_HIP(ctx, hipMemsetAsync(d_rows, 0, sizeof(int32_t) * 2 * nz, st));
+    }
+    if ((rc = tgt_rows_enqueue(ctx, s, (const int32_t *)(base + o_rp), (const ebvo_edge *)base, (const ebvo_edge *)(base + o_R), nullptr,
+                               nullptr, nullptr, nullptr, (const double *)(base + o_pl), (const double *)(base + o_pr),
+                               (const uint8_t *)(base + o_on), n_kf, np, tp_dist, d_rows, (uint8_t *)(base + o_tp), d_tot)))
+        return rc;
+    std::vector<int32_t> rows(2 * nz + 1);
+    unsigned long long tot[5] = {0, 0, 0, 0, 0};
+    if (n_kf)
+        EBVO_HIP(ctx, hipMemcpyAsync(rows.data(), d_rows, sizeof(int32_t) * 2 * nz, hipMemcpyDeviceToHost, st));
+    if (is_tp && np)
+        EBVO_HIP(ctx, hipMemcpyAsync(is_tp, base + o_tp, npz, hipMemcpyDeviceToHost, st));
+    EBVO_HIP(ctx, hipMemcpyAsync(tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, st));
+    EBVO_HIP(ctx, hipStreamSynchronize(st));
+    tgt_stage_doubles(rows.data(), row_on, n_kf, stage_out);
+    if ((rc = tgt_totals_agree(ctx, *stage_out, tot)))
+        return rc;
+    if (n_tp && n_kf)
+        memcpy(n_tp, rows.data(), sizeof(int32_t) * 2 * nz);
     return EBVO_OK;
 }
 

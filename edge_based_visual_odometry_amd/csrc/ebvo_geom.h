@@ -1,6 +1,7 @@
 /*
  * ebvo_geom.h -- the stereo geometry of one (left edge, right edge) pair, shared by the finalisation rows
- * (refine_kernels.hip: finalize_pairs_kernel) and the pose search (pose_kernels.hip): Gamma from
+ * (refine_kernels.hip: finalize_pairs_kernel), the pose search (pose_kernels.hip) and the temporal ground truth
+ * (tgt_kernels.hip): Gamma from
  * Utility::backproject_2D_point_to_3D_point_using_rays and T from reconstruct_3D_Tangent_through_intersection_of_planes
  * (src/utility.cpp:95-112).  The calibration inverses are formed once on the host (Eigen's cofactor inverse, restated),
  * every product / cross / normalize in Eigen's fixed-size order.  Compiled with -ffp-contract=off (no FMA).
@@ -50,6 +51,15 @@ __device__ static inline void normalize3(double *v)
         v[1] /= n;
         v[2] /= n;
     }
+}
+
+// Utility::project_3D_Tangent_to_2D_Tangent (src/utility.cpp:114-119): T - T.z * gamma, normalised
+__device__ static inline void project_tangent3(const double *T, const double *g, double *p)
+{
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        p[i] = T[i] - T[2] * g[i];
+    normalize3(p);
 }
 
 // Gamma (3-D point, left camera) and T (unit 3-D tangent) of one pair; g1 / g2: the two rays K^-1 (x, y, 1)

@@ -36,6 +36,9 @@ enum KernelId
     K_GT_POOL,   // gt_pool<count> and <fill>
     K_GT_CENSUS,
     K_GT_ROWS,
+    K_TGT_PROJECT,   // tgt_project
+    K_TGT_VERIDICAL, // tgt_veridical<count> and <fill>
+    K_TGT_ROWS,      // tgt_rows
     K_NUM
 };
 static_assert(K_NUM <= EBVO_MAX_KERNELS, "grow EBVO_MAX_KERNELS");
@@ -179,6 +182,14 @@ struct Slot
     ebvo_gt_params gt_params{};
     std::vector<uint8_t> gt_h_focused;  // host copy of focused[]
     std::vector<int32_t> gt_h_pool_rp;  // host copy of the pool's row_ptr
+    // temporal ground truth (tgt_kernels.hip, ebvo_temporal_set_gt): armed = the buffers below describe the slot's temporal match
+    GrowBuf tgt_geom, tgt_i32, tgt_idx, tgt_u8, tgt_rows, tgt_flags, tgt_tot;
+    GrowBuf tgt_up; // everything ebvo_tgt_veridical / ebvo_tgt_evaluate_rows need (host-array calls: they touch nothing else of slot 0)
+    bool tgt_armed = false;
+    int tgt_n_kf = 0;
+    int32_t tgt_n_rows = 0;      // keyframe mates with a veridical quad
+    int64_t tgt_n_ver = 0;       // veridical quads
+    std::vector<uint8_t> tgt_h_on; // host copy of row_on[]: a veridical quad and kf_is_tp
     bool sift_left_valid = false;                      // sift_desc holds the descriptors of every left TOED edge of this pair
     struct TqFinal                                     // the quads that leave the chain (pointers into tq_chain)
     {
@@ -406,6 +417,23 @@ struct ProfScope
     }
 };
 
+// temporal candidate grid (match_kernels.hip builds it; tgt_kernels.hip queries it too): the cells of a current-frame mate
+struct MateCells
+{
+    short lx, ly, rx, ry; // -30000: the edge is outside the grid and is never returned by a query
+};
+#ifdef __HIPCC__
+// both orientation tests of the temporal path (src/Temporal_Matches.cpp:124-134, :398-405): |a - b| in degrees, folded at
+// 180, within thr of 0 or of 180
+__device__ inline bool orient_close(double a, double b, double thr)
+{
+    double od = fabs((a - b) * 0x1.ca5dc1a63c1f8p+5 /* rad_to_deg: theta * (180.0 / M_PI) */);
+    if (od > 180.0)
+        od = 360.0 - od;
+    return od < thr || fabs(od - 180.0) < thr;
+}
+#endif
+
 // ---- device-level stages (device pointers; asynchronous on the slot's stream; NO host synchronisation) ----
 // A size argument is a host value plus an optional device pointer; when the pointer is non-null the kernels read
 // the size from device memory and `*_cap` bounds the launch.
@@ -461,6 +489,9 @@ int match_temporal_candidates_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d
                                       const ebvo_edge *d_cfL, const ebvo_edge *d_cfR, const void *d_grid, int n_cf, int cell,
                                       int sr, int gw, int gh, double orient_thr, int32_t *d_cnt, const int32_t *d_row_ptr,
                                       int32_t *d_col_idx, int64_t cap);
+// where the three arrays a query reads lie inside a grid buffer of match_temporal_cells_enqueue
+void match_temporal_grid_view(const void *d_grid, int n_cf, int n_cells, const MateCells **cells, const int32_t **cell_start,
+                              const int32_t **cell_list);
 int match_count_flags_enqueue(ebvo_ctx *ctx, Slot &s, const uint8_t *d_flags, int64_t n, unsigned long long *d_out,
                               const int32_t *d_n = nullptr);
 int match_ncc_quads_indexed_enqueue(ebvo_ctx *ctx, Slot &s, const float *kfLn, const uint8_t *kfLf, const float *kfRn,
@@ -583,6 +614,22 @@ int gt_rows_enqueue(ebvo_ctx *ctx, Slot &s, const int32_t *d_row_ptr, const ebvo
                     const ebvo_edge *d_R, const uint8_t *d_flags, const double *d_gt_xy, const uint8_t *d_focused, int nL,
                     double tp_dist, int32_t *d_rows, unsigned long long *d_tot);
 int gt_totals_enqueue(ebvo_ctx *ctx, Slot &s, const int32_t *d_rows, const uint8_t *d_focused, int nL, unsigned long long *d_tot);
+// tgt_kernels.hip
+// per keyframe mate: in_image, both projections [n][2], both projected orientations; d_gamma == nullptr: the triangulated one
+int tgt_project_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, const double *d_gamma, int n_kf,
+                        const double *R, const double *t, const ebvo_stereo_calib *calib, double margin, int img_w, int img_h, uint8_t *d_in, double *d_pl, double *d_pr, double *d_ol,
+                        double *d_or);
+// veridical quads: d_row_ptr == nullptr counts into d_cnt, else fills d_idx (cap entries) at d_row_ptr and d_on = (count > 0 && is_tp)
+int tgt_veridical_enqueue(ebvo_ctx *ctx, Slot &s, int n_kf, const uint8_t *d_in, const double *d_pl, const double *d_pr,
+                          const double *d_ol, const double *d_or, const ebvo_edge *d_cfL, const ebvo_edge *d_cfR, const void *d_grid,
+                          int n_cf, int cell, int sr, int gw, int gh, double dist_thr, double orient_thr, const uint8_t *d_is_tp,
+                          int32_t *d_cnt, const int32_t *d_row_ptr, int32_t *d_idx, int64_t cap, uint8_t *d_on);
+// (n, tp) per row of a CSR list of quads (centres d_cenL[k] / d_cenR[k], or d_cfL / d_cfR [d_col_idx[k]]; d_keep optional),
+// the per-quad b_is_TP byte (0 for a quad outside the list or on a row that is off) and the five integer totals
+int tgt_rows_enqueue(ebvo_ctx *ctx, Slot &s, const int32_t *d_row_ptr, const ebvo_edge *d_cenL, const ebvo_edge *d_cenR,
+                     const int32_t *d_col_idx, const ebvo_edge *d_cfL, const ebvo_edge *d_cfR, const uint8_t *d_keep,
+                     const double *d_pl, const double *d_pr, const uint8_t *d_on, int n_kf, int64_t n_quads, double tp_dist,
+                     int32_t *d_rows, uint8_t *d_is_tp, unsigned long long *d_tot);
 int pose_run(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, const int32_t *d_rp, int n_kf,
              const ebvo_edge *d_cfL, const ebvo_edge *d_cfR, int n, const ebvo_stereo_calib *cal, const ebvo_pose_params *p,
              ebvo_pose_result *res, uint8_t *inlier, double *quad_geom, int32_t *rank_order);

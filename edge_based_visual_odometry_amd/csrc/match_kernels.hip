@@ -1386,11 +1386,6 @@ __global__ __launch_bounds__(256, WPE) void ncc_tile_kernel(const uint8_t *__res
 // `left_candidates` (src/Temporal_Matches.cpp:352, :357), the right-grid membership is the cell test on the mate's right
 // edge.  ~25 cells x ~40 mates per query instead of every mate of the five cell rows (the mates are in raster order:
 // index ranges are narrow in y but span the image in x).
-struct MateCells
-{
-    short lx, ly, rx, ry; // -30000: the edge is outside the grid and is never returned by a query
-};
-
 __device__ inline short cell_of(double v, int cell, int n_cells)
 {
     const int c = (int)v / cell; // static_cast<int>(location.x) / cell_size
@@ -1483,14 +1478,6 @@ __global__ __launch_bounds__(256) void cell_sort_kernel(const int32_t *__restric
             sorted[a + rank] = v; // the indices of a cell are distinct
         }
     }
-}
-
-__device__ inline bool orient_close(double a, double b, double thr)
-{
-    double od = fabs((a - b) * 0x1.ca5dc1a63c1f8p+5 /* rad_to_deg: theta * (180.0 / M_PI) */);
-    if (od > 180.0)
-        od = 360.0 - od;
-    return od < thr || fabs(od - 180.0) < thr;
 }
 
 // sixteen lanes per keyframe mate: lane e tests every sixteenth mate of a cell's segment, the survivors of a step are
@@ -2160,6 +2147,15 @@ static TemporalGrid temporal_grid(void *base, int n_cf, int n_cells)
 size_t match_temporal_grid_bytes(int n_cf, int n_cells)
 {
     return ((sizeof(MateCells) * (size_t)n_cf + 63) & ~(size_t)63) + sizeof(int32_t) * (3 * (size_t)n_cells + 1 + 2 * (size_t)n_cf) + 64;
+}
+
+void match_temporal_grid_view(const void *d_grid, int n_cf, int n_cells, const MateCells **cells, const int32_t **cell_start,
+                              const int32_t **cell_list)
+{
+    const TemporalGrid g = temporal_grid(const_cast<void *>(d_grid), n_cf, n_cells);
+    *cells = g.cells;
+    *cell_start = g.start;
+    *cell_list = g.sorted;
 }
 
 int match_temporal_cells_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_cfL, const ebvo_edge *d_cfR, int n_cf, int cell, int gw,

@@ -1243,14 +1243,8 @@ __global__ void finalize_pairs_kernel(FinalCalib C, const ebvo_edge *__restrict_
         const ebvo_edge l = L[k], r = R[k];
         double G[3], T[3], g1[3], g2[3], p1[3], p2[3];
         stereo_gamma_tangent(C, l, r, G, T, g1, g2);
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-        {
-            p1[i] = T[i] - T[2] * g1[i];
-            p2[i] = T[i] - T[2] * g2[i];
-        }
-        normalize3(p1);
-        normalize3(p2);
+        project_tangent3(T, g1, p1);
+        project_tangent3(T, g2, p2);
         double *o = out + (size_t)k * 16;
         o[0] = l.x; o[1] = l.y; o[2] = l.theta;
         o[3] = r.x; o[4] = r.y; o[5] = r.theta;

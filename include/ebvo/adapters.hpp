@@ -926,6 +926,64 @@ inline FrameEvaluationMetrics evaluate(const Context &c, int slot)
     return out;
 }
 
+// A camera pose as the reference's Camera_Pose holds it (row-major R, t: X_camera = R X_world + t)
+struct CameraPose
+{
+    double R[9], t[3];
+};
+
+// Utility::get_Relative_Pose (src/utility.cpp:121-128): rel_R = target.R * source.R^T, rel_T = -rel_R * source.t + target.t
+inline CameraPose relative_pose(const CameraPose &source, const CameraPose &target)
+{
+    CameraPose rel;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j)
+            rel.R[i * 3 + j] = (target.R[i * 3] * source.R[j * 3] + target.R[i * 3 + 1] * source.R[j * 3 + 1]) + target.R[i * 3 + 2] * source.R[j * 3 + 2];
+    for (int i = 0; i < 3; ++i)
+        rel.t[i] = (((-rel.R[i * 3]) * source.t[0] + (-rel.R[i * 3 + 1]) * source.t[1]) + (-rel.R[i * 3 + 2]) * source.t[2]) + target.t[i];
+    return rel;
+}
+
+// build_Veridical_Quads + Evaluate_Temporal_Edge_Pairs_on_Quads (src/Temporal_Matches.cpp:57-166, :220-292) on the temporal
+// match of `slot`: arms it with the relative pose of the two GT camera poses (keyframe, current frame) and returns the
+// stages the match formed ("Orientation", "NCC", and "Edge Clustering" after stages = 1) under the reference's names.
+// kf_gamma (n_kf x 3) / kf_is_tp (n_kf): the keyframe mates' GT 3-D points and b_is_TP, or nullptr (ebvo_hip.h).
+inline FrameEvaluationMetrics evaluate(const Context &c, int slot, const CameraPose &keyframe_gt_pose, const CameraPose &current_gt_pose,
+                                       const ebvo_stereo_calib &calib, const ebvo_tgt_params *params = nullptr,
+                                       const double *kf_gamma = nullptr, const uint8_t *kf_is_tp = nullptr)
+{
+    static const char *const names[EBVO_TGT_NUM_STAGES] = {"Location Proximity", "Orientation", "NCC", "SIFT", "BNB-NCC", "BNB-SIFT",
+                                                           "Photometric Refinement", "Edge Clustering"};
+    FrameEvaluationMetrics out;
+    const CameraPose rel = relative_pose(keyframe_gt_pose, current_gt_pose);
+    out.status = ebvo_temporal_set_gt(c.get(), slot, rel.R, rel.t, &calib, params, kf_gamma, kf_is_tp);
+    if (out.status != EBVO_OK)
+    {
+        report(c, out.status, "ebvo_temporal_set_gt");
+        return out;
+    }
+    ebvo_gt_stage st[EBVO_TGT_NUM_STAGES];
+    const int n = ebvo_temporal_gt_metrics(c.get(), slot, st);
+    if (n < 0)
+    {
+        out.status = n;
+        report(c, n, "ebvo_temporal_gt_metrics");
+        return out;
+    }
+    for (int k = 0; k < n; ++k)
+        if (st[k].present)
+        {
+            StageMetrics m;
+            m.recall = st[k].recall;
+            m.precision = st[k].precision;
+            m.precision_pair = st[k].precision_pair;
+            m.ambiguity = st[k].ambiguity;
+            out.stages.emplace_back(names[st[k].stage], m);
+            out.totals.push_back(st[k]);
+        }
+    return out;
+}
+
 // cv::undistort(src, dst, K, dist) of src/Pipeline.cpp:78-79 on a CV_8UC1 image (K = fx fy cx cy, dist = k1 k2 p1 p2 [k3])
 inline std::vector<uint8_t> undistort(const Context &c, const uint8_t *img, int rows, int cols, ptrdiff_t step, const double K[4],
                                       const std::vector<double> &dist)

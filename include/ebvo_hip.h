@@ -576,7 +576,7 @@ int ebvo_temporal_fetch(ebvo_ctx *ctx, int slot, int32_t *row_ptr, int32_t *col_
  *     cluster centres (get_Gammas_and_Tangents_From_Quads :28-66): columns 6-11 of ebvo_finalize_pairs with K_right := K_left
  *     (the reference uses get_left_calib_matrix() for both cameras here; K_right of `cal` is not read);
  *   - rank order (:90-103): ascending row length of the KF mate, then KF index, then candidate index; every quad is kept
- *     (there is no ground truth on the device: the has_gt() filter and b_is_veridical do not apply);
+ *     (the has_gt() filter on b_is_veridical is not applied here; ebvo_temporal_gt_flags returns that flag per final quad);
  *     top_n = (size_t)(top_rank_fraction * n_quads);
  *   - the loop: termination test at its top (iterations > min_iterations && iterations > dynamic_max_iter), two indices
  *     rand() % top_n redrawn together while equal, the length / T1 / T2 / tangent constraints (:108-134; a rejected draw
@@ -592,7 +592,7 @@ int ebvo_temporal_fetch(ebvo_ctx *ctx, int slot, int32_t *row_ptr, int32_t *col_
  * Deliberate divergences, where the reference has undefined behaviour or never returns:
  *   - fewer than 2 quads or top_n < 2 (rand() % 0, or an endless redraw of idx1 == idx2): status 1, identity pose, nothing
  *     launched and no random number drawn (quads_by_kf.size() < 2 of the reference counts GT-veridical KF mates only, which
- *     the device cannot form; this rule replaces it);
+ *     the pose search does not read; this rule replaces it);
  *   - at most max_draws index pairs (idx1 != idx2) are drawn: when the loop still needs one more, status 2 (the reference
  *     loops forever when no pair passes the constraints);
  *   - the ceil(...) of the third branch is clamped to [0, 2^62] before its conversion to an integer.
@@ -714,6 +714,92 @@ int ebvo_gt_locate(ebvo_ctx *ctx, const ebvo_edge *edges, int n, const float *di
                    double *gamma_left, double *gamma_right);
 int ebvo_gt_evaluate_rows(ebvo_ctx *ctx, const int32_t *row_ptr, const ebvo_edge *cand_edges, int nL, const uint8_t *focused,
                           const double *gt_xy, double tp_dist, int32_t *n_tp, ebvo_gt_stage *stage_out);
+
+/* ---- temporal ground truth from a relative pose (the has_gt() == true branch of the temporal chain) ---------------- */
+/* Temporal_Matches::build_Veridical_Quads (src/Temporal_Matches.cpp:57-166) with orientation_mapping (:294-333) and
+ * Evaluate_Temporal_Edge_Pairs_on_Quads (:220-292), on what a slot holds after ebvo_temporal_match.  Nothing of the chain
+ * is run again and nothing the slot holds is written.
+ *   - Per keyframe mate: Gamma_CF = R Gamma_KF + t, its projections into the left and the right camera of the current frame,
+ *     the keyframe mate's 3-D tangent carried along and projected (both orientations), and the margin test (:100-105; BOTH
+ *     cameras against the LEFT width and height, as written).  (R_stereo * rel_pose.R) * T_1 of :321 is formed as it binds:
+ *     the 3x3 product first.
+ *   - Veridical quads of a keyframe mate inside the image: the current-frame mates in the whole grid cells of
+ *     getCandidatesWithinRadius(projection, search_radius) of BOTH grids (include/Dataset.h:92-113), in the order of
+ *     `left_candidates`, with both distances < tp_dist and both orientation differences (mod 180 degrees) < orient_thr_deg,
+ *     all strict (:122-137).  The grid is the current-frame grid of the slot's match (its cell_size).
+ *   - Rows of the evaluation: keyframe mates with at least one veridical quad whose b_is_TP holds (:233).  The reference
+ *     runs the temporal chain over the mates with a veridical quad only; every temporal stage acts row by row, so the
+ *     chain on all rows restricted to those rows is the same lists.
+ *   - A quad is a true positive when both its centres lie < tp_dist from the projections (strict, :248).  Per row
+ *     recall = (tp >= 1), precision = tp / n (0 for an empty row), ambiguity = n; recall is averaged over the rows,
+ *     precision and ambiguity over the non-empty rows, ambiguity minus 1 (:280-282); precision_pair = precision.
+ *     No rows, or no non-empty row: the four zeros of :274-278, not NaN.
+ *   - The four doubles are summed on the host from the per-row integers in KEYFRAME INDEX ORDER.  The reference's order is
+ *     that of its `out` vector, which depends on OpenMP scheduling (:71-165); index order is its one-thread order.
+ * Two deliberate departures, for datasets that have poses but no disparity map: kf_gamma = NULL uses the triangulated
+ * Gamma of the keyframe mates (columns 6-8 of ebvo_finalize_pairs) where the reference uses the GT 3-D point of the
+ * disparity map (src/Stereo_Matches.cpp:186, :1638: gamma_left of ebvo_stereo_gt_fetch at the mate's left index), and
+ * kf_is_tp = NULL takes every keyframe mate as a true positive (:1645).
+ * Accepted ranges: every value >= 0 and not NaN (+inf allowed); anything else EBVO_ERR_ARG, nothing touched. */
+typedef struct ebvo_tgt_params
+{
+    double orient_thr_deg; /* 10.0 (:67) */
+    double tp_dist;        /* DIST_TO_GT_THRESH_QUADS 2.0 (include/definitions.h): veridical test and true-positive test */
+    double search_radius;  /* 20.0 = 15 + DIST_TO_GT_THRESH_QUADS + 3 (:68) */
+    double img_margin;     /* 10 (:69) */
+} ebvo_tgt_params;
+void ebvo_tgt_default_params(ebvo_tgt_params *p);
+
+/* the stages in the reference's order with the names it gives them (:186-215) */
+enum
+{
+    EBVO_TGT_GRID = 0,    /* "Location Proximity" */
+    EBVO_TGT_ORIENTATION, /* "Orientation": the resident candidate lists */
+    EBVO_TGT_NCC,         /* "NCC": the candidates with keep */
+    EBVO_TGT_SIFT,        /* "SIFT" */
+    EBVO_TGT_BNB_NCC,     /* "BNB-NCC" */
+    EBVO_TGT_BNB_SIFT,    /* "BNB-SIFT" */
+    EBVO_TGT_REFINE,      /* "Photometric Refinement" */
+    EBVO_TGT_CLUSTER,     /* "Edge Clustering": the final quads of stages = 1, centres as ebvo_temporal_fetch_final returns them */
+    EBVO_TGT_NUM_STAGES
+};
+
+/* Arms `slot`, whose temporal match has completed.  R (row-major), t: the relative pose keyframe -> current frame as
+ * Utility::get_Relative_Pose returns it (R = R_cf R_kf^T, t = -R t_kf + t_cf).  kf_gamma: n_kf x 3 doubles or NULL,
+ * kf_is_tp: n_kf bytes or NULL (see above).  EBVO_ERR_STATE if the slot has no match, anything of it is in flight, or the
+ * keyframe was replaced since the match.  A new match, upload or run of the slot disarms it.  Every argument is checked
+ * before any state changes: a refused call leaves the slot, armed or not, as it was. */
+int ebvo_temporal_set_gt(ebvo_ctx *ctx, int slot, const double R[9], const double t[3], const ebvo_stereo_calib *calib,
+                         const ebvo_tgt_params *params, const double *kf_gamma, const uint8_t *kf_is_tp);
+/* keyframe mates, those with a veridical quad, veridical quads */
+int ebvo_temporal_gt_size(ebvo_ctx *ctx, int slot, int32_t *n_kf, int32_t *n_rows, int64_t *n_veridical);
+/* per keyframe mate: in_image [n_kf] (both projections inside the margin), proj_left / proj_right [n_kf][2],
+ * orient_left / orient_right [n_kf] (computed for every mate, as the reference does before its margin test), and the
+ * veridical quads as a CSR over the keyframe mates: ver_row_ptr [n_kf + 1], ver_idx [n_veridical] (current-frame mate
+ * indices).  Any pointer may be NULL. */
+int ebvo_temporal_gt_fetch(ebvo_ctx *ctx, int slot, uint8_t *in_image, double *proj_left, double *proj_right,
+                           double *orient_left, double *orient_right, int32_t *ver_row_ptr, int32_t *ver_idx);
+/* stages[EBVO_TGT_NUM_STAGES], indexed by stage id: ORIENTATION, NCC and (after stages = 1) CLUSTER are filled, every other
+ * stage has present = 0.  Returns the stage count (> 0) or a negative status. */
+int ebvo_temporal_gt_metrics(ebvo_ctx *ctx, int slot, ebvo_gt_stage *stages);
+/* per-quad b_is_TP of a present stage in that stage's CSR order (ORIENTATION: ebvo_temporal_fetch's candidates; NCC: those
+ * with keep; CLUSTER: ebvo_temporal_fetch_final's quads); 0 on rows outside the evaluation.  What
+ * Quad_for_Pose_Solution::b_is_veridical reads.  A stage that is not present: EBVO_ERR_STATE. */
+int ebvo_temporal_gt_flags(ebvo_ctx *ctx, int slot, int stage, uint8_t *is_tp);
+/* The kernels behind it on host arrays, on slot 0's stream (EBVO_ERR_STATE while work of slot 0 is in flight) with buffers
+ * of their own: slot 0's results and armed state are not touched.  ebvo_tgt_veridical: keyframe mates (kf_gamma may be
+ * NULL) and current-frame mates in, the arrays of ebvo_temporal_gt_fetch out (any may be NULL); the grid of the
+ * current-frame mates (img_w x img_h, cell_size >= 1) is built in the call's buffer.  ver_idx holds cap entries; more
+ * veridical quads than that: EBVO_ERR_CAPACITY with *n_veridical set.  ebvo_tgt_evaluate_rows: a CSR list of quad centres
+ * per keyframe mate, row_on [n_kf] (NULL: all), the projections; n_tp [n_kf][2], is_tp per quad (both may be NULL). */
+int ebvo_tgt_veridical(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *kf_right, const double *kf_gamma, int n_kf,
+                       const ebvo_edge *cf_left, const ebvo_edge *cf_right, int n_cf, int img_w, int img_h, int cell_size,
+                       const double R[9], const double t[3], const ebvo_stereo_calib *calib, const ebvo_tgt_params *params,
+                       uint8_t *in_image, double *proj_left, double *proj_right, double *orient_left, double *orient_right,
+                       int32_t *ver_row_ptr, int32_t *ver_idx, int64_t cap, int64_t *n_veridical);
+int ebvo_tgt_evaluate_rows(ebvo_ctx *ctx, const int32_t *row_ptr, const ebvo_edge *left_centres, const ebvo_edge *right_centres,
+                           int n_kf, const uint8_t *row_on, const double *proj_left, const double *proj_right, double tp_dist,
+                           int32_t *n_tp, uint8_t *is_tp, ebvo_gt_stage *stage_out);
 
 /* ---------------------------------------------------------------------------------------- */
 /* Device-resident stereo pipeline: TOED(left) + TOED(right) + candidates + NCC of one pair,  */
@@ -858,7 +944,7 @@ int ebvo_stereo_fetch_compact_begin(ebvo_ctx *ctx, int slot, int what);
 int ebvo_stereo_fetch_compact_end(ebvo_ctx *ctx, int slot, ebvo_stereo_compact_view *view);
 
 /* Per-kernel device timing (HIP events on the slots' streams, accumulated). */
-#define EBVO_MAX_KERNELS 24 /* >= the number of kernel ids (ebvo_internal.h) */
+#define EBVO_MAX_KERNELS 32 /* >= the number of kernel ids (ebvo_internal.h) */
 typedef struct ebvo_kernel_time
 {
     const char *name;
