@@ -52,6 +52,8 @@ ABI_SYMBOLS = (
     "ebvo_stereo_gt_stage_rows", "ebvo_gt_locate", "ebvo_gt_evaluate_rows",
     "ebvo_tgt_default_params", "ebvo_temporal_set_gt", "ebvo_temporal_gt_size", "ebvo_temporal_gt_fetch", "ebvo_temporal_gt_metrics",
     "ebvo_temporal_gt_flags", "ebvo_tgt_veridical", "ebvo_tgt_evaluate_rows",
+    "ebvo_pose_from_quads_gt", "ebvo_temporal_estimate_pose_gt", "ebvo_pose_constraint_metrics",
+    "ebvo_temporal_pose_constraint_metrics",
 )
 
 
@@ -121,6 +123,23 @@ class PoseResult(C.Structure):
 
 
 POSE_OK, POSE_INSUFFICIENT, POSE_DRAW_CAP = 0, 1, 2
+
+# stage ids (ebvo_hip.h EBVO_PC_*) and the names of Solution_Constraints_Application (src/MotionTracker.cpp:299-378)
+PC_STAGE_NAMES = ("Baseline", "Normalized Length Constraint", "T1 Angle Similarity Constraint", "T2 Angle Similarity Constraint",
+                  "Tangent Angle Similarity Constraint")
+(PC_BASELINE, PC_LENGTH, PC_T1, PC_T2, PC_TANGENT) = range(5)
+PC_NUM_STAGES = 5
+PC_MAX_DRAWS = 1 << 24   # n_runs x max_iterations of one call
+
+
+class PoseCascadeStage(C.Structure):
+    _fields_ = [("stage", C.c_int32), ("reserved", C.c_int32), ("surviving", C.c_int64), ("veridical", C.c_int64),
+                ("recall", C.c_double), ("precision", C.c_double)]
+
+
+class PoseCascadeRun(C.Structure):
+    _fields_ = [("status", C.c_int32), ("reserved", C.c_int32), ("n_quads", C.c_int64), ("top_n", C.c_int64),
+                ("draws", C.c_int64), ("stages", PoseCascadeStage * PC_NUM_STAGES)]
 
 
 class GtParams(C.Structure):
@@ -299,6 +318,17 @@ def load_library() -> C.CDLL:
     lib.ebvo_pose_from_quads.restype = i32
     lib.ebvo_pose_from_quads.argtypes = [vp, vp, vp, i32, vp, vp, vp, C.POINTER(StereoCalib), C.POINTER(PoseParams),
                                          C.POINTER(PoseResult), vp, vp, vp]
+    lib.ebvo_pose_from_quads_gt.restype = i32
+    lib.ebvo_pose_from_quads_gt.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, C.POINTER(StereoCalib), C.POINTER(PoseParams),
+                                            C.POINTER(PoseResult), vp, vp, vp]
+    lib.ebvo_temporal_estimate_pose_gt.restype = i32
+    lib.ebvo_temporal_estimate_pose_gt.argtypes = [vp, i32, C.POINTER(StereoCalib), C.POINTER(PoseParams), C.POINTER(PoseResult), vp]
+    lib.ebvo_pose_constraint_metrics.restype = i32
+    lib.ebvo_pose_constraint_metrics.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, C.POINTER(StereoCalib),
+                                                 C.POINTER(PoseParams), i32, C.POINTER(PoseCascadeRun), vp, vp]
+    lib.ebvo_temporal_pose_constraint_metrics.restype = i32
+    lib.ebvo_temporal_pose_constraint_metrics.argtypes = [vp, i32, C.POINTER(StereoCalib), C.POINTER(PoseParams), i32,
+                                                          C.POINTER(PoseCascadeRun), vp, vp]
     lib.ebvo_gt_default_params.restype = None
     lib.ebvo_gt_default_params.argtypes = [C.POINTER(GtParams)]
     lib.ebvo_stereo_set_gt.argtypes = [vp, i32, vp, i32, i32, ssz, C.POINTER(StereoCalib), C.POINTER(GtParams)]

@@ -36,6 +36,36 @@ class ToedResult:
     time_nms: float
 
 
+class _CascadeRun(list):
+    """one run of the constraint cascade: the list of its stage dicts, with the run's own fields as attributes"""
+
+    def __init__(self, stages, **fields):
+        super().__init__(stages)
+        self.__dict__.update(fields)
+
+
+def cascade_mean(runs) -> list:
+    """Per-stage mean over the runs of pose_constraint_metrics as Print_Quad_Pairs_Metrics_Statistics forms it
+    (src/MotionTracker.cpp:383-434): sums in run order divided by the run count.  One dict per stage of the first run: name,
+    recall, precision, veridical (the mean number of surviving veridical quad pairs)."""
+    out = []
+    if not runs or not runs[0]:
+        return out
+    for ref in runs[0]:
+        sum_recall, sum_precision, sum_veridical, count = 0.0, 0.0, 0, 0
+        for run in runs:
+            m = next((g for g in run if g["name"] == ref["name"]), None)
+            if m is not None:
+                sum_recall += m["recall"]
+                sum_precision += m["precision"]
+                sum_veridical += m["veridical"]
+                count += 1
+        if count:
+            out.append(dict(name=ref["name"], recall=sum_recall / float(count), precision=sum_precision / float(count),
+                            veridical=sum_veridical / float(count)))
+    return out
+
+
 class Context:
     """One HIP device workspace (``ebvo_ctx``).  Not thread-safe; one per process and GPU."""
 
@@ -686,6 +716,103 @@ class Context:
         out = self._pose_dict(r)
         out.update(inlier=inlier, quad_geom=geom, rank_order=order)
         return out
+
+    # -- the pose stage under ground truth (get_Quad_for_Pose_Solution's has_gt() branch, Solution_Constraints_Application) --
+    @staticmethod
+    def _row_mask(a, n_kf, what):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        if a.shape != (n_kf,):
+            raise ValueError(f"{what}: one byte per keyframe mate")
+        return a
+
+    def _gt_quads(self, kf_left, kf_right, row_ptr, cf_left, cf_right, row_listed, kf_is_tp):
+        kf_left, kf_right = _edges(kf_left), _edges(kf_right)
+        cf_left, cf_right = _edges(cf_left), _edges(cf_right)
+        row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int32)
+        assert len(kf_left) == len(kf_right) == len(row_ptr) - 1
+        assert len(cf_left) == len(cf_right) == int(row_ptr[-1])
+        n_kf = len(kf_left)
+        return (kf_left, kf_right, row_ptr, cf_left, cf_right, self._row_mask(row_listed, n_kf, "row_listed"),
+                self._row_mask(kf_is_tp, n_kf, "kf_is_tp"))
+
+    def pose_from_quads_gt(self, kf_left, kf_right, row_ptr, cf_left, cf_right, calib, row_listed=None, kf_is_tp=None,
+                           **params) -> dict:
+        """pose_from_quads over the quads of the rows that are listed and TP (ebvo_pose_from_quads_gt); row_listed / kf_is_tp:
+        one byte per keyframe mate or None (all set).  n_quads is the selected count; `inlier` and `quad_geom` are in the full
+        CSR order (zero on quads not selected), `rank_order` holds full-CSR indices, -1 beyond the selected count."""
+        kfL, kfR, rp, cfL, cfR, listed, tp = self._gt_quads(kf_left, kf_right, row_ptr, cf_left, cf_right, row_listed, kf_is_tp)
+        n = int(rp[-1])
+        p, cal, r = self.pose_params(**params), self._calib(calib), _lib.PoseResult()
+        inlier, geom, order = np.zeros(n, dtype=np.uint8), np.zeros((n, 12)), np.zeros(n, dtype=np.int32)
+        self._check(self.lib.ebvo_pose_from_quads_gt(self._ctx, ptr(kfL), ptr(kfR), len(kfL), ptr(rp), ptr(cfL), ptr(cfR), ptr(listed),
+                                                     ptr(tp), C.byref(cal), C.byref(p), C.byref(r), ptr(inlier), ptr(geom),
+                                                     ptr(order)), "ebvo_pose_from_quads_gt")
+        out = self._pose_dict(r)
+        out.update(inlier=inlier, quad_geom=geom, rank_order=order)
+        return out
+
+    def temporal_estimate_pose_gt(self, calib, slot: int = 0, **params) -> dict:
+        """temporal_estimate_pose over the ground-truth rows of a slot armed by temporal_set_gt after temporal_match(stages=1)
+        (ebvo_temporal_estimate_pose_gt)."""
+        p, cal, r = self.pose_params(**params), self._calib(calib), _lib.PoseResult()
+        n_kf, n = C.c_int32(), C.c_int64()
+        self._check(self.lib.ebvo_temporal_final_size(self._ctx, slot, C.byref(n_kf), C.byref(n)), "ebvo_temporal_final_size")
+        inlier = np.zeros(n.value, dtype=np.uint8)
+        self._check(self.lib.ebvo_temporal_estimate_pose_gt(self._ctx, slot, C.byref(cal), C.byref(p), C.byref(r), ptr(inlier)),
+                    "ebvo_temporal_estimate_pose_gt")
+        out = self._pose_dict(r)
+        out["inlier"] = inlier
+        return out
+
+    @staticmethod
+    def _cascade_runs(runs, draw_idx, draw_stage, details):
+        out = []
+        for r in runs:
+            stages = [dict(name=_lib.PC_STAGE_NAMES[g.stage], stage=g.stage, surviving=g.surviving, veridical=g.veridical,
+                           recall=g.recall, precision=g.precision) for g in r.stages]
+            out.append(_CascadeRun(stages, status=r.status, n_quads=r.n_quads, top_n=r.top_n, draws=r.draws))
+        return (out, draw_idx, draw_stage) if details else out
+
+    @staticmethod
+    def _cascade_buffers(p, n_runs, details):
+        """the run records and, for details, the draw arrays; sizes the library refuses are left to it (nothing is allocated
+        for them)"""
+        n_runs = int(n_runs)
+        runs = (_lib.PoseCascadeRun * max(n_runs, 0))()
+        ok = n_runs >= 1 and 0 <= p.max_iterations and n_runs * p.max_iterations <= _lib.PC_MAX_DRAWS
+        idx = np.zeros((n_runs, p.max_iterations, 2), dtype=np.int32) if details and ok else None
+        stage = np.zeros((n_runs, p.max_iterations), dtype=np.uint8) if details and ok else None
+        return n_runs, runs, idx, stage
+
+    def pose_constraint_metrics(self, kf_left, kf_right, row_ptr, cf_left, cf_right, calib, row_listed=None, kf_is_tp=None,
+                                quad_is_tp=None, n_runs: int = 1, details: bool = False, **params):
+        """Solution_Constraints_Application on host arrays (ebvo_pose_constraint_metrics): n_runs runs of max_iterations
+        sampled quad pairs each.  quad_is_tp: b_is_veridical per quad in CSR order or None (none veridical).  Returns a list
+        of runs; a run is a list of five stage dicts (name, stage, surviving, veridical, recall, precision) under the
+        reference's names and carries status, n_quads, top_n and draws as attributes.  details=True: also draw_idx
+        (n_runs x max_iterations x 2 rank positions) and draw_stage (bits 0-2: constraints passed, bit 7: both veridical)."""
+        kfL, kfR, rp, cfL, cfR, listed, tp = self._gt_quads(kf_left, kf_right, row_ptr, cf_left, cf_right, row_listed, kf_is_tp)
+        if quad_is_tp is not None:
+            quad_is_tp = np.ascontiguousarray(quad_is_tp, dtype=np.uint8)
+            if quad_is_tp.shape != (int(rp[-1]),):
+                raise ValueError("quad_is_tp: one byte per quad")
+        p, cal = self.pose_params(**params), self._calib(calib)
+        n_runs, runs, idx, stage = self._cascade_buffers(p, n_runs, details)
+        self._check(self.lib.ebvo_pose_constraint_metrics(self._ctx, ptr(kfL), ptr(kfR), len(kfL), ptr(rp), ptr(cfL), ptr(cfR),
+                                                          ptr(listed), ptr(tp), ptr(quad_is_tp), C.byref(cal), C.byref(p), n_runs, runs,
+                                                          ptr(idx), ptr(stage)), "ebvo_pose_constraint_metrics")
+        return self._cascade_runs(runs, idx, stage, details)
+
+    def temporal_pose_constraint_metrics(self, calib, slot: int = 0, n_runs: int = 1, details: bool = False, **params):
+        """The same on a slot armed by temporal_set_gt after temporal_match(stages=1)
+        (ebvo_temporal_pose_constraint_metrics): b_is_veridical is the slot's Edge Clustering flag."""
+        p, cal = self.pose_params(**params), self._calib(calib)
+        n_runs, runs, idx, stage = self._cascade_buffers(p, n_runs, details)
+        self._check(self.lib.ebvo_temporal_pose_constraint_metrics(self._ctx, slot, C.byref(cal), C.byref(p), n_runs, runs, ptr(idx),
+                                                                   ptr(stage)), "ebvo_temporal_pose_constraint_metrics")
+        return self._cascade_runs(runs, idx, stage, details)
 
     # -- ground-truth evaluation from a disparity map (Find_Stereo_GT_Locations, get_Stereo_Edge_GT_Pairs,
     # -- Evaluate_Stereo_Edge_Correspondences) ---------------------------------------------------------------

@@ -13,7 +13,8 @@
 const char *const g_kernel_names[K_NUM] = {
     "toed_conv",   "toed_nms",   "toed_rowscan", "toed_compact", "toed_finalize", "toed_exact_centre", "toed_exact_mags", "cand_boxes", "epi_lines",
     "cand_count",  "scan",       "cand_fill",    "edge_patches", "ncc_pairs",     "ncc_stored", "misc", "sobel", "gn_refine", "sift",
-    "gt_misc",     "gt_pool",    "gt_census",    "gt_rows",      "tgt_project",   "tgt_veridical", "tgt_rows"};
+    "gt_misc",     "gt_pool",    "gt_census",    "gt_rows",      "tgt_project",   "tgt_veridical", "tgt_rows",
+    "pose_cascade"};
 
 // ------------------------------------------------------------------------------------------
 int ebvo_fail_hip(ebvo_ctx *ctx, hipError_t e, const char *what, const char *file, int line)
@@ -174,7 +175,7 @@ static void slot_destroy(Slot *s)
                        &s->keep,         &s->patches_raw,  &s->patches_norm,   &s->patches_flag,   &s->patches_norm_r,
                        &s->patches_flag_r, &s->pair_left,  &s->sincos,         &s->scratch_b,      &s->scratch_c,
                        &s->scratch_d,    &s->fetch_pack,   &s->pose_in,        &s->pose_geom,      &s->pose_order,
-                       &s->pose_draw,    &s->pose_hyp,       &s->gt_disp,        &s->gt_geom,        &s->gt_flags,
+                       &s->pose_draw,    &s->pose_hyp,       &s->pose_sel,       &s->pose_casc,       &s->gt_disp,        &s->gt_geom,        &s->gt_flags,
                        &s->gt_boxes,     &s->gt_pool_i32,  &s->gt_pool_idx,    &s->gt_rows,        &s->gt_tot,
                        &s->gt_up,        &s->tgt_geom,     &s->tgt_i32,        &s->tgt_idx,        &s->tgt_u8,
                        &s->tgt_rows,     &s->tgt_flags,    &s->tgt_tot,        &s->tgt_up};
@@ -3913,6 +3914,192 @@ extern "C" int ebvo_pose_from_quads(ebvo_ctx *ctx, const ebvo_edge *kf_left, con
     EBVO_HIP(ctx, hipMemcpyAsync(d_cfR, cf_right, eq, hipMemcpyHostToDevice, st));
     EBVO_HIP(ctx, hipMemcpyAsync(d_rp, row_ptr, rb, hipMemcpyHostToDevice, st));
     return pose_run(ctx, s, d_kfL, d_kfR, d_rp, n_kf, d_cfL, d_cfR, n, cal, p, res, inlier, quad_geom, rank_order);
+}
+
+// ---- the pose stage under ground truth (pose_kernels.hip: row selection, constraint cascade) --------------------------
+static bool pose_cascade_args_ok(const ebvo_pose_params *p, int n_runs, const ebvo_pose_cascade_run *runs)
+{
+    return runs && n_runs >= 1 && (int64_t)n_runs * (int64_t)p->max_iterations <= ((int64_t)1 << 24);
+}
+
+// Host quads of a GT call, checked, counted and uploaded into slot 0's own pose buffer.  n_listed / n_sel: listed rows and
+// selected quads, counted here; upload = false: only check and count.
+struct PoseHostQuads
+{
+    const ebvo_edge *kfL = nullptr, *kfR = nullptr, *cfL = nullptr, *cfR = nullptr;
+    const int32_t *rp = nullptr;
+    const uint8_t *on = nullptr, *tp = nullptr;
+    int n = 0;
+    int64_t n_listed = 0, n_sel = 0;
+};
+
+static int pose_host_quads_check(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *kf_right, int n_kf, const int32_t *row_ptr,
+                                 const ebvo_edge *cf_left, const ebvo_edge *cf_right, const uint8_t *row_listed, const uint8_t *kf_is_tp,
+                                 PoseHostQuads *q)
+{
+    if (!ctx || n_kf < 0 || !row_ptr || (n_kf > 0 && (!kf_left || !kf_right)) || row_ptr[0] != 0)
+        return EBVO_ERR_ARG;
+    for (int i = 0; i < n_kf; ++i)
+        if (row_ptr[i + 1] < row_ptr[i])
+            return EBVO_ERR_ARG;
+    q->n = row_ptr[n_kf];
+    if (q->n > 0 && (!cf_left || !cf_right))
+        return EBVO_ERR_ARG;
+    q->n_listed = q->n_sel = 0;
+    for (int i = 0; i < n_kf; ++i)
+    {
+        const bool listed = !row_listed || row_listed[i];
+        q->n_listed += listed;
+        if (listed && (!kf_is_tp || kf_is_tp[i]))
+            q->n_sel += row_ptr[i + 1] - row_ptr[i];
+    }
+    Slot &s = *ctx->slots[0];
+    if (s.in_flight || s.fin_in_flight || s.tq_in_flight)
+    {
+        ctx->last_error = "slot 0 has submitted work in flight; wait for it first";
+        return EBVO_ERR_STATE;
+    }
+    return EBVO_OK;
+}
+
+static int pose_host_quads_upload(ebvo_ctx *ctx, Slot &s, const ebvo_edge *kf_left, const ebvo_edge *kf_right, int n_kf,
+                                  const int32_t *row_ptr, const ebvo_edge *cf_left, const ebvo_edge *cf_right, const uint8_t *row_listed,
+                                  const uint8_t *kf_is_tp, const uint8_t *quad_is_tp, PoseHostQuads *q)
+{
+    const size_t kz = (size_t)n_kf, nz = (size_t)q->n;
+    const size_t ek = sizeof(ebvo_edge) * kz, eq = sizeof(ebvo_edge) * nz, rb = sizeof(int32_t) * (kz + 1);
+    if (int rc = ebvo_grow(ctx, s, s.pose_in, 2 * ek + 2 * eq + rb + kz + nz))
+        return rc;
+    uint8_t *base = (uint8_t *)s.pose_in.p;
+    q->kfL = (ebvo_edge *)base;
+    q->kfR = (ebvo_edge *)(base + ek);
+    q->cfL = (ebvo_edge *)(base + 2 * ek);
+    q->cfR = (ebvo_edge *)(base + 2 * ek + eq);
+    q->rp = (int32_t *)(base + 2 * ek + 2 * eq);
+    uint8_t *d_on = base + 2 * ek + 2 * eq + rb, *d_tp = d_on + kz;
+    q->on = d_on;
+    q->tp = quad_is_tp ? d_tp : nullptr;
+    std::vector<uint8_t> on(kz);
+    for (size_t i = 0; i < kz; ++i)
+        on[i] = (!row_listed || row_listed[i]) && (!kf_is_tp || kf_is_tp[i]);
+    hipStream_t st = s.stream;
+    EBVO_HIP(ctx, hipMemcpyAsync((void *)q->kfL, kf_left, ek, hipMemcpyHostToDevice, st));
+    EBVO_HIP(ctx, hipMemcpyAsync((void *)q->kfR, kf_right, ek, hipMemcpyHostToDevice, st));
+    EBVO_HIP(ctx, hipMemcpyAsync((void *)q->cfL, cf_left, eq, hipMemcpyHostToDevice, st));
+    EBVO_HIP(ctx, hipMemcpyAsync((void *)q->cfR, cf_right, eq, hipMemcpyHostToDevice, st));
+    EBVO_HIP(ctx, hipMemcpyAsync((void *)q->rp, row_ptr, rb, hipMemcpyHostToDevice, st));
+    EBVO_HIP(ctx, hipMemcpyAsync(d_on, on.data(), kz, hipMemcpyHostToDevice, st));
+    if (quad_is_tp)
+        EBVO_HIP(ctx, hipMemcpyAsync(d_tp, quad_is_tp, nz, hipMemcpyHostToDevice, st));
+    EBVO_HIP(ctx, hipStreamSynchronize(st)); // `on` is a local
+    return EBVO_OK;
+}
+
+static bool pose_gt_insufficient(const PoseHostQuads &q, const ebvo_pose_params *p)
+{
+    return q.n_listed < 2 || q.n_sel < 2 || (int64_t)(p->top_rank_fraction * (double)q.n_sel) < 2;
+}
+
+extern "C" int ebvo_pose_from_quads_gt(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *kf_right, int n_kf,
+                                       const int32_t *row_ptr, const ebvo_edge *cf_left, const ebvo_edge *cf_right,
+                                       const uint8_t *row_listed, const uint8_t *kf_is_tp, const ebvo_stereo_calib *cal,
+                                       const ebvo_pose_params *p, ebvo_pose_result *res, uint8_t *inlier, double *quad_geom,
+                                       int32_t *rank_order)
+{
+    if (!ctx || !pose_args_ok(cal, p, res))
+        return EBVO_ERR_ARG;
+    PoseHostQuads q;
+    if (int rc = pose_host_quads_check(ctx, kf_left, kf_right, n_kf, row_ptr, cf_left, cf_right, row_listed, kf_is_tp, &q))
+        return rc;
+    Slot &s = *ctx->slots[0];
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    if (pose_gt_insufficient(q, p)) // nothing to upload or launch
+    {
+        if (int rc = pose_run(ctx, s, nullptr, nullptr, nullptr, 0, nullptr, nullptr, (int)q.n_sel, cal, p, res, nullptr, nullptr, nullptr,
+                              true))
+            return rc;
+        if (inlier && q.n > 0)
+            memset(inlier, 0, (size_t)q.n);
+        return EBVO_OK;
+    }
+    if (int rc = pose_host_quads_upload(ctx, s, kf_left, kf_right, n_kf, row_ptr, cf_left, cf_right, row_listed, kf_is_tp, nullptr, &q))
+        return rc;
+    return pose_run_gt(ctx, s, q.kfL, q.kfR, q.rp, n_kf, q.cfL, q.cfR, q.n, q.on, q.n_listed, cal, p, res, inlier, quad_geom, rank_order);
+}
+
+extern "C" int ebvo_pose_constraint_metrics(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *kf_right, int n_kf,
+                                            const int32_t *row_ptr, const ebvo_edge *cf_left, const ebvo_edge *cf_right,
+                                            const uint8_t *row_listed, const uint8_t *kf_is_tp, const uint8_t *quad_is_tp,
+                                            const ebvo_stereo_calib *cal, const ebvo_pose_params *p, int n_runs,
+                                            ebvo_pose_cascade_run *runs, int32_t *draw_idx, uint8_t *draw_stage)
+{
+    ebvo_pose_result unused;
+    if (!ctx || !pose_args_ok(cal, p, &unused) || !pose_cascade_args_ok(p, n_runs, runs))
+        return EBVO_ERR_ARG;
+    PoseHostQuads q;
+    if (int rc = pose_host_quads_check(ctx, kf_left, kf_right, n_kf, row_ptr, cf_left, cf_right, row_listed, kf_is_tp, &q))
+        return rc;
+    Slot &s = *ctx->slots[0];
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    if (pose_gt_insufficient(q, p))
+    {
+        pose_cascade_insufficient(ctx, p, q.n_sel, n_runs, runs);
+        return EBVO_OK;
+    }
+    if (int rc = pose_host_quads_upload(ctx, s, kf_left, kf_right, n_kf, row_ptr, cf_left, cf_right, row_listed, kf_is_tp, quad_is_tp, &q))
+        return rc;
+    return pose_cascade_run(ctx, s, q.kfL, q.kfR, q.rp, n_kf, q.cfL, q.cfR, q.n, q.on, q.n_listed, q.tp, cal, p, n_runs, runs, draw_idx,
+                            draw_stage);
+}
+
+static int tgt_armed_slot(ebvo_ctx *ctx, int slot, Slot **out);
+
+// the armed slot of the resident GT pose calls: its match formed the final quads
+static int pose_gt_slot(ebvo_ctx *ctx, int slot, Slot **out)
+{
+    if (int rc = tgt_armed_slot(ctx, slot, out))
+        return rc;
+    if ((*out)->tq_final.n < 0)
+    {
+        ctx->last_error = "the slot holds no final quads (ebvo_temporal_match with stages = 1, then ebvo_temporal_set_gt)";
+        return EBVO_ERR_STATE;
+    }
+    return (*out)->tq_final.n > INT32_MAX ? EBVO_ERR_ARG : EBVO_OK;
+}
+
+extern "C" int ebvo_temporal_estimate_pose_gt(ebvo_ctx *ctx, int slot, const ebvo_stereo_calib *cal, const ebvo_pose_params *p,
+                                              ebvo_pose_result *res, uint8_t *inlier)
+{
+    if (!ctx || !pose_args_ok(cal, p, res))
+        return EBVO_ERR_ARG;
+    Slot *sp;
+    if (int rc = pose_gt_slot(ctx, slot, &sp))
+        return rc;
+    Slot &s = *sp;
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    const Slot::TqFinal &F = s.tq_final;
+    const uint8_t *on = (const uint8_t *)s.tgt_u8.p + (size_t)s.tgt_n_kf; // row_on[]: a veridical quad and kf_is_tp
+    return pose_run_gt(ctx, s, ctx->kf_L, ctx->kf_R, F.rp, s.tq_n_kf, F.L, F.R, (int)F.n, on, s.tgt_n_rows, cal, p, res, inlier, nullptr,
+                       nullptr);
+}
+
+extern "C" int ebvo_temporal_pose_constraint_metrics(ebvo_ctx *ctx, int slot, const ebvo_stereo_calib *cal, const ebvo_pose_params *p,
+                                                     int n_runs, ebvo_pose_cascade_run *runs, int32_t *draw_idx, uint8_t *draw_stage)
+{
+    ebvo_pose_result unused;
+    if (!ctx || !pose_args_ok(cal, p, &unused) || !pose_cascade_args_ok(p, n_runs, runs))
+        return EBVO_ERR_ARG;
+    Slot *sp;
+    if (int rc = pose_gt_slot(ctx, slot, &sp))
+        return rc;
+    Slot &s = *sp;
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    const Slot::TqFinal &F = s.tq_final;
+    const uint8_t *on = (const uint8_t *)s.tgt_u8.p + (size_t)s.tgt_n_kf;
+    // the EBVO_TGT_CLUSTER flags of ebvo_temporal_gt_flags; no row is on when arming walked nothing, so they are not read then
+    const uint8_t *tp = (const uint8_t *)s.tgt_flags.p + 2 * (size_t)s.tq_n;
+    return pose_cascade_run(ctx, s, ctx->kf_L, ctx->kf_R, F.rp, s.tq_n_kf, F.L, F.R, (int)F.n, on, s.tgt_n_rows, tp, cal, p, n_runs, runs,
+                            draw_idx, draw_stage);
 }
 
 // the slot's page-locked result arena holds at least `bytes` (a re-allocation waits for copies still heading into the old one).

@@ -39,6 +39,7 @@ enum KernelId
     K_TGT_PROJECT,   // tgt_project
     K_TGT_VERIDICAL, // tgt_veridical<count> and <fill>
     K_TGT_ROWS,      // tgt_rows
+    K_POSE_CASCADE,  // pose_cascade (the constraint cascade; the other pose kernels run under K_MISC)
     K_NUM
 };
 static_assert(K_NUM <= EBVO_MAX_KERNELS, "grow EBVO_MAX_KERNELS");
@@ -171,6 +172,8 @@ struct Slot
     uint64_t tq_kf_gen = 0;                            // the keyframe (ebvo_ctx::kf_gen) the quads were matched against
     GrowBuf pose_in, pose_geom, pose_order, pose_draw, pose_hyp; // pose search (pose_kernels.hip): uploaded quads, geometry, rank
                                                                  // order, one batch of draws, its hypotheses
+    GrowBuf pose_sel, pose_casc; // ground-truth rows: the compacted selection and what is scattered back; the cascade's draws,
+                                 // counters and stage bytes
     // ground-truth evaluation (gt_kernels.hip, ebvo_stereo_set_gt): armed = the buffers below describe the resident pair
     GrowBuf gt_disp, gt_geom, gt_flags, gt_boxes, gt_pool_i32, gt_pool_idx, gt_rows, gt_tot;
     GrowBuf gt_up; // everything ebvo_gt_locate / ebvo_gt_evaluate_rows need (host-array calls: they touch nothing else of slot 0)
@@ -632,7 +635,20 @@ int tgt_rows_enqueue(ebvo_ctx *ctx, Slot &s, const int32_t *d_row_ptr, const ebv
                      int32_t *d_rows, uint8_t *d_is_tp, unsigned long long *d_tot);
 int pose_run(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, const int32_t *d_rp, int n_kf,
              const ebvo_edge *d_cfL, const ebvo_edge *d_cfR, int n, const ebvo_stereo_calib *cal, const ebvo_pose_params *p,
-             ebvo_pose_result *res, uint8_t *inlier, double *quad_geom, int32_t *rank_order);
+             ebvo_pose_result *res, uint8_t *inlier, double *quad_geom, int32_t *rank_order, bool insufficient = false);
+// The same over the rows with d_on[i] != 0 (device bytes per KF mate), compacted on the device; n_listed: the reference's
+// quads_by_kf.size() (fewer than 2: status 1).  inlier / quad_geom / rank_order in the full CSR order.
+int pose_run_gt(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, const int32_t *d_rp, int n_kf,
+                const ebvo_edge *d_cfL, const ebvo_edge *d_cfR, int n, const uint8_t *d_on, int64_t n_listed,
+                const ebvo_stereo_calib *cal, const ebvo_pose_params *p, ebvo_pose_result *res, uint8_t *inlier, double *quad_geom,
+                int32_t *rank_order);
+// Solution_Constraints_Application over the same rows; d_tp (may be NULL): b_is_TP per quad in CSR order
+int pose_cascade_run(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, const int32_t *d_rp, int n_kf,
+                     const ebvo_edge *d_cfL, const ebvo_edge *d_cfR, int n, const uint8_t *d_on, int64_t n_listed, const uint8_t *d_tp,
+                     const ebvo_stereo_calib *cal, const ebvo_pose_params *p, int n_runs, ebvo_pose_cascade_run *runs,
+                     int32_t *draw_idx, uint8_t *draw_stage);
+// status 1 for every run: n selected quads, nothing launched, no random number drawn
+void pose_cascade_insufficient(ebvo_ctx *ctx, const ebvo_pose_params *p, int64_t n, int n_runs, ebvo_pose_cascade_run *runs);
 int misc_fp64_peak(ebvo_ctx *ctx, Slot &s, int iters, double *tf_muladd, double *tf_fma);
 
 #endif

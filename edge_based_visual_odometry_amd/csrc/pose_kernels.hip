@@ -110,7 +110,41 @@ __global__ __launch_bounds__(256) void pose_rank_kernel(const int32_t *__restric
     }
 }
 
-// Apply_Normalized_Length / T1 / T2 / Tangent_Angle_Similarity_Constraint and estimate_Pose_From_a_Quad_Pair
+// Apply_Normalized_Length / T1 / T2 / Tangent_Angle_Similarity_Constraint (:108-134) in the loop's order: the number of
+// constraints the pair passed before its first failure (4 = all of them).  d21 / d21b: Gamma_2 - Gamma_1 and its barred twin,
+// which the pose of a passing pair starts from.  One function for the search (pose_hyp_kernel) and for the constraint
+// cascade (pose_cascade_kernel): the same operations in the same order.
+__device__ static inline int pose_constraints(const double *a, const double *b, const PoseTaus &tau, double *d21, double *d21b)
+{
+    double d12[3], d12b[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+    {
+        d12[i] = a[i] - b[i];
+        d12b[i] = a[3 + i] - b[3 + i];
+        d21[i] = b[i] - a[i];
+        d21b[i] = b[3 + i] - a[3 + i];
+    }
+    // (a zero length ends in NaN / inf: the comparison is false, the draw is rejected, as in the reference)
+    const double lG = sqrt(dot3(d12, d12)), lGb = sqrt(dot3(d12b, d12b));
+    if (!(fabs(lG - lGb) / lG < tau.len))
+        return 0;
+    const double n21 = sqrt(dot3(d21, d21)), n21b = sqrt(dot3(d21b, d21b));
+    {
+        const double c = dot3(d21, a + 6) / n21, cb = dot3(d21b, a + 9) / n21b;
+        if (!(fabs(fabs(c) - fabs(cb)) < tau.t1))
+            return 1;
+    }
+    {
+        const double c = dot3(d21, b + 6) / n21, cb = dot3(d21b, b + 9) / n21b;
+        if (!(fabs(fabs(c) - fabs(cb)) < tau.t2))
+            return 2;
+    }
+    const double c = dot3(a + 6, b + 6), cb = dot3(a + 9, b + 9);
+    return fabs(fabs(c) - fabs(cb)) < tau.tan ? 4 : 3;
+}
+
+// the four constraints and, if they pass, estimate_Pose_From_a_Quad_Pair
 __global__ void pose_hyp_kernel(const int32_t *__restrict__ draws, int nb, const int32_t *__restrict__ order,
                                 const double *__restrict__ geom, PoseTaus tau, uint8_t *__restrict__ ok, double *__restrict__ hyp)
 {
@@ -118,34 +152,8 @@ __global__ void pose_hyp_kernel(const int32_t *__restrict__ draws, int nb, const
     {
         const double *a = geom + (size_t)order[draws[2 * d]] * 12;     // q1
         const double *b = geom + (size_t)order[draws[2 * d + 1]] * 12; // q2
-        double d12[3], d12b[3], d21[3], d21b[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-        {
-            d12[i] = a[i] - b[i];
-            d12b[i] = a[3 + i] - b[3 + i];
-            d21[i] = b[i] - a[i];
-            d21b[i] = b[3 + i] - a[3 + i];
-        }
-        // (a zero length ends in NaN / inf: the comparison is false, the draw is rejected, as in the reference)
-        const double lG = sqrt(dot3(d12, d12)), lGb = sqrt(dot3(d12b, d12b));
-        bool pass = fabs(lG - lGb) / lG < tau.len;
-        const double n21 = sqrt(dot3(d21, d21)), n21b = sqrt(dot3(d21b, d21b));
-        if (pass)
-        {
-            const double c = dot3(d21, a + 6) / n21, cb = dot3(d21b, a + 9) / n21b;
-            pass = fabs(fabs(c) - fabs(cb)) < tau.t1;
-        }
-        if (pass)
-        {
-            const double c = dot3(d21, b + 6) / n21, cb = dot3(d21b, b + 9) / n21b;
-            pass = fabs(fabs(c) - fabs(cb)) < tau.t2;
-        }
-        if (pass)
-        {
-            const double c = dot3(a + 6, b + 6), cb = dot3(a + 9, b + 9);
-            pass = fabs(fabs(c) - fabs(cb)) < tau.tan;
-        }
+        double d21[3], d21b[3];
+        const bool pass = pose_constraints(a, b, tau, d21, d21b) == 4;
         ok[d] = pass ? 1 : 0;
         if (!pass)
             continue;
@@ -254,6 +262,153 @@ __global__ void pose_mask_kernel(PoseRt H, const double *__restrict__ pts, int n
     }
 }
 
+// ---- the search and the constraint cascade over ground-truth rows (the has_gt() branch of get_Quad_for_Pose_Solution :68-106)
+// The selected rows are COMPACTED on the device and the kernels above run unchanged on the compacted arrays: dropping rows
+// does not change the relative order of the rest under (row length, KF index, candidate index).
+//   pose_select_scan_kernel     one block: exclusive scans over on[i] (compacted row) and on[i] * len[i] (compacted quad
+//                               offset), the compacted row_ptr and the two totals
+//   pose_select_gather_kernel   one thread per selected row: its KF mate, its quads, their CSR indices (map) and flags
+//   pose_scatter_kernel         mask and geometry back to the CSR order, the rank order as CSR indices, -1 beyond
+//   pose_cascade_kernel         Solution_Constraints_Application (:255-381): one thread per draw, grid.y = runs
+constexpr int POSE_SCAN_T = 256;
+constexpr int POSE_CASC_T = 256;
+constexpr int POSE_CASC_COUNTERS = 2 * EBVO_PC_NUM_STAGES; // per run: surviving per stage, then veridical per stage
+
+__global__ __launch_bounds__(POSE_SCAN_T) void pose_select_scan_kernel(const uint8_t *__restrict__ on, const int32_t *__restrict__ rp,
+                                                                      int n_kf, int32_t *__restrict__ crow, int32_t *__restrict__ cq,
+                                                                      int32_t *__restrict__ crp, int32_t *__restrict__ tot)
+{
+    __shared__ int32_t sr[POSE_SCAN_T], sq[POSE_SCAN_T];
+    const int t = threadIdx.x;
+    int32_t rows = 0, quads = 0; // the totals of the tiles before this one (the same in every thread)
+    for (int base = 0; base < n_kf; base += POSE_SCAN_T)
+    {
+        const int i = base + t;
+        const bool o = i < n_kf && on[i];
+        const int32_t r = o ? 1 : 0, q = o ? rp[i + 1] - rp[i] : 0;
+        sr[t] = r;
+        sq[t] = q;
+        __syncthreads();
+        for (int off = 1; off < POSE_SCAN_T; off <<= 1)
+        {
+            const int32_t ar = t >= off ? sr[t - off] : 0, aq = t >= off ? sq[t - off] : 0;
+            __syncthreads();
+            sr[t] += ar;
+            sq[t] += aq;
+            __syncthreads();
+        }
+        if (i < n_kf)
+        {
+            crow[i] = rows + sr[t] - r;
+            cq[i] = quads + sq[t] - q;
+            if (o)
+                crp[rows + sr[t] - r] = quads + sq[t] - q;
+        }
+        rows += sr[POSE_SCAN_T - 1];
+        quads += sq[POSE_SCAN_T - 1];
+        __syncthreads();
+    }
+    if (t == 0)
+    {
+        crp[rows] = quads;
+        tot[0] = rows;
+        tot[1] = quads;
+    }
+}
+
+// tp (may be NULL: no quad is veridical): b_is_TP per quad in CSR order; otp (may be NULL): the same per compacted quad
+__global__ void pose_select_gather_kernel(const uint8_t *__restrict__ on, const int32_t *__restrict__ rp, int n_kf,
+                                          const int32_t *__restrict__ crow, const int32_t *__restrict__ cq,
+                                          const ebvo_edge *__restrict__ kfL, const ebvo_edge *__restrict__ kfR,
+                                          const ebvo_edge *__restrict__ cfL, const ebvo_edge *__restrict__ cfR,
+                                          const uint8_t *__restrict__ tp, ebvo_edge *__restrict__ okfL, ebvo_edge *__restrict__ okfR,
+                                          ebvo_edge *__restrict__ ocfL, ebvo_edge *__restrict__ ocfR, int32_t *__restrict__ map,
+                                          uint8_t *__restrict__ otp)
+{
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_kf; i += gridDim.x * blockDim.x)
+    {
+        if (!on[i])
+            continue;
+        const int r = crow[i], q0 = rp[i], len = rp[i + 1] - q0, o0 = cq[i];
+        okfL[r] = kfL[i];
+        okfR[r] = kfR[i];
+        for (int c = 0; c < len; ++c)
+        {
+            ocfL[o0 + c] = cfL[q0 + c];
+            ocfR[o0 + c] = cfR[q0 + c];
+            map[o0 + c] = q0 + c;
+            if (otp)
+                otp[o0 + c] = tp ? (tp[q0 + c] ? 1 : 0) : 0;
+        }
+    }
+}
+
+// n: selected quads, n_full: all quads.  mask / geom (may be NULL) were zeroed before; order (may be NULL) has n_full entries
+__global__ void pose_scatter_kernel(const int32_t *__restrict__ map, int n, int n_full, const uint8_t *__restrict__ cmask,
+                                    uint8_t *__restrict__ mask, const double *__restrict__ cgeom, double *__restrict__ geom,
+                                    const int32_t *__restrict__ corder, int32_t *__restrict__ order)
+{
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n_full; k += gridDim.x * blockDim.x)
+    {
+        if (k < n)
+        {
+            const size_t m = (size_t)map[k];
+            if (mask)
+                mask[m] = cmask[k];
+            if (geom)
+#pragma unroll
+                for (int j = 0; j < 12; ++j)
+                    geom[m * 12 + j] = cgeom[(size_t)k * 12 + j];
+        }
+        if (order)
+            order[k] = k < n ? map[corder[k]] : -1;
+    }
+}
+
+// grid (chunks of a run's draws, runs): no block straddles two runs.  stage[]: bits 0-2 the constraints passed, bit 7 both
+// quads veridical.  counters[run][POSE_CASC_COUNTERS] zeroed before: ballot + popcount into LDS, then one integer atomic per
+// block and counter (order-free sums, as in pose_score_kernel).
+__global__ __launch_bounds__(POSE_CASC_T) void pose_cascade_kernel(const int32_t *__restrict__ draws, int per_run, int n_runs,
+                                                                  const int32_t *__restrict__ order, const double *__restrict__ geom,
+                                                                  const uint8_t *__restrict__ tp, PoseTaus tau,
+                                                                  uint8_t *__restrict__ stage, int32_t *__restrict__ counters)
+{
+    __shared__ int cnt[POSE_CASC_COUNTERS];
+    const int d = blockIdx.x * POSE_CASC_T + threadIdx.x;
+    const bool have = d < per_run;
+    const int lane = threadIdx.x & (warpSize - 1);
+    for (int run = blockIdx.y; run < n_runs; run += gridDim.y)
+    {
+        if (threadIdx.x < POSE_CASC_COUNTERS)
+            cnt[threadIdx.x] = 0;
+        __syncthreads();
+        int np = -1;
+        bool ver = false;
+        if (have)
+        {
+            const size_t g = (size_t)run * (size_t)per_run + (size_t)d;
+            const int q1 = order[draws[2 * g]], q2 = order[draws[2 * g + 1]];
+            double d21[3], d21b[3];
+            np = pose_constraints(geom + (size_t)q1 * 12, geom + (size_t)q2 * 12, tau, d21, d21b);
+            ver = tp[q1] && tp[q2];
+            stage[g] = (uint8_t)(np | (ver ? 0x80 : 0));
+        }
+#pragma unroll
+        for (int k = 0; k < EBVO_PC_NUM_STAGES; ++k)
+        {
+            const unsigned long long m = __ballot(np >= k), mv = __ballot(np >= k && ver);
+            if (lane == 0 && m)
+                atomicAdd(&cnt[k], (int)__popcll(m));
+            if (lane == 0 && mv)
+                atomicAdd(&cnt[EBVO_PC_NUM_STAGES + k], (int)__popcll(mv));
+        }
+        __syncthreads();
+        if (threadIdx.x < POSE_CASC_COUNTERS && cnt[threadIdx.x])
+            atomicAdd(&counters[(size_t)run * POSE_CASC_COUNTERS + threadIdx.x], cnt[threadIdx.x]);
+        __syncthreads();
+    }
+}
+
 unsigned grid_for(int64_t n, int64_t cap)
 {
     const int64_t b = (n + 255) / 256;
@@ -307,7 +462,7 @@ void draw_pairs(PoseRng &g, int64_t top_n, int nb, int32_t *out)
 
 int pose_run(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, const int32_t *d_rp, int n_kf,
              const ebvo_edge *d_cfL, const ebvo_edge *d_cfR, int n, const ebvo_stereo_calib *cal, const ebvo_pose_params *p,
-             ebvo_pose_result *res, uint8_t *inlier, double *quad_geom, int32_t *rank_order)
+             ebvo_pose_result *res, uint8_t *inlier, double *quad_geom, int32_t *rank_order, bool insufficient)
 {
     ebvo_pose_result r;
     memset(&r, 0, sizeof r);
@@ -319,7 +474,7 @@ int pose_run(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_
     PoseRng &g = ctx->pose_rng;
     if (!p->continue_stream || !g.seeded)
         rng_seed(g, p->rand_seed);
-    if (n < 2 || r.top_n < 2)
+    if (insufficient || n < 2 || r.top_n < 2)
     {
         r.status = 1;
         if (inlier && n > 0)
@@ -463,5 +618,225 @@ int pose_run(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_
     }
     EBVO_HIP(ctx, hipStreamSynchronize(st));
     *res = r;
+    return EBVO_OK;
+}
+
+// ---- ground-truth rows ---------------------------------------------------------------------------------------------------
+namespace
+{
+struct PoseSel // the selected rows, compacted (pointers into Slot::pose_sel)
+{
+    ebvo_edge *kfL, *kfR, *cfL, *cfR;
+    double *full_geom;
+    int32_t *rp, *map, *crow, *cq, *tot, *full_order;
+    uint8_t *tp, *full_mask;
+    int n_rows, n;
+};
+
+// d_on: per KF mate, its quads are selected; d_tp (may be NULL): b_is_TP per quad.  Waits for the two totals.
+int pose_select(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, const int32_t *d_rp, int n_kf,
+                const ebvo_edge *d_cfL, const ebvo_edge *d_cfR, int n, const uint8_t *d_on, const uint8_t *d_tp, bool want_tp, PoseSel *out)
+{
+    const size_t kz = (size_t)n_kf, nz = (size_t)n;
+    const size_t o_geom = sizeof(ebvo_edge) * 2 * (kz + nz), o_i32 = o_geom + sizeof(double) * 12 * nz,
+                 n_i32 = (kz + 1) + nz + 2 * kz + 2 + nz, o_u8 = o_i32 + sizeof(int32_t) * n_i32;
+    if (int rc = ebvo_grow(ctx, s, s.pose_sel, o_u8 + 2 * nz + 64))
+        return rc;
+    char *base = (char *)s.pose_sel.p;
+    PoseSel S;
+    S.kfL = (ebvo_edge *)base;
+    S.kfR = S.kfL + kz;
+    S.cfL = S.kfR + kz;
+    S.cfR = S.cfL + nz;
+    S.full_geom = (double *)(base + o_geom);
+    S.rp = (int32_t *)(base + o_i32);
+    S.map = S.rp + kz + 1;
+    S.crow = S.map + nz;
+    S.cq = S.crow + kz;
+    S.tot = S.cq + kz;
+    S.full_order = S.tot + 2;
+    S.tp = (uint8_t *)(base + o_u8);
+    S.full_mask = S.tp + nz;
+    S.n_rows = S.n = 0;
+    if (n_kf > 0 && n > 0)
+    {
+        hipStream_t st = s.stream;
+        int32_t tot[2] = {0, 0};
+        {
+            ProfScope ps(ctx, s, K_MISC);
+            hipLaunchKernelGGL(pose_select_scan_kernel, dim3(1), dim3(POSE_SCAN_T), 0, st, d_on, d_rp, n_kf, S.crow, S.cq, S.rp, S.tot);
+        }
+        EBVO_HIP(ctx, hipGetLastError());
+        EBVO_HIP(ctx, hipMemcpyAsync(tot, S.tot, sizeof tot, hipMemcpyDeviceToHost, st));
+        EBVO_HIP(ctx, hipStreamSynchronize(st));
+        if (tot[0] < 0 || tot[0] > n_kf || tot[1] < 0 || tot[1] > n)
+        {
+            ctx->last_error = "pose row selection: the device totals exceed the rows given";
+            return EBVO_ERR_HIP;
+        }
+        S.n_rows = tot[0];
+        S.n = tot[1];
+        if (S.n > 0)
+        {
+            ProfScope ps(ctx, s, K_MISC);
+            hipLaunchKernelGGL(pose_select_gather_kernel, dim3(grid_for(n_kf, 2048)), dim3(256), 0, st, d_on, d_rp, n_kf, S.crow, S.cq,
+                               d_kfL, d_kfR, d_cfL, d_cfR, d_tp, S.kfL, S.kfR, S.cfL, S.cfR, S.map, want_tp ? S.tp : nullptr);
+            EBVO_HIP(ctx, hipGetLastError());
+        }
+    }
+    *out = S;
+    return EBVO_OK;
+}
+} // namespace
+
+int pose_run_gt(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, const int32_t *d_rp, int n_kf,
+                const ebvo_edge *d_cfL, const ebvo_edge *d_cfR, int n, const uint8_t *d_on, int64_t n_listed,
+                const ebvo_stereo_calib *cal, const ebvo_pose_params *p, ebvo_pose_result *res, uint8_t *inlier, double *quad_geom,
+                int32_t *rank_order)
+{
+    PoseSel S;
+    if (int rc = pose_select(ctx, s, d_kfL, d_kfR, d_rp, n_kf, d_cfL, d_cfR, n, d_on, nullptr, false, &S))
+        return rc;
+    const size_t nz = (size_t)n, cz = (size_t)S.n;
+    std::vector<uint8_t> cmask(inlier ? cz : 0); // pose_run forms the mask on the device only for a caller that asks for it
+    if (int rc = pose_run(ctx, s, S.kfL, S.kfR, S.rp, S.n_rows, S.cfL, S.cfR, S.n, cal, p, res, inlier ? cmask.data() : nullptr, nullptr,
+                          nullptr, n_listed < 2))
+        return rc;
+    if (inlier && n > 0)
+        memset(inlier, 0, nz);
+    if (res->status == 1 || !(inlier || quad_geom || rank_order))
+        return EBVO_OK;
+    // pose_run left the compacted geometry, rank order and mask in the slot (its own layout over cz quads)
+    hipStream_t st = s.stream;
+    const double *c_geom = (const double *)s.pose_geom.p;
+    const int32_t *c_order = (const int32_t *)s.pose_order.p;
+    const uint8_t *c_mask = (const uint8_t *)(c_order + cz);
+    const bool mask = inlier && res->found;
+    if (mask)
+        EBVO_HIP(ctx, hipMemsetAsync(S.full_mask, 0, nz, st));
+    if (quad_geom)
+        EBVO_HIP(ctx, hipMemsetAsync(S.full_geom, 0, sizeof(double) * 12 * nz, st));
+    {
+        ProfScope ps(ctx, s, K_MISC);
+        hipLaunchKernelGGL(pose_scatter_kernel, dim3(grid_for(n, 2048)), dim3(256), 0, st, S.map, S.n, n, mask ? c_mask : nullptr,
+                           mask ? S.full_mask : nullptr, c_geom, quad_geom ? S.full_geom : nullptr, c_order,
+                           rank_order ? S.full_order : nullptr);
+    }
+    EBVO_HIP(ctx, hipGetLastError());
+    if (mask)
+        EBVO_HIP(ctx, hipMemcpyAsync(inlier, S.full_mask, nz, hipMemcpyDeviceToHost, st));
+    if (quad_geom)
+        EBVO_HIP(ctx, hipMemcpyAsync(quad_geom, S.full_geom, sizeof(double) * 12 * nz, hipMemcpyDeviceToHost, st));
+    if (rank_order)
+        EBVO_HIP(ctx, hipMemcpyAsync(rank_order, S.full_order, sizeof(int32_t) * nz, hipMemcpyDeviceToHost, st));
+    EBVO_HIP(ctx, hipStreamSynchronize(st));
+    return EBVO_OK;
+}
+
+void pose_cascade_insufficient(ebvo_ctx *ctx, const ebvo_pose_params *p, int64_t n, int n_runs, ebvo_pose_cascade_run *runs)
+{
+    PoseRng &g = ctx->pose_rng;
+    if (!p->continue_stream || !g.seeded)
+        rng_seed(g, p->rand_seed);
+    for (int k = 0; k < n_runs; ++k)
+    {
+        ebvo_pose_cascade_run &r = runs[k];
+        memset(&r, 0, sizeof r);
+        r.status = 1;
+        r.n_quads = n;
+        r.top_n = (int64_t)(p->top_rank_fraction * (double)n);
+        for (int j = 0; j < EBVO_PC_NUM_STAGES; ++j)
+            r.stages[j].stage = j;
+    }
+}
+
+int pose_cascade_run(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, const int32_t *d_rp, int n_kf,
+                     const ebvo_edge *d_cfL, const ebvo_edge *d_cfR, int n, const uint8_t *d_on, int64_t n_listed, const uint8_t *d_tp,
+                     const ebvo_stereo_calib *cal, const ebvo_pose_params *p, int n_runs, ebvo_pose_cascade_run *runs,
+                     int32_t *draw_idx, uint8_t *draw_stage)
+{
+    PoseSel S;
+    if (int rc = pose_select(ctx, s, d_kfL, d_kfR, d_rp, n_kf, d_cfL, d_cfR, n, d_on, d_tp, true, &S))
+        return rc;
+    const int64_t top_n = (int64_t)(p->top_rank_fraction * (double)S.n);
+    if (n_listed < 2 || S.n < 2 || top_n < 2)
+    {
+        pose_cascade_insufficient(ctx, p, S.n, n_runs, runs);
+        return EBVO_OK;
+    }
+    PoseRng &g = ctx->pose_rng;
+    if (!p->continue_stream || !g.seeded)
+        rng_seed(g, p->rand_seed);
+    const int per_run = p->max_iterations;
+    const size_t cz = (size_t)S.n, dz = (size_t)n_runs * (size_t)per_run, rz = (size_t)n_runs;
+    int rc;
+    if ((rc = ebvo_grow(ctx, s, s.pose_geom, sizeof(double) * 17 * cz)) || (rc = ebvo_grow(ctx, s, s.pose_order, (sizeof(int32_t) + 1) * cz)) ||
+        (rc = ebvo_grow(ctx, s, s.pose_casc, sizeof(int32_t) * (2 * dz + POSE_CASC_COUNTERS * rz) + dz + 64)))
+        return rc;
+    double *d_geom = (double *)s.pose_geom.p, *d_pts = d_geom + 12 * cz;
+    int32_t *d_order = (int32_t *)s.pose_order.p, *d_draws = (int32_t *)s.pose_casc.p, *d_cnt = d_draws + 2 * dz;
+    uint8_t *d_stage = (uint8_t *)(d_cnt + POSE_CASC_COUNTERS * rz);
+    hipStream_t st = s.stream;
+    std::vector<int32_t> draws(2 * dz), cnt(POSE_CASC_COUNTERS * rz, 0);
+    EBVO_HIP(ctx, hipMemsetAsync(d_cnt, 0, sizeof(int32_t) * POSE_CASC_COUNTERS * rz, st));
+    if (dz)
+    {
+        const FinalCalib C = final_calib_host(cal->K_left, cal->K_left, cal->R21, cal->T21);
+        const PoseTaus tau{p->tau_length, p->tau_t1, p->tau_t2, p->tau_tangent};
+        {
+            ProfScope ps(ctx, s, K_MISC);
+            hipLaunchKernelGGL(pose_prepare_kernel, dim3(grid_for(S.n, 2048)), dim3(256), 0, st, C, S.kfL, S.kfR, S.rp, S.n_rows, S.cfL,
+                               S.cfR, S.n, d_geom, d_pts);
+            hipLaunchKernelGGL(pose_rank_kernel, dim3(grid_for(S.n_rows, 1 << 30)), dim3(256), 0, st, S.rp, S.n_rows, d_order);
+        }
+        EBVO_HIP(ctx, hipGetLastError());
+        // every draw of every run depends on the random stream alone: run k + 1 continues where run k stopped
+        draw_pairs(g, top_n, (int)dz, draws.data());
+        EBVO_HIP(ctx, hipMemcpyAsync(d_draws, draws.data(), sizeof(int32_t) * 2 * dz, hipMemcpyHostToDevice, st));
+        {
+            ProfScope ps(ctx, s, K_POSE_CASCADE);
+            hipLaunchKernelGGL(pose_cascade_kernel, dim3((unsigned)((per_run + POSE_CASC_T - 1) / POSE_CASC_T), (unsigned)std::min(n_runs, 32768)),
+                               dim3(POSE_CASC_T), 0, st, d_draws, per_run, n_runs, d_order, d_geom, S.tp, tau, d_stage, d_cnt);
+        }
+        EBVO_HIP(ctx, hipGetLastError());
+        EBVO_HIP(ctx, hipMemcpyAsync(cnt.data(), d_cnt, sizeof(int32_t) * POSE_CASC_COUNTERS * rz, hipMemcpyDeviceToHost, st));
+        if (draw_stage)
+            EBVO_HIP(ctx, hipMemcpyAsync(draw_stage, d_stage, dz, hipMemcpyDeviceToHost, st));
+        EBVO_HIP(ctx, hipStreamSynchronize(st));
+        if (draw_idx)
+            memcpy(draw_idx, draws.data(), sizeof(int32_t) * 2 * dz);
+    }
+    for (int k = 0; k < n_runs; ++k)
+    {
+        const int32_t *c = cnt.data() + (size_t)k * POSE_CASC_COUNTERS;
+        if (c[0] != per_run)
+        {
+            ctx->last_error = "constraint cascade: the device counted other draws than were drawn";
+            return EBVO_ERR_HIP;
+        }
+        ebvo_pose_cascade_run &r = runs[k];
+        memset(&r, 0, sizeof r);
+        r.n_quads = S.n;
+        r.top_n = top_n;
+        r.draws = per_run;
+        const int64_t initial = c[EBVO_PC_NUM_STAGES];
+        for (int j = 0; j < EBVO_PC_NUM_STAGES; ++j)
+        {
+            ebvo_pose_cascade_stage &g2 = r.stages[j];
+            g2.stage = j;
+            g2.surviving = c[j];
+            g2.veridical = c[EBVO_PC_NUM_STAGES + j];
+            if (j == EBVO_PC_BASELINE)
+            {
+                g2.precision = static_cast<double>(g2.veridical) / static_cast<double>(per_run);
+                g2.recall = 1.0;
+            }
+            else
+            {
+                g2.recall = static_cast<double>(g2.veridical) / static_cast<double>(initial);
+                g2.precision = (g2.surviving == 0) ? 0.0 : static_cast<double>(g2.veridical) / static_cast<double>(g2.surviving);
+            }
+        }
+    }
     return EBVO_OK;
 }

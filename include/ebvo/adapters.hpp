@@ -30,7 +30,9 @@
 #include <cstdio>
 #include <fstream>
 #include <cstring>
+#include <iomanip>
 #include <memory>
+#include <ostream>
 #include <string>
 #include <utility>
 #include <vector>
@@ -822,6 +824,9 @@ class TemporalMatcherHIP
 // mirror Ransac_Options / Ransac_State (include/MotionTracker.h); `opt` defaults to the reference's values (plus TAU_C1..4).
 // Returns false, with the identity pose, where the reference returns false (fewer than two quads to sample) and on an error
 // (last_status); a search that hit the draw cap (pose.status = 2) returns true with the best hypothesis so far.
+// On a slot armed with ground truth (ebvo_temporal_set_gt after the match), gt_rows = true runs the search the reference runs
+// under has_gt() -- over the quads of the listed, true-positive keyframe mates -- and Solution_Constraints_Application /
+// Print_Quad_Pairs_Metrics_Statistics (:255-434) report the recall and precision of the four quad-pair constraints.
 class MotionTrackerHIP
 {
   public:
@@ -845,7 +850,16 @@ class MotionTrackerHIP
         ebvo_pose_result pose{};      // every field of the search
     };
 
-    bool estimate_Relative_Pose_From_Quad_Pairs(int slot, const Ransac_Options &opt, Ransac_State &state, bool want_inliers = false)
+    struct Quad_Pair_Evaluation_Metrics // include/MotionTracker.h
+    {
+        std::string stage_name;
+        double recall;
+        double precision;
+        size_t num_of_surviving_veridical_quad_pairs;
+    };
+
+    bool estimate_Relative_Pose_From_Quad_Pairs(int slot, const Ransac_Options &opt, Ransac_State &state, bool want_inliers = false,
+                                                bool gt_rows = false)
     {
         state = Ransac_State();
         int32_t n_kf = 0;
@@ -855,9 +869,10 @@ class MotionTrackerHIP
             return false;
         if (want_inliers)
             state.inliers.assign((size_t)n_final, 0);
-        last_status = ebvo_temporal_estimate_pose(ctx_->get(), slot, &calib_, &opt.p, &state.pose,
-                                                  want_inliers ? state.inliers.data() : nullptr);
-        if (!report(*ctx_, last_status, "ebvo_temporal_estimate_pose"))
+        uint8_t *mask = want_inliers ? state.inliers.data() : nullptr;
+        last_status = gt_rows ? ebvo_temporal_estimate_pose_gt(ctx_->get(), slot, &calib_, &opt.p, &state.pose, mask)
+                              : ebvo_temporal_estimate_pose(ctx_->get(), slot, &calib_, &opt.p, &state.pose, mask);
+        if (!report(*ctx_, last_status, gt_rows ? "ebvo_temporal_estimate_pose_gt" : "ebvo_temporal_estimate_pose"))
             return false;
         const ebvo_pose_result &r = state.pose;
         std::copy(r.R, r.R + 9, state.R.begin());
@@ -867,6 +882,65 @@ class MotionTrackerHIP
         state.best_minimal_inlier_count = (size_t)r.best_inliers;
         state.dynamic_max_iter = (size_t)r.dynamic_max_iter;
         return r.status != 1;
+    }
+
+    // n_runs calls of the reference's Solution_Constraints_Application (src/Pipeline.cpp:198-203 makes 20) in one device
+    // call: one vector of five stages per run.  Empty on an error (last_status) and when the slot has too few quads.
+    std::vector<std::vector<Quad_Pair_Evaluation_Metrics>> Solution_Constraints_Application(int slot, const Ransac_Options &opt,
+                                                                                             int n_runs = 1)
+    {
+        static const char *const names[EBVO_PC_NUM_STAGES] = {"Baseline", "Normalized Length Constraint",
+                                                              "T1 Angle Similarity Constraint", "T2 Angle Similarity Constraint",
+                                                              "Tangent Angle Similarity Constraint"};
+        std::vector<std::vector<Quad_Pair_Evaluation_Metrics>> out;
+        std::vector<ebvo_pose_cascade_run> runs((size_t)(n_runs > 0 ? n_runs : 0));
+        last_status = ebvo_temporal_pose_constraint_metrics(ctx_->get(), slot, &calib_, &opt.p, n_runs, runs.data(), nullptr, nullptr);
+        if (!report(*ctx_, last_status, "ebvo_temporal_pose_constraint_metrics"))
+            return out;
+        for (const ebvo_pose_cascade_run &r : runs)
+        {
+            if (r.status != 0)
+                continue;
+            std::vector<Quad_Pair_Evaluation_Metrics> m;
+            for (const ebvo_pose_cascade_stage &g : r.stages)
+                m.push_back({names[g.stage], g.recall, g.precision, (size_t)g.veridical});
+            out.push_back(std::move(m));
+        }
+        return out;
+    }
+
+    // the per-stage means over the runs, formed and laid out as the reference does (:383-434)
+    static void Print_Quad_Pairs_Metrics_Statistics(const std::vector<std::vector<Quad_Pair_Evaluation_Metrics>> &all, std::ostream &os)
+    {
+        if (all.empty() || all.front().empty())
+            return;
+        os << "\n===== Quad Pair Constraints Metrics (Solution Constraints Application) =====" << std::endl;
+        os << "               Stage               |         Recall         |        Precision       |       Number of Surviving "
+              "Veridical Quad Pairs"
+           << std::endl;
+        for (const auto &ref_metric : all.front())
+        {
+            double sum_recall = 0.0, sum_precision = 0.0;
+            std::size_t sum_num_veridical = 0, count = 0;
+            for (const auto &per_run : all)
+            {
+                auto it = std::find_if(per_run.begin(), per_run.end(), [&ref_metric](const Quad_Pair_Evaluation_Metrics &m) {
+                    return m.stage_name == ref_metric.stage_name;
+                });
+                if (it != per_run.end())
+                {
+                    sum_recall += it->recall;
+                    sum_precision += it->precision;
+                    sum_num_veridical += it->num_of_surviving_veridical_quad_pairs;
+                    ++count;
+                }
+            }
+            if (count > 0)
+                os << std::setw(35) << ref_metric.stage_name << " | " << std::setw(20) << sum_recall / static_cast<double>(count) << " | "
+                   << std::setw(20) << sum_precision / static_cast<double>(count) << " | " << std::setw(20)
+                   << sum_num_veridical / static_cast<double>(count) << std::endl;
+        }
+        os << std::endl;
     }
 
   private:

@@ -37,7 +37,9 @@ extern "C" {
                               stage-wise calls (ebvo_toed_resident, ebvo_epi_candidates_resident, ebvo_ncc_pairs_resident); 6: ebvo_toed_screen_audit, ebvo_stereo_upload_async, ebvo_host_register, ebvo_stereo_fetch_compact_begin / _end, ebvo_stereo_pushed_view;
                               still 6 with the additive pose search: ebvo_pose_params / _result, ebvo_pose_default_params,
                               ebvo_temporal_estimate_pose, ebvo_pose_from_quads, ebvo_temporal_final_size,
-                              ebvo_debug_set key 20 */
+                              ebvo_debug_set key 20; and with the additive pose stage under ground truth:
+                              ebvo_pose_from_quads_gt, ebvo_temporal_estimate_pose_gt, ebvo_pose_constraint_metrics,
+                              ebvo_temporal_pose_constraint_metrics */
 
 typedef struct ebvo_ctx ebvo_ctx;
 
@@ -576,7 +578,8 @@ int ebvo_temporal_fetch(ebvo_ctx *ctx, int slot, int32_t *row_ptr, int32_t *col_
  *     cluster centres (get_Gammas_and_Tangents_From_Quads :28-66): columns 6-11 of ebvo_finalize_pairs with K_right := K_left
  *     (the reference uses get_left_calib_matrix() for both cameras here; K_right of `cal` is not read);
  *   - rank order (:90-103): ascending row length of the KF mate, then KF index, then candidate index; every quad is kept
- *     (the has_gt() filter on b_is_veridical is not applied here; ebvo_temporal_gt_flags returns that flag per final quad);
+ *     (the has_gt() filter on the keyframe mates is not applied here: ebvo_pose_from_quads_gt /
+ *     ebvo_temporal_estimate_pose_gt below apply it, and ebvo_pose_constraint_metrics reads b_is_veridical);
  *     top_n = (size_t)(top_rank_fraction * n_quads);
  *   - the loop: termination test at its top (iterations > min_iterations && iterations > dynamic_max_iter), two indices
  *     rand() % top_n redrawn together while equal, the length / T1 / T2 / tangent constraints (:108-134; a rejected draw
@@ -643,6 +646,76 @@ int ebvo_pose_from_quads(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edg
                          const ebvo_edge *cf_left, const ebvo_edge *cf_right, const ebvo_stereo_calib *cal,
                          const ebvo_pose_params *p, ebvo_pose_result *res, uint8_t *inlier, double *quad_geom,
                          int32_t *rank_order);
+
+/* ---- the pose stage under ground truth (the has_gt() == true branch of src/MotionTracker.cpp:68-106, :255-381) -------- */
+/* Selected quads.  Under ground truth the reference's quads_by_kf holds the keyframe mates with at least one veridical quad
+ * (the LISTED rows, row_listed), and get_Quad_for_Pose_Solution skips the rows whose keyframe mate is not a true positive
+ * (kf_is_tp, :78).  The selected quads are all quads of the rows that are listed and TP; the rank order is (row length, KF
+ * index, candidate index) restricted to them, top_n = (size_t)(top_rank_fraction * n_selected), and n_selected is the
+ * denominator of the inlier ratio.  The selected rows are compacted on the device and the search of ebvo_pose_from_quads
+ * runs on the compacted arrays.
+ * Status 1 (identity pose, no search kernel launched, no random number drawn): fewer than 2 listed rows (the reference's own
+ * quads_by_kf.size() < 2, :177), fewer than 2 selected quads, or top_n < 2.
+ * row_listed / kf_is_tp: n_kf bytes each, NULL = all set.  res->n_quads is the selected count; best_q1 / best_q2 are positions
+ * in the selected rank order.  inlier (n bytes) and quad_geom (n x 12) are in the full CSR order, zero on quads not selected;
+ * rank_order (n) holds full-CSR indices in rank order, -1 beyond n_selected.  quad_geom and rank_order are left untouched
+ * when status = 1.  With both masks NULL every output equals ebvo_pose_from_quads bit for bit.  Slot 0's stream, as there. */
+int ebvo_pose_from_quads_gt(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *kf_right, int n_kf, const int32_t *row_ptr,
+                            const ebvo_edge *cf_left, const ebvo_edge *cf_right, const uint8_t *row_listed, const uint8_t *kf_is_tp,
+                            const ebvo_stereo_calib *cal, const ebvo_pose_params *p, ebvo_pose_result *res, uint8_t *inlier,
+                            double *quad_geom, int32_t *rank_order);
+/* The same on a slot armed by ebvo_temporal_set_gt after a match with stages = 1: the slot's final quads, its device row_on
+ * (a veridical quad and kf_is_tp) and its count of listed rows.  EBVO_ERR_STATE when the slot is not armed, has no final
+ * quads, has anything in flight, or the keyframe was replaced.  inlier (may be NULL): n_final bytes.  The slot's results, its
+ * armed state and ebvo_temporal_gt_metrics are unchanged. */
+int ebvo_temporal_estimate_pose_gt(ebvo_ctx *ctx, int slot, const ebvo_stereo_calib *cal, const ebvo_pose_params *p,
+                                   ebvo_pose_result *res, uint8_t *inlier);
+
+/* Solution_Constraints_Application (:255-381): recall and precision of the four quad-pair constraints over sampled pairs of
+ * the selected quads.  Per run exactly max_iterations index pairs are drawn with the loop's
+ * do { rand() % top_n; rand() % top_n } while (equal) -- no termination test, no iteration adjustment -- from the context's
+ * generator under the rand_seed / continue_stream rules of the search; run k + 1 continues where run k stopped.
+ * "Baseline": veridical = the pairs with both quads veridical, precision = veridical / max_iterations, recall = 1.0.  The
+ * Length, T1, T2 and Tangent constraints are applied progressively to the survivors of the stage before:
+ * recall = veridical / Baseline's veridical (0 / 0 is the NaN it is), precision = surviving == 0 ? 0 : veridical / surviving.
+ * The doubles are formed on the host from the device's integer counts.  A pair of zero length fails the Length constraint.
+ * Insufficient quads (the three rules above): every run has status 1, zero counts and doubles, draws = 0; draw_idx and
+ * draw_stage are left untouched. */
+enum
+{
+    EBVO_PC_BASELINE = 0, /* "Baseline" */
+    EBVO_PC_LENGTH,       /* "Normalized Length Constraint" */
+    EBVO_PC_T1,           /* "T1 Angle Similarity Constraint" */
+    EBVO_PC_T2,           /* "T2 Angle Similarity Constraint" */
+    EBVO_PC_TANGENT,      /* "Tangent Angle Similarity Constraint" */
+    EBVO_PC_NUM_STAGES
+};
+typedef struct ebvo_pose_cascade_stage
+{
+    int32_t stage, reserved;
+    int64_t surviving, veridical; /* pairs that passed every constraint up to this stage; ... with both quads veridical */
+    double recall, precision;
+} ebvo_pose_cascade_stage;
+typedef struct ebvo_pose_cascade_run
+{
+    int32_t status, reserved; /* 0 ok / 1 insufficient quads */
+    int64_t n_quads, top_n, draws;
+    ebvo_pose_cascade_stage stages[EBVO_PC_NUM_STAGES];
+} ebvo_pose_cascade_run;
+/* On host arrays (as ebvo_pose_from_quads_gt).  quad_is_tp: per quad in CSR order (Quad_for_Pose_Solution::b_is_veridical),
+ * NULL = none veridical.  runs[n_runs]: one record per run.  draw_idx (may be NULL): n_runs x max_iterations x 2 positions in
+ * the selected rank order; draw_stage (may be NULL): n_runs x max_iterations bytes, bits 0-2 the number of constraints the
+ * pair passed (0-4), bit 7 set when both quads are veridical.  The ranges of ebvo_pose_params apply, n_runs >= 1 and
+ * n_runs x max_iterations <= 1 << 24 (else EBVO_ERR_ARG, nothing touched). */
+int ebvo_pose_constraint_metrics(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *kf_right, int n_kf, const int32_t *row_ptr,
+                                 const ebvo_edge *cf_left, const ebvo_edge *cf_right, const uint8_t *row_listed,
+                                 const uint8_t *kf_is_tp, const uint8_t *quad_is_tp, const ebvo_stereo_calib *cal,
+                                 const ebvo_pose_params *p, int n_runs, ebvo_pose_cascade_run *runs, int32_t *draw_idx,
+                                 uint8_t *draw_stage);
+/* The resident twin on an armed slot (as ebvo_temporal_estimate_pose_gt): b_is_veridical is the slot's EBVO_TGT_CLUSTER flag
+ * (what ebvo_temporal_gt_flags returns). */
+int ebvo_temporal_pose_constraint_metrics(ebvo_ctx *ctx, int slot, const ebvo_stereo_calib *cal, const ebvo_pose_params *p,
+                                          int n_runs, ebvo_pose_cascade_run *runs, int32_t *draw_idx, uint8_t *draw_stage);
 
 /* ---- ground-truth evaluation from a disparity map (the reference's has_gt() == true branch, is_left = true) ------- */
 /* Find_Stereo_GT_Locations (src/Stereo_Matches.cpp:133-200), get_Stereo_Edge_GT_Pairs (:202-268) and
