@@ -37,6 +37,7 @@ struct CandParams
     int64_t cap;        // capacity of col_idx (FILL)
     int32_t *stage;     // [nL][STAGE] first STAGE candidates of every left edge, written by the counting pass
     int32_t *tile_flag; // [tiles] 1: some row of the tile has more than STAGE candidates -> the fill pass redoes the tile
+    int32_t *tile_tot;  // [tiles] candidates of the tile's rows (int32, wraps like the row offsets), written by the counting pass
 };
 
 // Can any point of the box satisfy the enabled epipolar / disparity predicates?  Conservative.

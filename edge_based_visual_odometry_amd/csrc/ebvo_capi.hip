@@ -170,7 +170,7 @@ static void slot_destroy(Slot *s)
         (void)hipFree(ws.cand_lists);
         (void)hipFree(ws.cand_lcount);
     }
-    GrowBuf *bufs[] = {&s->lines,        &s->boxes_chunk,  &s->boxes_group,    &s->cand_cnt,       &s->cand_stage, &s->cand_tileflag, &s->row_ptr, &s->grad_x, &s->grad_y, &s->gn_xy, &s->gn_out, &s->gn_valid, &s->gn_iters, &s->gn_state, &s->gn_lists, &s->gn_pack, &s->sift_used, &s->sift_img, &s->sift_desc, &s->sift_f32, &s->sift_dist, &s->tq_i32, &s->tq_cols, &s->tq_f64, &s->tq_u8, &s->tq_cells, &s->tq_chain, &s->fin_i32, &s->fin_edges, &s->fin_f64, &s->fin_u8, &s->fin_out,
+    GrowBuf *bufs[] = {&s->lines,        &s->boxes_chunk,  &s->boxes_group,    &s->cand_cnt,       &s->cand_stage, &s->cand_tileflag, &s->cand_tiletot, &s->row_ptr, &s->grad_x, &s->grad_y, &s->gn_xy, &s->gn_out, &s->gn_valid, &s->gn_iters, &s->gn_state, &s->gn_lists, &s->gn_pack, &s->sift_used, &s->sift_img, &s->sift_desc, &s->sift_f32, &s->sift_dist, &s->tq_i32, &s->tq_cols, &s->tq_f64, &s->tq_u8, &s->tq_cells, &s->tq_chain, &s->fin_i32, &s->fin_edges, &s->fin_f64, &s->fin_u8, &s->fin_out,
                        &s->scan_tmp,     &s->col_idx,      &s->rc_edges,       &s->sims,           &s->best,
                        &s->keep,         &s->patches_raw,  &s->patches_norm,   &s->patches_flag,   &s->patches_norm_r,
                        &s->patches_flag_r, &s->pair_left,  &s->sincos,         &s->scratch_b,      &s->scratch_c,
@@ -1449,7 +1449,8 @@ static int ensure_pipeline_buffers(ebvo_ctx *ctx, Slot &s, int64_t cap_pairs)
     return EBVO_OK;
 }
 
-// lines -> candidates (count, scan, fill) -> right patch bank -> LDS-tiled NCC -> result record; no host synchronisation
+// lines -> candidates<count> -> [row offsets + staged rows || right patch bank] -> long-row redo -> LDS-tiled NCC -> result
+// record; no host synchronisation
 static int enqueue_matching(ebvo_ctx *ctx, Slot &s, int toed_mode = -1)
 {
     const ebvo_stereo_params &p = s.params;
@@ -1470,9 +1471,9 @@ static int enqueue_matching(ebvo_ctx *ctx, Slot &s, int toed_mode = -1)
                                        (const double *)s.lines.p, p.epi_thr, p.max_disp, p.orient_thr_deg, p.stage_mask,
                                        true, prep)))
         return rc;
-    if (stop && stop <= 11)
+    if (stop == 9)
         return EBVO_OK;
-    if ((rc = match_ncc_resident_enqueue(ctx, s, h, w, ce, p.ncc_thr, 0, !(p.reserved & EBVO_PAIR_NO_SIMS), prep)))
+    if ((rc = match_ncc_resident_enqueue(ctx, s, h, w, ce, p.ncc_thr, 0, !(p.reserved & EBVO_PAIR_NO_SIMS), prep, &p)))
         return rc;
     if (stop)
         return EBVO_OK;
@@ -1675,7 +1676,7 @@ static void pair_graph_drop(Slot &s)
     s.pair_graph = nullptr;
 }
 
-// The chain of one pair is 18 launches whose arguments depend only on PairGraphKey and on the slot's buffers (the sizes
+// The chain of one pair is 16 launches whose arguments depend only on PairGraphKey and on the slot's buffers (the sizes
 // of everything live on the device): the second submission with an unchanged key captures it, later ones launch the graph
 // (measured, tools/ubench/graph_launch.hip: 7-20 us of host time for a 30-kernel chain against 86 us of direct launches,
 // and ~2 us instead of ~2.9 us between dependent kernels on the device).  Anything unusual -- profiling markers, a key

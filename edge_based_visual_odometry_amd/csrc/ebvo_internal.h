@@ -223,7 +223,7 @@ struct Slot
     int32_t *d_fin_tot = nullptr, *h_fin_tot = nullptr; // [8] device / page-locked: n_sift, n_ncc, n_bnb, n_clusters, n_ncc2, n_final
     hipEvent_t ev_fin = nullptr;
     bool fin_in_flight = false;
-    GrowBuf lines, boxes_chunk, boxes_group, cand_cnt, cand_stage, cand_tileflag, row_ptr, scan_tmp, col_idx, rc_edges, sims, best, keep,
+    GrowBuf lines, boxes_chunk, boxes_group, cand_cnt, cand_stage, cand_tileflag, cand_tiletot, row_ptr, scan_tmp, col_idx, rc_edges, sims, best, keep,
         patches_raw, patches_norm, patches_flag, patches_norm_r, patches_flag_r, pair_left, sincos, scratch_b, scratch_c,
         scratch_d;
     int64_t cap_pairs = 0;               // capacity of col_idx & co. as the kernels of the current call see it
@@ -342,12 +342,12 @@ struct ebvo_ctx
     int64_t graph_launches = 0; // pairs submitted as a graph launch
     int exact_blocks[2] = {0, 0}; // developer keys (ebvo_debug_set 11, 12): grid of the exact centre / mags kernel in blocks (0 = what the device keeps resident)
     int cand_blocks = 0;        // developer key (ebvo_debug_set 19): most blocks of candidates<count> (0 = 1024; at most EBVO_TOTAL_PARTS)
-    int small_div = 0;          // developer key (ebvo_debug_set 18): the grids of the latency-bound decide / cand_scatter / candidates<fill> are
-                                // 512 / 512 / 4096 blocks divided by this (0 = 4: +1.0 % pairs/s against 1, +0.7 % for 2, two runs; 8: -0.3 %)
+    int small_div = 0;          // developer key (ebvo_debug_set 18): the grids of the latency-bound decide / cand_scatter / candidates<fill> and the
+                                // rows range of bank_rows_kernel are 512 / 512 / 4096 / 512 blocks divided by this (0 = 4: +1.0 % pairs/s against 1, +0.7 % for 2, two runs; 8: -0.3 %)
     int ncc_blocks = 0;         // developer key (ebvo_debug_set 17): grid of ncc_tile_kernel in blocks (0 = what the device keeps resident)
     int stop_stage = 0;         // developer key (ebvo_debug_set 16): the resident pair's chain ends after stage N (tools/gpu_prefix_chain.py:
                                 // the pair rate of every prefix of the chain = what each stage costs in the steady state); 0 = whole chain
-    int repeat_mask = 0;        // developer key (ebvo_debug_set 15): bit 0 centre, 1 mags, 2 right bank, 3 NCC tile launched TWICE (idempotent kernels: what
+    int repeat_mask = 0;        // developer key (ebvo_debug_set 15): bit 0 centre, 1 mags, 2 right bank (+ candidate rows), 3 NCC tile launched TWICE (idempotent kernels: what
                                 // one more launch of each costs the pair rate, tools/gpu_marginal_cost.py)
     int no_prep = 0;            // developer key (ebvo_debug_set 14): 1 = lines, boxes, sincos and row pairs as four launches (A/B)
     int ingest_stream = 0;      // developer key (ebvo_debug_set 13): 1 = ebvo_stereo_upload_async copies on the upload stream (A/B)
@@ -459,11 +459,11 @@ int match_lines_enqueue(ebvo_ctx *ctx, Slot &s, const double *d_F, const ebvo_ed
 // s.d_total receives the 64-bit number of pairs found
 int match_candidates_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_L, int nL, const int32_t *d_nL,
                              const ebvo_edge *d_R, int nR, const int32_t *d_nR, int cap_edges, const double *d_lines,
-                             double epi_thr, double max_disp, double orient_thr_deg, int stage_mask, bool fill, bool prep_done = false);
+                             double epi_thr, double max_disp, double orient_thr_deg, int stage_mask, bool resident, bool prep_done = false);
 int match_candidates_fill_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_L, int nL, const int32_t *d_nL,
                                   const ebvo_edge *d_R, int nR, const int32_t *d_nR, int cap_edges,
                                   const double *d_lines, double epi_thr, double max_disp, double orient_thr_deg,
-                                  int stage_mask);
+                                  int stage_mask, bool redo_only = false /* the staged rows are already in col_idx */);
 int match_patches_enqueue(ebvo_ctx *ctx, Slot &s, const uint8_t *d_img, int h, int w, int pitch,
                           const ebvo_edge *d_edges, int n, const int32_t *d_n, int cap_n, float *d_raw, float *d_norm,
                           uint8_t *d_flag);
@@ -475,8 +475,10 @@ int match_ncc_pairs_enqueue(ebvo_ctx *ctx, Slot &s, const uint8_t *d_imgR, int h
                             const int32_t *d_n_pairs = nullptr /* the count on the device; n_pairs is then its bound */);
 // resident pipeline: sin/cos, right patch bank, LDS-tiled NCC of every CSR pair (sizes read on the device)
 // left = index of the slot's image workspace that holds the LEFT image and edges (the right one is the other)
+// cand: the resident pair's chain, behind match_candidates_enqueue(resident = true) -- the row offsets and the staged rows of
+// its candidates are produced in the right bank's launch, the long-row redo follows, then the NCC
 int match_ncc_resident_enqueue(ebvo_ctx *ctx, Slot &s, int h, int w, int cap_edges, double thr, int left = 0, bool want_sims = true,
-                               bool prep_done = false);
+                               bool prep_done = false, const ebvo_stereo_params *cand = nullptr);
 // epipolar lines, right-edge boxes (+ tile flags), sin / cos of both edge lists and both row-pair images of a resident pair in
 // ONE launch; pass prep_done = true to the two calls above / below afterwards
 int match_prep_enqueue(ebvo_ctx *ctx, Slot &s, int h, int w, int cap_edges);

@@ -125,9 +125,12 @@ __device__ inline Box region_box(const LeftCtx &l, double D, double band, int ma
 //      chunks in ascending order, ONE pair test per lane per chunk; a ballot gives the 16-bit hit mask, hence every
 //      hit's rank in the row.  ~2 M threads instead of one per left edge: the walk used to be a serial chain of
 //      ~120 dependent LDS reads + tests per lane with two waves per SIMD to hide it behind.
-// The counting pass also keeps the first STAGE candidates of every row; after the scan of the counts a copy kernel
-// completes every row that fits, and the FILL pass only redoes tiles that hold a longer row.
-template <bool FILL>
+// The counting pass also keeps the first STAGE candidates of every row and the total of every tile; once the row offsets
+// are known every row that fits is completed from the staging area, and the FILL pass only redoes tiles that hold a longer
+// row.  COPY: the fill pass copies the staged rows itself, as its prologue (host-buffer path, behind the two scan kernels);
+// the resident pair's chain has the offsets and the copy in the right bank's launch (cand_rows_body) and runs the fill pass
+// without the prologue, as the long-row redo only.
+template <bool FILL, bool COPY = FILL>
 __global__ __launch_bounds__(256) void candidates_kernel(const ebvo_edge *__restrict__ L,
                                                          const ebvo_edge *__restrict__ R,
                                                          const double *__restrict__ lines,
@@ -180,7 +183,7 @@ __global__ __launch_bounds__(256) void candidates_kernel(const ebvo_edge *__rest
 
     if (!FILL && blockIdx.x == 0 && tid == 0)
         cnt[nL] = 0; // the scan covers nL + 1 counts: row_ptr[nL] = total
-    if (FILL)
+    if (FILL && COPY)
     {
         // rows with at most STAGE candidates are completed from the staging area (round 4: here, as the prologue of the fill
         // pass, instead of in a launch of their own; the tiles below only redo rows that are longer -- disjoint writes)
@@ -339,7 +342,11 @@ __global__ __launch_bounds__(256) void candidates_kernel(const ebvo_edge *__rest
                 s_tot[wid] = tsum;
             __syncthreads();
             if (tid == 0)
-                blk_total += s_tot[0] + s_tot[1] + s_tot[2] + s_tot[3];
+            {
+                const unsigned long long t = s_tot[0] + s_tot[1] + s_tot[2] + s_tot[3];
+                blk_total += t;
+                P.tile_tot[tile] = (int32_t)(uint32_t)t; // the low word: what the int32 sum of the tile's counts gives
+            }
         }
         __syncthreads();
     }
@@ -1103,15 +1110,12 @@ constexpr int BANK_EDGE = 112;  // floats per edge (448 B)
 constexpr int NCC_NW = 4;       // left edges per wave (one sampling round: four 16-lane groups)
 constexpr int NCC_WPE = 4;      // waves per SIMD the tile kernel is compiled for (the prefetched loads need the registers)
 
-__global__ __launch_bounds__(256) void right_bank_kernel(const uint8_t *__restrict__ img,
-                                                         const uint16_t *__restrict__ pix2, int h, int w, int pitch,
-                                                         const ebvo_edge *__restrict__ edges,
-                                                         const double2 *__restrict__ sc, DevN nd,
-                                                         float *__restrict__ bank)
+__device__ inline void right_bank_body(const uint8_t *__restrict__ img, const uint16_t *__restrict__ pix2, int h, int w, int pitch,
+                                       const ebvo_edge *__restrict__ edges, const double2 *__restrict__ sc, int n,
+                                       float *__restrict__ bank, int vb, int vg)
 {
-    const int n = devn(nd);
-    const int groups = (gridDim.x * blockDim.x) >> 4;
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int groups = (vg * blockDim.x) >> 4;
+    const int t = vb * blockDim.x + threadIdx.x;
     const int g = t & 15, side = g >> 3, row = g & 7;
     const int iters = (n + groups - 1) / groups;
     for (int it = 0; it < iters; ++it)
@@ -1134,6 +1138,128 @@ __global__ __launch_bounds__(256) void right_bank_kernel(const uint8_t *__restri
             dst[1] = make_float4(nr[4], nr[5], nr[6], sent ? 1.0f : 0.0f);
         }
     }
+}
+
+__global__ __launch_bounds__(256) void right_bank_kernel(const uint8_t *__restrict__ img,
+                                                         const uint16_t *__restrict__ pix2, int h, int w, int pitch,
+                                                         const ebvo_edge *__restrict__ edges,
+                                                         const double2 *__restrict__ sc, DevN nd,
+                                                         float *__restrict__ bank)
+{
+    right_bank_body(img, pix2, h, w, pitch, edges, sc, devn(nd), bank, blockIdx.x, gridDim.x);
+}
+
+// Row offsets of the candidate CSR and the copy of the staged rows, for the resident pair: what scan_reduce_kernel +
+// scan_apply_kernel and the prologue of candidates_kernel<true> do in three dependent launches in front of the right bank,
+// as a block range of the bank's own launch (the bank samples the right edges and reads nothing of the candidates).
+// A WAVE owns a tile of the counting pass (TILE = 64 rows, one per lane) and walks the tiles grid-stride:
+//   * the offset in front of the tile is the sum of the counting pass's per-tile totals before it -- in full for the
+//     wave's first tile, then only the totals it has not yet added.  No atomics, no look-back, nothing waits for another
+//     wave; no LDS, so the range takes no wave slot from the bank blocks;
+//   * an exclusive scan of the tile's 64 counts gives row_ptr.  uint32 arithmetic: sums modulo 2^32 do not depend on their
+//     order, so these are the scan kernels' int32 values bit for bit, also where the total wraps (the 64-bit total and
+//     the overflow flag of pair_result_kernel guard that case as before);
+//   * every lane copies its own row from the staging area (rows beyond STAGE are left to the redo pass): 16-byte loads
+//     of the 256-byte staged row, sixteen entries in flight before the first store.
+__device__ inline void cand_rows_body(const int32_t *__restrict__ cnt, const int32_t *__restrict__ tile_tot,
+                                      const int32_t *__restrict__ stage, int nL, int64_t cap, int32_t *__restrict__ row_ptr,
+                                      int32_t *__restrict__ col_idx, int vb, int vg)
+{
+    static_assert(TILE == 64, "one lane per row of a tile");
+    const int lane = threadIdx.x & 63;
+    const int vw = vb * 4 + (threadIdx.x >> 6), nw = vg * 4; // 256 threads: four waves per block
+    if (nL <= 0)
+    {
+        if (vw == 0 && lane == 0)
+            row_ptr[0] = 0;
+        return;
+    }
+    const int ntiles = (nL + TILE - 1) / TILE;
+    uint32_t off = 0; // sum of tile_tot[0 .. done)
+    int done = 0;
+    for (int tile = vw; tile < ntiles; tile += nw)
+    {
+        uint32_t part = 0;
+        for (int k = done + lane; k < tile; k += 64)
+            part += (uint32_t)tile_tot[k];
+        for (int d = 32; d > 0; d >>= 1)
+            part += __shfl_xor(part, d);
+        off += part;
+        done = tile;
+        const int i = tile * TILE + lane;
+        const bool live = i < nL;
+        const int n = live ? cnt[i] : 0;
+        uint32_t incl = (uint32_t)n;
+        for (int d = 1; d < 64; d <<= 1)
+        {
+            const uint32_t t = __shfl_up(incl, d);
+            if (lane >= d)
+                incl += t;
+        }
+        const int32_t o32 = (int32_t)(off + incl - (uint32_t)n);
+        if (live)
+        {
+            row_ptr[i] = o32;
+            if (i == nL - 1)
+                row_ptr[nL] = (int32_t)(off + incl);
+        }
+        const int64_t o = o32;
+        const int nc = (live && n <= STAGE) ? n : 0;
+        const int4 *__restrict__ src = reinterpret_cast<const int4 *>(stage + (size_t)i * STAGE); // read below nc only
+        for (int k0 = 0; __any(k0 < nc); k0 += 16)
+        {
+            int4 v[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+            {
+                v[t] = make_int4(0, 0, 0, 0);
+                if (k0 + 4 * t < nc)
+                    v[t] = src[(k0 >> 2) + t];
+            }
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+            {
+                const int x[4] = {v[t].x, v[t].y, v[t].z, v[t].w};
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                {
+                    const int k = k0 + 4 * t + c;
+                    // o + k < cap as in the fill pass's prologue; unsigned, so an offset that wrapped below zero stores nothing
+                    if (k < nc && (uint64_t)(o + k) < (uint64_t)cap)
+                        col_idx[o + k] = x[c];
+                }
+            }
+        }
+    }
+}
+
+// The right bank and, in front of it so that they are dispatched first, the rows range of the candidate search: independent
+// jobs as block ranges of one launch, as in match_prep_kernel.
+struct BankRowsArgs
+{
+    const uint8_t *img;
+    const uint16_t *pix2;
+    int h, w, pitch;
+    const ebvo_edge *edges;
+    const double2 *sc;
+    DevN nR;
+    float *bank;
+    const int32_t *cnt, *tile_tot, *stage;
+    DevN nL;
+    int64_t cap;
+    int32_t *row_ptr, *col_idx;
+    int b_rows; // blocks of the rows range; the rest of the grid is the bank's
+};
+
+__global__ __launch_bounds__(256, 5) void bank_rows_kernel(BankRowsArgs A) // five waves per SIMD, as right_bank_kernel gets alone
+{
+    const int b = blockIdx.x;
+    if (b < A.b_rows)
+    {
+        cand_rows_body(A.cnt, A.tile_tot, A.stage, devn(A.nL), A.cap, A.row_ptr, A.col_idx, b, A.b_rows);
+        return;
+    }
+    right_bank_body(A.img, A.pix2, A.h, A.w, A.pitch, A.edges, A.sc, devn(A.nR), A.bank, b - A.b_rows, (int)gridDim.x - A.b_rows);
 }
 
 // wave-synchronous exchange through LDS: the writes of this wave are complete and visible to its other lanes
@@ -1850,20 +1976,28 @@ static CandParams cand_params(Slot &s, int nL, const int32_t *d_nL, int nR, cons
     P.cap = cap;
     P.stage = (int32_t *)s.cand_stage.p;
     P.tile_flag = (int32_t *)s.cand_tileflag.p;
+    P.tile_tot = (int32_t *)s.cand_tiletot.p;
     return P;
 }
 
 int match_candidates_fill_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_L, int nL, const int32_t *d_nL,
                                   const ebvo_edge *d_R, int nR, const int32_t *d_nR, int cap_edges,
                                   const double *d_lines, double epi_thr, double max_disp, double orient_thr_deg,
-                                  int stage_mask)
+                                  int stage_mask, bool redo_only)
 {
     const CandParams P = cand_params(s, nL, d_nL, nR, d_nR, epi_thr, max_disp, orient_thr_deg, stage_mask, s.cap_pairs);
     ProfScope ps(ctx, s, K_CAND_FILL);
-    hipLaunchKernelGGL(candidates_kernel<true>, dim3(blocks_for(d_nL ? cap_edges : nL, TILE, 4096 / (ctx->small_div > 0 ? ctx->small_div : 4))), dim3(256), 0,
-                       s.stream, d_L, d_R, d_lines, (const Box *)s.boxes_chunk.p, (const Box *)s.boxes_group.p, P,
-                       (int32_t *)nullptr, (const int32_t *)s.row_ptr.p, (int32_t *)s.col_idx.p,
-                       (unsigned long long *)nullptr);
+    const dim3 grid(blocks_for(d_nL ? cap_edges : nL, TILE, 4096 / (ctx->small_div > 0 ? ctx->small_div : 4)));
+    // redo_only: the staged rows were copied beside the right bank (bank_rows_kernel); at KITTI size no tile is flagged and
+    // every block leaves after reading its tile flags
+    if (redo_only)
+        hipLaunchKernelGGL((candidates_kernel<true, false>), grid, dim3(256), 0, s.stream, d_L, d_R, d_lines,
+                           (const Box *)s.boxes_chunk.p, (const Box *)s.boxes_group.p, P, (int32_t *)nullptr,
+                           (const int32_t *)s.row_ptr.p, (int32_t *)s.col_idx.p, (unsigned long long *)nullptr);
+    else
+        hipLaunchKernelGGL((candidates_kernel<true, true>), grid, dim3(256), 0, s.stream, d_L, d_R, d_lines,
+                           (const Box *)s.boxes_chunk.p, (const Box *)s.boxes_group.p, P, (int32_t *)nullptr,
+                           (const int32_t *)s.row_ptr.p, (int32_t *)s.col_idx.p, (unsigned long long *)nullptr);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
 }
@@ -1885,6 +2019,8 @@ static int candidates_buffers(ebvo_ctx *ctx, Slot &s, int capL, int capR, size_t
     if ((rc = ebvo_grow(ctx, s, s.cand_stage, sizeof(int32_t) * STAGE * ((size_t)capL + 1))))
         return rc;
     if ((rc = ebvo_grow(ctx, s, s.cand_tileflag, sizeof(int32_t) * ntiles)))
+        return rc;
+    if ((rc = ebvo_grow(ctx, s, s.cand_tiletot, sizeof(int32_t) * ntiles)))
         return rc;
     *ntiles_out = ntiles;
     *capgroups_out = capgroups;
@@ -1932,7 +2068,7 @@ int match_prep_enqueue(ebvo_ctx *ctx, Slot &s, int h, int w, int cap_edges)
 
 int match_candidates_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_L, int nL, const int32_t *d_nL,
                              const ebvo_edge *d_R, int nR, const int32_t *d_nR, int cap_edges, const double *d_lines,
-                             double epi_thr, double max_disp, double orient_thr_deg, int stage_mask, bool fill, bool prep_done)
+                             double epi_thr, double max_disp, double orient_thr_deg, int stage_mask, bool resident, bool prep_done)
 {
     const int capL = d_nL ? cap_edges : nL, capR = d_nR ? cap_edges : nR;
     int rc;
@@ -1961,23 +2097,20 @@ int match_candidates_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_L, int n
         hipLaunchKernelGGL(candidates_kernel<false>, dim3(nblk), dim3(256), 0, s.stream, d_L, d_R, d_lines,
                            (const Box *)s.boxes_chunk.p, (const Box *)s.boxes_group.p, P, cnt, (const int32_t *)nullptr,
                            (int32_t *)nullptr, s.d_total + 1);
-        if (!fill) // host-buffer path reads the total back; the pipeline sums the parts in pair_result_kernel
+        if (!resident) // host-buffer path reads the total back; the pipeline sums the parts in pair_result_kernel
             hipLaunchKernelGGL(total_sum_kernel, dim3(1), dim3(64), 0, s.stream,
                                (const unsigned long long *)(s.d_total + 1), nblk, s.d_total);
     }
-    if (ctx->stop_stage == 9)
-        return EBVO_OK;
+    // the resident pair's chain goes on in match_ncc_resident_enqueue: the row offsets and the copy of the staged rows run
+    // beside the right bank (bank_rows_kernel), the long-row redo behind them; the host-buffer callers scan here and
+    // enqueue the fill pass themselves once they have read the total
+    if (!resident)
     {
         ProfScope ps(ctx, s, K_SCAN);
         if ((rc = device_exclusive_scan(ctx, s, cnt, (int32_t *)s.row_ptr.p, DevN{nL, d_nL}, 1, capL + 1)))
             return rc;
     }
     EBVO_HIP(ctx, hipGetLastError());
-    if (ctx->stop_stage == 10)
-        return EBVO_OK;
-    if (fill)
-        return match_candidates_fill_enqueue(ctx, s, d_L, nL, d_nL, d_R, nR, d_nR, cap_edges, d_lines, epi_thr, max_disp,
-                                             orient_thr_deg, stage_mask);
     return EBVO_OK;
 }
 
@@ -2042,8 +2175,35 @@ int match_ncc_pairs_enqueue(ebvo_ctx *ctx, Slot &s, const uint8_t *d_imgR, int h
 
 // NCC of the CSR pairs in s.row_ptr / s.col_idx of the resident pair: sin/cos of both edge lists, the right bank, the
 // tile kernel.  s.patches_norm_r holds the right bank (BANK_EDGE floats per edge).
+// the right bank of workspace iR, alone or -- rows given, its candidate fields filled in -- behind the rows range of the
+// candidate search in the same launch
+static void right_bank_launch(Slot &s, int iR, const double2 *scR, DevN nRd, int h, int w, int cap_edges, const BankRowsArgs *rows)
+{
+    const unsigned b_bank = blocks_for((int64_t)cap_edges * 16, 256, 1024);
+    const uint8_t *img = ncc_img(s, iR);
+    const uint16_t *pix2 = (const uint16_t *)s.im[iR].pix2;
+    const ebvo_edge *edges = (const ebvo_edge *)s.im[iR].edges;
+    float *bank = (float *)s.patches_norm_r.p;
+    if (!rows)
+    {
+        hipLaunchKernelGGL(right_bank_kernel, dim3(b_bank), dim3(256), 0, s.stream, img, pix2, h, w, w, edges, scR, nRd, bank);
+        return;
+    }
+    BankRowsArgs A = *rows;
+    A.img = img;
+    A.pix2 = pix2;
+    A.h = h;
+    A.w = w;
+    A.pitch = w;
+    A.edges = edges;
+    A.sc = scR;
+    A.nR = nRd;
+    A.bank = bank;
+    hipLaunchKernelGGL(bank_rows_kernel, dim3(A.b_rows + b_bank), dim3(256), 0, s.stream, A);
+}
+
 int match_ncc_resident_enqueue(ebvo_ctx *ctx, Slot &s, int h, int w, int cap_edges, double thr, int left, bool want_sims,
-                               bool prep_done)
+                               bool prep_done, const ebvo_stereo_params *cand)
 {
     int rc;
     if ((rc = ebvo_grow(ctx, s, s.sincos, sizeof(double2) * 2 * (size_t)cap_edges)))
@@ -2066,12 +2226,33 @@ int match_ncc_resident_enqueue(ebvo_ctx *ctx, Slot &s, int h, int w, int cap_edg
                                ncc_img(s, 0), ncc_img(s, 1), s.im[0].pix2, s.im[1].pix2, h, w);
             hipLaunchKernelGGL(sincos_batch_kernel, dim3(blocks_for(cap_edges, 256, 512), 2), dim3(256), 0, s.stream, B);
         }
+        BankRowsArgs rows{};
+        if (cand)
+        {
+            // the candidates of the resident pair (match_candidates_enqueue has run the counting pass): row offsets and staged
+            // rows as the first blocks of the bank's launch.  128 blocks = 512 waves, four tiles each at KITTI size; key 18
+            // divides the range like the other latency-bound grids (512: ONE block walks every tile)
+            rows.cnt = (const int32_t *)s.cand_cnt.p;
+            rows.tile_tot = (const int32_t *)s.cand_tiletot.p;
+            rows.stage = (const int32_t *)s.cand_stage.p;
+            rows.nL = nLd;
+            rows.cap = s.cap_pairs;
+            rows.row_ptr = (int32_t *)s.row_ptr.p;
+            rows.col_idx = (int32_t *)s.col_idx.p;
+            rows.b_rows = (int)blocks_for(((int64_t)cap_edges + TILE - 1) / TILE, 4, 512 / (ctx->small_div > 0 ? ctx->small_div : 4));
+        }
         for (int rep = 0; rep < ((ctx->repeat_mask & 4) ? 2 : 1); ++rep)
-            hipLaunchKernelGGL(right_bank_kernel, dim3(blocks_for((int64_t)cap_edges * 16, 256, 1024)), dim3(256), 0, s.stream,
-                               ncc_img(s, iR), (const uint16_t *)s.im[iR].pix2, h, w, w, (const ebvo_edge *)s.im[iR].edges,
-                               (const double2 *)B.sc[iR], nRd, (float *)s.patches_norm_r.p);
+            right_bank_launch(s, iR, (const double2 *)B.sc[iR], nRd, h, w, cap_edges, cand ? &rows : nullptr);
     }
-    if (ctx->stop_stage == 12)
+    EBVO_HIP(ctx, hipGetLastError());
+    if (ctx->stop_stage == 10)
+        return EBVO_OK;
+    if (cand && (rc = match_candidates_fill_enqueue(ctx, s, (const ebvo_edge *)s.im[iL].edges, 0, nLd.dev,
+                                                    (const ebvo_edge *)s.im[iR].edges, 0, nRd.dev, cap_edges,
+                                                    (const double *)s.lines.p, cand->epi_thr, cand->max_disp,
+                                                    cand->orient_thr_deg, cand->stage_mask, true)))
+        return rc;
+    if (ctx->stop_stage == 11)
         return EBVO_OK;
     {
         ProfScope ps(ctx, s, K_NCC_PAIRS);

@@ -1,6 +1,6 @@
 """Run ON the GPU box: what one more launch of a kernel costs the PAIR RATE (six pairs in flight), next to the kernel's
-duration alone.  Key 15 of ebvo_debug_set launches an idempotent kernel of the chain twice (bit 0 centre, 1 mags, 2 right bank,
-3 NCC tile); one context per setting, interleaved and repeated; the counts must not move.
+duration alone.  Key 15 of ebvo_debug_set launches an idempotent kernel of the chain twice (bit 0 centre, 1 mags, 2 right bank
+with the candidate rows range in front of it, 3 NCC tile); one context per setting, interleaved and repeated; the counts must not move.
   marginal us per pair = 1e6 / rate(with the repeat) - 1e6 / rate(default)"""
 import os
 import sys
@@ -14,7 +14,7 @@ H, W = synth.SHAPES["kitti"]
 F = synth.fundamental_for("kitti")
 NS = 6
 left, right = synth.stereo_pair("s2", H, W, scene=7, noise_base=0, disparity=12)
-NAMES = {0: "default", 1: "centre x 2", 2: "mags x 2", 4: "right bank x 2", 8: "NCC tile x 2", 15: "all four x 2"}
+NAMES = {0: "default", 1: "centre x 2", 2: "mags x 2", 4: "rows + right bank x 2", 8: "NCC tile x 2", 15: "all four x 2"}
 settings = [int(a) for a in sys.argv[1:]] or [0, 1, 2, 4, 8, 15]
 
 
