@@ -462,9 +462,12 @@ EBVO_MATH_FN double ebvo_exp(double x)
  * table-driven hal::exp32f and the gradient orientations with hal::fastAtan2, both approximations whose last bits depend
  * on the build (SIMD width, FMA); here both sides (oracle and kernels) call these two routines, float arithmetic with
  * separate multiply and add:
- *   ebvo_expf          exp(x) by Cody-Waite reduction and a degree-6 Taylor polynomial, about 1 ulp;
- *   ebvo_fast_atan2_deg  OpenCV's published fastAtan2 polynomial (degrees in [0, 360), max error ~0.3 degrees),
- *                        modules/core/src/mathfuncs_core.simd.hpp: atan_f32.
+ *   ebvo_expf          exp(x) by Cody-Waite reduction and a degree-6 Taylor polynomial; measured against mpmath on
+ *                        10^5 inputs of [-2, 0] (the descriptor's weights use (-1.5625, 0]): at most 2.73 ulp
+ *                        (tests/test_math.py);
+ *   ebvo_fast_atan2_deg  OpenCV's published fastAtan2 polynomial (degrees, max error ~0.3 degrees),
+ *                        modules/core/src/mathfuncs_core.simd.hpp: atan_f32.  The range is [0, 360]: for a negative y
+ *                        below half an ulp of 360 relative to x, 360.f - a rounds to 360 itself.
  */
 EBVO_MATH_FN float ebvo_expf(float x)
 {

@@ -1397,6 +1397,18 @@ void orc_sincos_v(const double *t, int n, int math_mode, double *s, double *c)
     }
 }
 
+void orc_expf_v(const float *x, int n, float *out)
+{
+    for (int k = 0; k < n; k++)
+        out[k] = ebvo_expf(x[k]);
+}
+
+void orc_fast_atan2_deg_v(const float *y, const float *x, int n, float *out)
+{
+    for (int k = 0; k < n; k++)
+        out[k] = ebvo_fast_atan2_deg(y[k], x[k]);
+}
+
 uint64_t orc_fnv1a64(const uint8_t *b, size_t n)
 {
     uint64_t h = 1469598103934665603ull;

@@ -99,6 +99,9 @@ void orc_ncc_quads(const float *kfL, const float *kfR, const float *cfL, const f
 void orc_atan2_v(const double *y, const double *x, int n, int math_mode, double *out);
 void orc_sincos_v(const double *t, int n, int math_mode, double *s, double *c);
 void orc_exp_v(const double *x, int n, int math_mode, double *out);
+/* the two single-precision routines of the SIFT descriptor (ebvo_expf, ebvo_fast_atan2_deg) */
+void orc_expf_v(const float *x, int n, float *out);
+void orc_fast_atan2_deg_v(const float *y, const float *x, int n, float *out);
 
 /* FNV-1a-64 helpers used by the known-answer tests. */
 uint64_t orc_fnv1a64(const uint8_t *bytes, size_t n);

@@ -259,6 +259,23 @@ def exp_v(x, math_mode):
     return out
 
 
+def expf_v(x):
+    """ebvo_expf (csrc/ebvo_math.h) element-wise on float32"""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    out = np.zeros(len(x), dtype=np.float32)
+    lib().orc_expf_v(_p(x), len(x), _p(out))
+    return out
+
+
+def fast_atan2_deg_v(y, x):
+    """ebvo_fast_atan2_deg (csrc/ebvo_math.h) element-wise on float32"""
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    out = np.zeros(len(y), dtype=np.float32)
+    lib().orc_fast_atan2_deg_v(_p(y), _p(x), len(y), _p(out))
+    return out
+
+
 def undistort(img, K, dist):
     """cv::undistort(img, K, dist) restated (oracle/ebvo_oracle.c: orc_undistort).  K = (fx, fy, cx, cy)."""
     img = np.ascontiguousarray(img, dtype=np.uint8)

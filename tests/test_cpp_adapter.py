@@ -155,3 +155,53 @@ def test_adapter_matches_oracle(tmp_path):
     assert_edges_equal(t_left, q["final"]["left"], "temporal left centres")
     assert_edges_equal(t_right, q["final"]["right"], "temporal right centres")
     assert_bit_equal(t_valid, q["final"]["valid"], "temporal validity")
+
+
+# ---- the input side: ebvo::undistort, ebvo::sift_descriptors, ebvo::sift_min_distances (tests/cpp/input_demo.cpp) ----------------
+INPUT_SRC = os.path.join(ROOT, "tests", "cpp", "input_demo.cpp")
+INPUT_EXE = os.path.join(ROOT, "tests", "cpp", "input_demo")
+
+
+def build_input_demo():
+    libdir = os.path.dirname(_lib.LIB_PATH)
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), INPUT_SRC,
+                           "-o", INPUT_EXE, "-L", libdir, "-lebvo_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
+
+
+def test_input_demo_builds_with_plain_gxx():
+    build_input_demo()
+    assert os.path.exists(INPUT_EXE)
+
+
+@pytest.mark.gpu
+def test_input_adapters_match_oracle(tmp_path):
+    """cv::undistort over the border (undistort_cases: pincushion), descriptors that saturate and vanish (sift_cases: step32)
+    and their distances over a small CSR with empty rows, through the C++ adapters: the raw results against the oracle"""
+    from tests import sift_cases as sc
+    from tests import undistort_cases as uc
+    build_input_demo()
+    (h, w), K, dist = uc.CASES["pincushion"]
+    img = uc.image("pincushion")
+    simg, e = sc.case("step32")
+    n = len(e)
+    lens = np.array([0, 3, 0, 1] + [2] * (n - 6) + [0, 0])        # leading, interior and trailing empty rows
+    row_ptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    cand = ((np.repeat(np.arange(n), lens) * 7 + np.arange(int(lens.sum()))) % n).astype(np.int32)
+    blob = b"".join([np.array([h, w, len(dist)], dtype=np.int32).tobytes(), np.array(K, dtype=np.float64).tobytes(),
+                     np.array(dist, dtype=np.float64).tobytes(), img.tobytes(),
+                     np.array([simg.shape[0], simg.shape[1], n], dtype=np.int32).tobytes(), simg.tobytes(),
+                     np.ascontiguousarray(e, dtype=orc.EDGE_DTYPE).tobytes(), np.array([len(cand)], dtype=np.int32).tobytes(),
+                     row_ptr.tobytes(), cand.tobytes()])
+    (tmp_path / "in.bin").write_bytes(blob)
+    out = tmp_path / "out.bin"
+    subprocess.check_call([INPUT_EXE, str(tmp_path / "in.bin"), str(out)])
+    buf = out.read_bytes()
+    assert len(buf) == h * w + 4 * 256 * n + 8 * len(cand)
+    und = np.frombuffer(buf, dtype=np.uint8, count=h * w).reshape(h, w)
+    desc = np.frombuffer(buf, dtype=np.float32, count=256 * n, offset=h * w).reshape(n, 2, 128)
+    d = np.frombuffer(buf, dtype=np.float64, count=len(cand), offset=h * w + 1024 * n)
+    assert (und == orc.undistort(img, K, dist)).all()
+    ref = sc.oracle_descriptors("step32")
+    assert_bit_equal(desc, ref, "descriptors")
+    assert (desc == 255).any() and (~desc.any(axis=2)).any()
+    assert_bit_equal(d, orc.sift_min_distances(ref, ref[cand], row_ptr), "min distances")

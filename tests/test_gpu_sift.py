@@ -57,3 +57,73 @@ def test_chain_with_sift_equals_oracle_chain(ctx, shape):
     # the SIFT stages change the result: the chain without them keeps more candidates per row
     counts0, _ = ctx.stereo_finalize(calib)
     assert counts0["n_bnb"] > counts["n_bnb"]
+
+
+# ---- the branches the generator's textured images never reach (tests/sift_cases.py; tests/test_sift_cases.py shows on the CPU that
+# every case reaches its branch and that a second reading of the algorithm agrees with the oracle there) ---------------------------
+import functools
+
+from tests import sift_cases as sc
+
+
+@pytest.mark.parametrize("name", sc.NAMES)
+def test_branch_cases_equal_oracle(ctx, name):
+    """saturation at 255, all-zero descriptors (flat image, windows off the image), both sides of the all-inside test, negative
+    first bins and votes in front of the histogram, an image size that is no multiple of 64 or 4"""
+    img, e = sc.case(name)
+    got = ctx.sift_descriptors(img, e)
+    assert_bit_equal(got, sc.oracle_descriptors(name), f"{name} descriptors")
+    if name in ("flat", "offimage"):
+        assert not got.any()
+    if name == "step32":
+        assert (got == 255).sum() == 128 and int((~got.any(axis=2)).sum()) == 16
+
+
+@pytest.mark.parametrize("n", [0, 1, 31, 32, 33])
+def test_keypoint_counts_around_one_wave(ctx, n):
+    """64 keypoints (32 edges) fill exactly one wave"""
+    img, e = sc.case("s2_odd")
+    order, _ = sc.interleaved_order("s2_odd")
+    got = ctx.sift_descriptors(img, e[order[:n]])
+    assert got.shape == (n, 2, 128)
+    assert_bit_equal(got, sc.oracle_descriptors("s2_odd")[order[:n]], f"{n} edges")
+
+
+@pytest.mark.parametrize("name", ["s2_odd", "step32"])
+def test_strided_image(ctx, name):
+    img, e = sc.case(name)
+    h, w = img.shape
+    wide = np.full((h, w + 13), 201, dtype=np.uint8)
+    wide[:, :w] = img
+    assert_bit_equal(ctx.sift_descriptors(wide[:, :w], e), sc.oracle_descriptors(name), "strided image")
+
+
+def test_descriptor_does_not_depend_on_its_neighbours_in_the_wave(ctx):
+    """The same keypoint through the all-inside fast path (a wave of interior keypoints) and through the general path (a wave
+    that holds a keypoint next to the border): TOED lists edges row by row, so most waves of the plain list are all-inside,
+    while the interleaved list puts a border edge into every wave."""
+    img, e = sc.case("s2_odd")
+    order, inside = sc.interleaved_order("s2_odd")
+    runs = np.diff(np.flatnonzero(np.concatenate([[True], ~inside[order], [True]])))
+    assert runs.max() <= 32                    # no 32 consecutive interior edges: no all-inside wave in the permuted list
+    plain = ctx.sift_descriptors(img, e)
+    mixed = ctx.sift_descriptors(img, e[order])
+    assert_bit_equal(mixed, plain[order], "descriptors per edge")
+    assert_bit_equal(plain, sc.oracle_descriptors("s2_odd"), "descriptors")
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle_distances(n_pairs):
+    left, cand, row_ptr, _ = sc.distance_case(n_pairs)
+    return orc.sift_min_distances(left, cand, row_ptr)
+
+
+@pytest.mark.parametrize("n_pairs", sc.DIST_PAIRS)
+def test_min_distances_on_integer_descriptors(ctx, n_pairs):
+    """sift_dist_kernel around its sixteen-lane groups and around one full sweep of its capped grid (4096 blocks = 65,536
+    pairs): the second sweep's tail is partly invalid under the shuffles"""
+    from tests.test_sift_cases import check_specials
+    left, cand, row_ptr, sp = sc.distance_case(n_pairs)
+    d = ctx.sift_min_distances(left, cand, row_ptr)
+    assert_bit_equal(d, _oracle_distances(n_pairs), "min distances")
+    check_specials(d, left, cand, row_ptr, sp, n_pairs)

@@ -74,3 +74,109 @@ def test_resident_pipeline_with_undistortion(ctx):
     ctx.stereo_upload(l, r)
     c2 = ctx.stereo_run(ctx.default_params(F))
     assert_edges_equal(ctx.stereo_fetch(c2)["left"], orc.toed(l)["edges"])
+
+
+# ---- the branches no EuRoC-like model reaches: borders, the (short) wrap, saturation, stripes of 1 .. 3 rows --------------------
+# (tests/undistort_cases.py; tests/test_undistort_cases.py shows on the CPU that every case reaches its branch and that a second
+# reading of the algorithm agrees with the oracle there)
+import ctypes as C
+
+from edge_based_visual_odometry_amd._lib import EBVO_ERR_ARG
+from edge_based_visual_odometry_amd.api import Context
+from tests import undistort_cases as uc
+
+F_KITTI = synth.fundamental_for("kitti")
+
+
+@pytest.fixture(scope="module")
+def wide_ctx():
+    """the stripe cases are wider than the session context"""
+    c = Context(*uc.WIDE_CONTEXT, device=0)
+    yield c
+    c.close()
+
+
+def _oracle(name):
+    _, K, dist = uc.CASES[name]
+    return orc.undistort(uc.image(name), K, dist)
+
+
+def _check_case(c, name):
+    (h, w), K, dist = uc.CASES[name]
+    img, ref = uc.image(name), _oracle(name)
+    got = c.undistort(img, K, dist)
+    assert (got == ref).all(), f"{name}: {int((got != ref).sum())} pixels differ, first at {np.argwhere(got != ref)[:4].tolist()}"
+    wide = np.full((h, w + 13), 201, dtype=np.uint8)             # strided input: the padding must never be sampled
+    wide[:, :w] = img
+    got = c.undistort(wide[:, :w], K, dist)
+    assert (got == ref).all(), f"{name} (strided): {int((got != ref).sum())} pixels differ"
+
+
+@pytest.mark.parametrize("name", [n for n in uc.CASES if n not in uc.WIDE])
+def test_border_wrap_and_saturation_cases_equal_oracle(ctx, name):
+    _check_case(ctx, name)
+
+
+@pytest.mark.parametrize("name", uc.WIDE)
+def test_stripe_cases_equal_oracle(wide_ctx, name):
+    _check_case(wide_ctx, name)
+
+
+def _raw_undistort(c, img, h, w, K, dist, out, out_stride, n_dist=None):
+    K = np.ascontiguousarray(K, dtype=np.float64)
+    dist = np.ascontiguousarray(dist, dtype=np.float64)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    return c.lib.ebvo_undistort(c._ctx, p(img), h, w, img.strides[0], p(K), p(dist), len(dist) if n_dist is None else n_dist,
+                                p(out), out_stride)
+
+
+def test_padded_output_rows_and_refusals(ctx):
+    """ebvo_undistort with out_stride != w (the 2-D copy back, which api.undistort never asks for), and the argument checks"""
+    name = "pincushion"
+    (h, w), K, dist = uc.CASES[name]
+    img = np.ascontiguousarray(uc.image(name))
+    out = np.full((h, w + 7), 0xA5, dtype=np.uint8)
+    assert _raw_undistort(ctx, img, h, w, K, dist, out, w + 7) == 0
+    assert (out[:, :w] == _oracle(name)).all()
+    assert (out[:, w:] == 0xA5).all()                                # the padding bytes are untouched
+    before = out.copy()
+    six = list(dist) + [0.0, 0.0]
+    assert _raw_undistort(ctx, img, h, w, K, six, out, w + 7, n_dist=6) == EBVO_ERR_ARG
+    assert _raw_undistort(ctx, img, h, w, K, dist, out, w - 1) == EBVO_ERR_ARG
+    assert _raw_undistort(ctx, img, 31, w, K, dist, out, w + 7) == EBVO_ERR_ARG
+    assert (out == before).all()                                     # a refused call writes nothing
+
+
+def test_resident_pipeline_samples_over_the_border(ctx):
+    """set_undistort with two models that leave the image (left: pincushion, right: corner_pp): the detector then runs on images
+    with black regions, whose rims are edges themselves"""
+    h, w = 97, 131
+    _, K, d = uc.CASES["pincushion"]
+    _, Kr, dr = uc.CASES["corner_pp"]
+    l, r = synth.stereo_pair("s2", h, w)
+    lu, ru = orc.undistort(l, K, d), orc.undistort(r, Kr, dr)
+    ctx.set_undistort(K, d, Kr, dr)
+    try:
+        ctx.stereo_upload(l, r)
+        c = ctx.stereo_run(ctx.default_params(F_KITTI))
+        out = ctx.stereo_fetch(c)
+    finally:
+        ctx.set_undistort()
+    L, R = orc.toed(lu)["edges"], orc.toed(ru)["edges"]
+    assert_edges_equal(out["left"], L, "left edges (undistorted image)")
+    assert_edges_equal(out["right"], R, "right edges (undistorted image)")
+    rp, ci = orc.epi_candidates(L, R, orc.epipolar_lines(F_KITTI, L))
+    assert len(ci) > 1000
+    assert_bit_equal(out["row_ptr"], rp, "row_ptr")
+    assert_bit_equal(out["col_idx"], ci, "col_idx")
+    sims, _, keep, _ = orc.ncc_pairs(l, r, L, R[ci], rp)
+    assert_bit_equal(out["sims"], sims, "sims (raw images)")
+    assert_bit_equal(out["keep"], keep, "keep")
+    assert not np.array_equal(orc.ncc_pairs(lu, ru, L, R[ci], rp)[0], sims)
+    # the border is really in play: left edges next to the region that no source pixel reaches
+    from tests import undistort_reading as ur
+    black = ur.undistort(l, K, d)[1]["none_mask"]
+    assert black.sum() >= 1000 and (lu[black] == 0).all()
+    x, y = np.rint(L["x"]).astype(int), np.rint(L["y"]).astype(int)
+    near = [black[max(0, b - 3):b + 4, max(0, a - 3):a + 4].any() for a, b in zip(x, y)]
+    assert sum(near) >= 1
