@@ -83,6 +83,38 @@ __global__ __launch_bounds__(256) void boxes_kernel(const ebvo_edge *__restrict_
     boxes_body(R, devn(nRd), cb, gb, tile_flag, ntiles, blockIdx.x, gridDim.x);
 }
 
+// fmin / fmax of the candidate search as the bare instruction.  llvm.minnum / maxnum put a canonicalising v_max_f64 x, x, x
+// in front of every operand that is not the result of an arithmetic instruction (anything read from LDS or moved between
+// lanes), to quiet a signalling NaN; v_min_f64 / v_max_f64 return the other operand when one is a quiet NaN, as fmin / fmax
+// do, so the value is theirs for every input but a signalling NaN, which the instruction (IEEE mode) returns quieted where
+// fmin / fmax would return the other operand.  Here every operand is the result of arithmetic or of fmin / fmax except the
+// box of a chunk of one edge (a copy of the caller's coordinates): a NaN there makes the compares behind it false, which
+// marks the chunk -- conservative, and such an edge passes no enabled predicate.  Not volatile: free to be hoisted or merged.
+__device__ inline double fmin_q(double a, double b)
+{
+    double r;
+    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ inline double fmax_q(double a, double b)
+{
+    double r;
+    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ inline double wave_min_q(double v)
+{
+    for (int d = 32; d > 0; d >>= 1)
+        v = fmin_q(v, __shfl_xor(v, d));
+    return v;
+}
+__device__ inline double wave_max_q(double v)
+{
+    for (int d = 32; d > 0; d >>= 1)
+        v = fmax_q(v, __shfl_xor(v, d));
+    return v;
+}
+
 // Conservative bounding box of one left edge's search region {band} ∩ {disparity square}.
 __device__ inline Box region_box(const LeftCtx &l, double D, double band, int mask)
 {
@@ -101,37 +133,110 @@ __device__ inline Box region_box(const LeftCtx &l, double D, double band, int ma
         {
             const double ya = -(l.ah * r.x0 + l.ch) / l.bh, yb = -(l.ah * r.x1 + l.ch) / l.bh;
             const double e = band / fabs(l.bh) + BOX_SLACK;
-            r.y0 = fmax(r.y0, fmin(ya, yb) - e);
-            r.y1 = fmin(r.y1, fmax(ya, yb) + e);
+            r.y0 = fmax_q(r.y0, fmin_q(ya, yb) - e);
+            r.y1 = fmin_q(r.y1, fmax_q(ya, yb) + e);
         }
         if (fabs(l.ah) > m)
         {
             const double xa = -(l.bh * r.y0 + l.ch) / l.ah, xb = -(l.bh * r.y1 + l.ch) / l.ah;
             const double e = band / fabs(l.ah) + BOX_SLACK;
-            r.x0 = fmax(r.x0, fmin(xa, xb) - e);
-            r.x1 = fmin(r.x1, fmax(xa, xb) + e);
+            r.x0 = fmax_q(r.x0, fmin_q(xa, xb) - e);
+            r.x1 = fmin_q(r.x1, fmax_q(xa, xb) + e);
         }
     }
     return r;
 }
 
+// box_may_match (ebvo_cand.h) for the candidate walk: the same operations in the same order with fmin_q / fmax_q, hence the
+// same answer (for every input without a signalling NaN, see above).  The walk's fallback mark; gt_kernels.hip keeps the
+// header's version.
+__device__ inline bool box_may_match_q(const Box &bx, double xl, double yl, double ah, double bh, double ch, double D,
+                                       double band, int mask)
+{
+    double x0 = bx.x0, x1 = bx.x1, y0 = bx.y0, y1 = bx.y1;
+    bool out = false; // no early return: the line test of an empty intersection is computed and discarded
+    if (mask & EBVO_STAGE_DISPARITY)
+    {
+        x0 = fmax_q(x0, xl - D);
+        x1 = fmin_q(x1, xl + D);
+        y0 = fmax_q(y0, yl - D);
+        y1 = fmin_q(y1, yl + D);
+        out = x0 > x1 || y0 > y1;
+    }
+    if (mask & EBVO_STAGE_EPIPOLAR)
+    {
+        const double gx0 = ah * x0, gx1 = ah * x1, gy0 = bh * y0, gy1 = bh * y1;
+        const double gmin = fmin_q(gx0, gx1) + fmin_q(gy0, gy1) + ch;
+        const double gmax = fmax_q(gx0, gx1) + fmax_q(gy0, gy1) + ch;
+        out = out || gmin > band || gmax < -band;
+    }
+    return !out;
+}
+
+// Fast mark of the walk: does a chunk box meet the left edge's region box (region_box above it)?  Four compares, nothing of
+// the line.  It may stand in for box_may_match because every right edge (x, y) that passes pair_passes for the left edge
+// lies inside that edge's region box -- the property the union U of these boxes, which selects what is staged at all, has
+// always rested on:
+//   * disparity: the pair passes with fl(dx*dx + dy*dy) <= max_disp^2 (1 + 2^-50) (or its root <= max_disp), so
+//     |dx|, |dy| <= max_disp (1 + 2^-50) with dx = fl(lx - x); the roundings of dx and of the box's own fl(lx -+ D) are at
+//     most 2^-53 * 2^12 = 4.6e-13 each for coordinates below 4096, and max_disp * 2^-50 stays below 1e-12 up to
+//     max_disp = 1000: together 2e-12 against the BOX_SLACK = 1e-6 that D = max_disp + BOX_SLACK adds on either side.
+//   * epipolar: the pair passes with |a x + b y + c| / nrm < epi_thr (1 + 2^-50); dividing through by |bh|, y lies within
+//     epi_thr / |bh| of the line's height at x (up to the roundings of the three products and two sums: a few 2^-53 of
+//     (|ah| x + |bh| y + |ch|) <= 1.2e4 for lines that cross a 4096-px frame, i.e. 1e-11, again over |bh|), x lies in the
+//     square's [x0, x1], and a line's height over an interval is between its heights ya, yb at the ends.  The box takes
+//     min(ya, yb) - e .. max(ya, yb) + e with e = (epi_thr + BOX_SLACK) / |bh| + BOX_SLACK: 1e-6 / |bh| + 1e-6 of room for
+//     1e-11 / |bh|.  The x-range follows from the resulting y-range the same way.  Where a slope is below 1e-9 or the
+//     line is NaN the box keeps the square's bound (+-inf without the disparity stage).
+// A NaN bound marks: every comparison with it is false.  The flag `flat` (candidates_kernel, step 1) only chooses between
+// this filter and box_may_match_q, both conservative; no result depends on it.
+//   box_meets_region(bx, r) = !(bx.x0 > r.x1 || bx.x1 < r.x0 || bx.y0 > r.y1 || bx.y1 < r.y0)
+// region_ballot is the ballot of that over the active lanes, taken straight from the four compares' lane masks (ANDed as
+// scalars) instead of from a per-lane flag: "not greater" is the unordered-or-less-equal compare, and so on.
+__device__ inline unsigned long long region_ballot(const Box bx, const Box r)
+{
+    constexpr int UGE = 11, ULE = 13; // llvm::CmpInst::FCMP_UGE / FCMP_ULE
+    return __builtin_amdgcn_fcmp(bx.x0, r.x1, ULE) & __builtin_amdgcn_fcmp(bx.x1, r.x0, UGE) &
+           __builtin_amdgcn_fcmp(bx.y0, r.y1, ULE) & __builtin_amdgcn_fcmp(bx.y1, r.y0, UGE);
+}
+
+// `flat`: the extent that the line's tilt adds to the region box across the disparity square, 2 D min(|ah|, |bh|) /
+// max(|ah|, |bh|), is at most FLAT_BANDS bands.  Then the region box is the band ∩ square up to that much (for a rectified
+// pair, a = 0, exactly), and the box-against-box test marks what box_may_match marks; a steeper line cuts the corner of
+// its region box, which only the line test sees.  NaN (no line, a = b = 0) is not flat.  DESIGN §5.3 item 5 has the counts.
+constexpr double FLAT_BANDS = 4.0;
+__device__ inline bool region_is_flat(const LeftCtx &l, double D, double band)
+{
+    const double p = fabs(l.ah), q = fabs(l.bh);
+    return 2.0 * D * fmin(p, q) <= FLAT_BANDS * band * fmax(p, q);
+}
+
 // Candidate search.  One block = one tile of TILE (64) consecutive left edges; the right edges are visited through
-// two levels of index-range bounding boxes (chunks of 16 edges, groups of 64 chunks):
-//   1. wave 0 builds the 64 left-edge contexts (LDS) and the union of their search regions;
+// two levels of index-range bounding boxes (chunks of 8 edges, groups of 64 chunks):
+//   1. wave 0 builds the 64 left-edge contexts, their region boxes and `flat` flags (LDS) and the union of the regions;
 //   2. all 256 threads select the groups, then the chunks, whose boxes meet the union (ordered LDS compaction, so
-//      chunks stay in ascending index), and stage the selected chunks' edges in LDS, 64 chunks at a time;
-//   3. walk: sixteen lanes per left edge (four rounds of sixteen left edges).  The sixteen lanes test the staged
-//      chunk boxes against their edge's own region (four ballots -> a 64-bit chunk mask), then take the marked
-//      chunks in ascending order, ONE pair test per lane per chunk; a ballot gives the 16-bit hit mask, hence every
-//      hit's rank in the row.  ~2 M threads instead of one per left edge: the walk used to be a serial chain of
-//      ~120 dependent LDS reads + tests per lane with two waves per SIMD to hide it behind.
+//      chunks stay in ascending index), and stage the selected chunks' edges and boxes in LDS, 64 chunks at a time;
+//   3. walk: eight lanes per left edge (two rounds of 32 left edges).  The eight lanes mark the staged chunks that can
+//      meet their edge's own region -- lane e looks at boxes e, e + 8, ...; eight ballots -> a 64-bit chunk mask --, then
+//      take the marked chunks in ascending order, ONE pair test per lane per chunk; a ballot gives the 8-bit hit mask,
+//      hence every hit's rank in the row.
+//      The mark: with the epipolar and the disparity stage both enabled (the resident pipeline's case) an edge whose
+//      line is `flat` (region_is_flat: every edge of a rectified or nearly rectified rig) tests the chunk box against
+//      its region box -- four compares whose lane masks, ANDed, ARE the ballot: about 7 VALU instructions per box
+//      where the line test took 36 + 8 (14 of them canonicalising v_max_f64 x, x, x in front of fmin / fmax of LDS
+//      operands).  Every other edge, and every edge under another stage mask, takes the line test, box_may_match_q,
+//      which marks what box_may_match marks; a wave without such an edge branches around it.  Both marks are conservative
+//      (box_meets_region has the bound), the pair predicates decide, so the CSR is the same whichever ran.
+//      No fmin / fmax in the kernel's loops goes through the canonicalising form (fmin_q / fmax_q).
 // The counting pass also keeps the first STAGE candidates of every row and the total of every tile; once the row offsets
 // are known every row that fits is completed from the staging area, and the FILL pass only redoes tiles that hold a longer
 // row.  COPY: the fill pass copies the staged rows itself, as its prologue (host-buffer path, behind the two scan kernels);
 // the resident pair's chain has the offsets and the copy in the right bank's launch (cand_rows_body) and runs the fill pass
 // without the prologue, as the long-row redo only.
+// Four waves per SIMD as a launch bound: 117 VGPRs, what the kernel took before the region marks; unbounded, the scheduler
+// spends 144 on the unrolled marks.
 template <bool FILL, bool COPY = FILL>
-__global__ __launch_bounds__(256) void candidates_kernel(const ebvo_edge *__restrict__ L,
+__global__ __launch_bounds__(256, 4) void candidates_kernel(const ebvo_edge *__restrict__ L,
                                                          const ebvo_edge *__restrict__ R,
                                                          const double *__restrict__ lines,
                                                          const Box *__restrict__ cb, const Box *__restrict__ gb,
@@ -143,6 +248,8 @@ __global__ __launch_bounds__(256) void candidates_kernel(const ebvo_edge *__rest
     __shared__ double s_x[BATCH * CHUNK], s_y[BATCH * CHUNK], s_th[BATCH * CHUNK];
     __shared__ Box s_box[BATCH];
     __shared__ LeftCtx s_left[TILE];
+    __shared__ Box s_region[TILE]; // every left edge's own region box: the walk's fast mark
+    __shared__ int s_flat[TILE];   // 1: the fast mark stands in for box_may_match_q (region_is_flat, both stages enabled)
     __shared__ int s_round[256];   // chunks selected in the current round, ascending
     __shared__ int s_groups[256];  // groups selected in the current group round, ascending
     __shared__ int s_wcnt[4];
@@ -160,6 +267,7 @@ __global__ __launch_bounds__(256) void candidates_kernel(const ebvo_edge *__rest
     const double d2 = P.max_disp * P.max_disp;
     const double D = P.max_disp + BOX_SLACK, band = P.epi_thr + BOX_SLACK;
     const double inf = __builtin_inf();
+    const bool both_stages = (P.mask & EBVO_STAGE_EPIPOLAR) && (P.mask & EBVO_STAGE_DISPARITY);
     unsigned long long blk_total = 0; // thread 0: candidates counted by this block
 
     // ordered (index-preserving) compaction of one value per selected thread into an LDS list
@@ -216,7 +324,9 @@ __global__ __launch_bounds__(256) void candidates_kernel(const ebvo_edge *__rest
             Box rb = region_box(l, D, band, P.mask);
             if (!live) { rb.x0 = inf; rb.x1 = -inf; rb.y0 = inf; rb.y1 = -inf; }
             s_left[lane] = l;
-            const double a0 = wave_min(rb.x0), a1 = wave_max(rb.x1), b0 = wave_min(rb.y0), b1 = wave_max(rb.y1);
+            s_region[lane] = rb;
+            s_flat[lane] = both_stages && region_is_flat(l, D, band);
+            const double a0 = wave_min_q(rb.x0), a1 = wave_max_q(rb.x1), b0 = wave_min_q(rb.y0), b1 = wave_max_q(rb.y1);
             if (lane == 0) { s_red[0] = a0; s_red[1] = a1; s_red[2] = b0; s_red[3] = b1; }
         }
         __syncthreads();
@@ -267,8 +377,9 @@ __global__ __launch_bounds__(256) void candidates_kernel(const ebvo_edge *__rest
                         }
                         s_x[idx] = x; s_y[idx] = y; s_th[idx] = th;
                     }
-                    if (tid < mb)
-                        s_box[tid] = cb[s_round[b0 + tid]];
+                    if (tid < BATCH) // all BATCH boxes, so that the marks read them unguarded; `staged` drops those beyond mb
+                        s_box[tid] = cb[tid < mb ? s_round[b0 + tid] : 0];
+                    const unsigned long long staged = mb < 64 ? (1ull << mb) - 1ull : ~0ull; // bit j: box j holds a staged chunk
                     __syncthreads();
                     // ---- 3. walk
 #pragma unroll
@@ -279,17 +390,34 @@ __global__ __launch_bounds__(256) void candidates_kernel(const ebvo_edge *__rest
                         const bool live = i < nL; // uniform in the group
                         const LeftCtx l = s_left[li];
                         // which staged chunks can meet this edge's region: lane e looks at boxes e, e + LPE, e + 2 LPE, ...
+                        // and the ballot's byte of the edge's lanes becomes byte k of the mask.  A flat edge tests the
+                        // boxes against its region box; any other edge -- and every edge unless both stages are
+                        // enabled -- against the line itself.  The choice is uniform in the edge's lanes (so a ballot
+                        // taken inside either branch has the whole byte), and a wave without an edge of the second
+                        // kind skips that branch.
                         unsigned long long pm = 0;
-#pragma unroll
-                        for (int k = 0; k < BATCH / LPE; ++k)
+                        if (live && s_flat[li])
                         {
-                            const int j = k * LPE + e;
-                            const bool may = live && j < mb &&
-                                             box_may_match(s_box[j < mb ? j : 0], l.lx, l.ly, l.ah, l.bh, l.ch, D, band,
-                                                           P.mask);
-                            const unsigned long long bal = __ballot(may);
-                            pm |= ((bal >> gshift) & GMASK) << (LPE * k);
+                            const Box rg = s_region[li];
+#pragma unroll
+                            for (int k = 0; k < BATCH / LPE; ++k)
+                            {
+                                const Box bx = s_box[k * LPE + e];
+                                pm |= ((region_ballot(bx, rg) >> gshift) & GMASK) << (LPE * k);
+                            }
                         }
+                        else if (live)
+                        {
+                            const double ah = s_left[li].ah, bh = s_left[li].bh, ch = s_left[li].ch;
+#pragma unroll 2
+                            for (int k = 0; k < BATCH / LPE; ++k)
+                            {
+                                const Box bx = s_box[k * LPE + e];
+                                const unsigned long long bal = __ballot(box_may_match_q(bx, l.lx, l.ly, ah, bh, ch, D, band, P.mask));
+                                pm |= ((bal >> gshift) & GMASK) << (LPE * k);
+                            }
+                        }
+                        pm &= staged;
                         // marked chunks in ascending order, one pair test per lane
                         while (__any(pm != 0))
                         {
