@@ -81,7 +81,9 @@ def _mv(m, v):
 
 def find_gt_locations(left_edges, disp, K_left, R21, T21, gate_deg=4.0):
     """Find_Stereo_GT_Locations (:133-200), is_left = true, per left edge: valid (the edge reaches :162), gt_xy, gamma_left,
-    gamma_right ((-1, -1) / (-1, -1, -1) where skipped: the device's fill values; the reference stores nothing there)."""
+    gamma_right ((-1, -1) / (-1, -1, -1) where skipped: the device's fill values; the reference stores nothing there).
+    An edge with a NaN or infinite coordinate is skipped (valid 0, fill -1): the reference would index the map with it;
+    the device calls it out of bounds (gt_kernels.hip: bilinear_f32_nan), and that is the rule stated here."""
     K = np.asarray(K_left, dtype=np.float64).reshape(3, 3)
     R = [[float(v) for v in row] for row in np.asarray(R21, dtype=np.float64).reshape(3, 3)]
     T = [float(v) for v in np.asarray(T21, dtype=np.float64).reshape(3)]
@@ -94,6 +96,8 @@ def find_gt_locations(left_edges, disp, K_left, R21, T21, gate_deg=4.0):
         x, y, th = float(left_edges["x"][i]), float(left_edges["y"][i]), float(left_edges["theta"][i])
         deg = th * RAD_TO_DEG
         if abs(deg) < gate_deg or abs(deg - 180.0) < gate_deg or abs(deg + 180.0) < gate_deg:     # :146
+            continue
+        if not (math.isfinite(x) and math.isfinite(y)):                                # the stated rule (docstring)
             continue
         d = bilinear_f32(disp, x, y)                                                   # :152
         if math.isnan(d) or math.isinf(d) or d < 0:                                    # :154
@@ -196,16 +200,30 @@ def metrics(n_tp, focused, drop_empty=False):
                 precision_pair=div(acc_pair, float(nonempty)), ambiguity=div(acc_n, float(nonempty)))         # :367-368
 
 
+def geometric_lists(L, R, lines, epi_thr=0.5, max_disp=25.0, orient_thr_deg=10.0, stage_mask=7):
+    """The three geometric lists (:1374, :1387, :1399) of a run with `stage_mask`: the candidate lists at stage_mask & 1,
+    stage_mask & 3 and stage_mask & 7, each predicate on top of the previous ones -- a stage that is switched off passes
+    every pair it is given.  With no predicate enabled yet the list is every right edge on every row (built densely)."""
+    out = {}
+    for sid, bits in ((EPIPOLAR, 1), (DISPARITY, 3), (ORIENTATION, 7)):
+        mask = stage_mask & bits
+        if mask:
+            r_, c_ = orc.epi_candidates(L, R, lines, epi_thr, max_disp, orient_thr_deg, stage_mask=mask)
+        else:
+            r_ = (np.arange(len(L) + 1, dtype=np.int64) * len(R)).astype(np.int32)
+            c_ = np.tile(np.arange(len(R), dtype=np.int32), len(L))
+        out[sid] = (r_, R["x"][c_].copy(), R["y"][c_].copy())
+    return out
+
+
 def stage_lists(left_img, right_img, F, stage1, sift=False, bnb_ratio=0.9, ncc_thr=0.6, sift_thr=500.0, bnb_sift=0.4,
-                max_iter=20, tol=1e-3, huber_delta=3.0, epi_thr=0.5, max_disp=25.0, orient_thr_deg=10.0):
+                max_iter=20, tol=1e-3, huber_delta=3.0, epi_thr=0.5, max_disp=25.0, orient_thr_deg=10.0, stage_mask=7):
     """Every list Evaluate_Stereo_Edge_Correspondences sees (:1377-1536) as {stage id: (row_ptr, x, y)}; the composition of
-    tests/oracle_chain.py:stereo_edge_pairs.  stage1: dict(left, right, row_ptr, col_idx, best, keep) of the oracle."""
+    tests/oracle_chain.py:stereo_edge_pairs.  stage1: dict(left, right, row_ptr, col_idx, best, keep) of the oracle, formed
+    with the same epi_thr, max_disp, orient_thr_deg and stage_mask."""
     L, R, rp, ci, best, keep = (stage1[k] for k in ("left", "right", "row_ptr", "col_idx", "best", "keep"))
     lines = orc.epipolar_lines(F, L)
-    out = {}
-    for sid, mask in ((EPIPOLAR, 1), (DISPARITY, 3), (ORIENTATION, 7)):                # :1374, :1387, :1399
-        r_, c_ = orc.epi_candidates(L, R, lines, epi_thr, max_disp, orient_thr_deg, stage_mask=mask)
-        out[sid] = (r_, R["x"][c_].copy(), R["y"][c_].copy())
+    out = geometric_lists(L, R, lines, epi_thr, max_disp, orient_thr_deg, stage_mask)
     assert (out[ORIENTATION][0] == rp).all()
     put = lambda sid, rp_, cand: out.__setitem__(sid, (np.asarray(rp_).copy(), cand["x"].copy(), cand["y"].copy()))
     conf = None
@@ -267,9 +285,11 @@ def evaluate_stages(lists, focused, gt_xy, tp_dist=1.0):
     return res
 
 
-def disparity_map(h, w, shift, seed=0):
+def disparity_map(h, w, shift, seed=0, zero_patch=False):
     """A float32 left disparity map for a synth.stereo_pair of constant `shift`: that constant, with a smooth ramp region
-    (so the bilinear weights matter), a NaN band, a +inf patch and a negative patch."""
+    (so the bilinear weights matter), a NaN band, a +inf patch and a negative patch.  zero_patch: also a patch of exact
+    0.0 -- d = 0 is valid (:154 refuses only d < 0), the GT location is the edge itself, and with an identity R21 the
+    back-projection's denominator (src/utility.cpp:99) is exactly 0."""
     yy, xx = np.mgrid[0:h, 0:w]
     d = np.full((h, w), float(shift), dtype=np.float32)
     ramp = (xx >= w // 2) & (xx < w // 2 + w // 4)
@@ -277,4 +297,6 @@ def disparity_map(h, w, shift, seed=0):
     d[h // 3:h // 3 + 6, :] = np.nan
     d[h // 2:h // 2 + 12, w // 8:w // 8 + 20] = np.inf
     d[2 * h // 3:2 * h // 3 + 10, w // 3:w // 3 + 24] = -3.0
+    if zero_patch:
+        d[h // 6:h // 6 + 12, 5 * w // 8:5 * w // 8 + 30] = 0.0
     return d

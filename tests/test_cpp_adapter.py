@@ -104,11 +104,13 @@ def test_adapter_matches_oracle(tmp_path):
     # stage glue through the adapters
     obest = orc.ncc_pairs(l, r, ol["edges"], orr["edges"][oci], orp)[1]
     oc, oo = orc.bnb_test(orp, obest, 0.9, True)
-    assert_bit_equal(bnb_cnt, oc) and assert_bit_equal(bnb_order, oo)
+    assert_bit_equal(bnb_cnt, oc, "bnb count")
+    assert_bit_equal(bnb_order, oo, "bnb order")
     osh = orc.epipolar_shift(orr["edges"][oci], lines, orp)
     assert_edges_equal(shifted, osh)
     occ, _, ocof = orc.cluster_rows(osh, orp, False, True)
-    assert_bit_equal(cl_cnt, occ) and assert_bit_equal(cl_of, ocof)
+    assert_bit_equal(cl_cnt, occ, "cluster count")
+    assert_bit_equal(cl_of, ocof, "cluster_of")
     assert_bit_equal(best_cnt, (np.diff(orp) > 0).astype(np.int32))
     # the output file of the reference's writer: header + 16 numbers per kept match at 6 significant digits
     kept = okeep.astype(bool)

@@ -84,7 +84,8 @@ def test_on_pipeline_scores(ctx):
     scores = o["best"][keep]
     cnt, order = ctx.bnb_test(rp, scores, 0.9, True)
     oc, oo = orc.bnb_test(rp, scores, 0.9, True)
-    assert_bit_equal(cnt, oc) and assert_bit_equal(order, oo)
+    assert_bit_equal(cnt, oc, "count")
+    assert_bit_equal(order, oo, "order")
     assert 0 < cnt.sum() < len(scores)
     # every survivor's score is within the ratio of its row's best
     for i in np.nonzero(cnt > 0)[0][:500]:
@@ -150,5 +151,6 @@ def test_cluster_on_refined_matches(ctx):
     cand["theta"] = o["right"]["theta"][o["col_idx"][keep]]
     cnt, centres, cof = ctx.cluster_rows(cand, rp)
     oc, ocen, ocof = orc.cluster_rows(cand, rp)
-    assert_bit_equal(cnt, oc) and assert_bit_equal(cof, ocof)
+    assert_bit_equal(cnt, oc, "new_count")
+    assert_bit_equal(cof, ocof, "cluster_of")
     assert cnt.sum() < len(cand)                                   # refinement pulls neighbouring candidates together

@@ -213,7 +213,8 @@ def test_finalize_pairs_equals_oracle_and_geometry(ctx):
     out = ctx.finalize_pairs(K, K, cal["R21"], cal["T21"], L, R)
     ref = orc.finalize_pairs(K, K, cal["R21"], cal["T21"], L, R)
     assert_bit_equal(out, ref, "finalize_pairs")
-    assert_bit_equal(out[:, 0], L["x"]) and assert_bit_equal(out[:, 5], R["theta"])
+    assert_bit_equal(out[:, 0], L["x"], "left x")
+    assert_bit_equal(out[:, 5], R["theta"], "right theta")
     d = L["x"] - R["x"]
     ok = np.abs(d - 12.0) < 0.5
     assert ok.mean() > 0.5

@@ -57,7 +57,8 @@ def test_resident_pipeline_with_undistortion(ctx):
     assert_edges_equal(out["right"], R, "right edges (undistorted image)")
     lines = orc.epipolar_lines(F, L)
     rp, ci = orc.epi_candidates(L, R, lines)
-    assert_bit_equal(out["row_ptr"], rp) and assert_bit_equal(out["col_idx"], ci)
+    assert_bit_equal(out["row_ptr"], rp, "row_ptr")
+    assert_bit_equal(out["col_idx"], ci, "col_idx")
     sims, best, keep, lp = orc.ncc_pairs(l, r, L, R[ci], rp)
     assert_bit_equal(out["sims"], sims, "sims (raw images)")
     assert_bit_equal(out["keep"], keep, "keep")
