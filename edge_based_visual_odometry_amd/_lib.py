@@ -52,6 +52,8 @@ ABI_SYMBOLS = (
     "ebvo_stereo_gt_stage_rows", "ebvo_gt_locate", "ebvo_gt_evaluate_rows",
     "ebvo_tgt_default_params", "ebvo_temporal_set_gt", "ebvo_temporal_gt_size", "ebvo_temporal_gt_fetch", "ebvo_temporal_gt_metrics",
     "ebvo_temporal_gt_flags", "ebvo_tgt_veridical", "ebvo_tgt_evaluate_rows",
+    "ebvo_temporal_keep_stages", "ebvo_temporal_stage_size", "ebvo_temporal_fetch_stage", "ebvo_temporal_gt_stage_rows",
+    "ebvo_tgt_grid_rows",
     "ebvo_pose_from_quads_gt", "ebvo_temporal_estimate_pose_gt", "ebvo_pose_constraint_metrics",
     "ebvo_temporal_pose_constraint_metrics",
 )
@@ -348,6 +350,11 @@ def load_library() -> C.CDLL:
     lib.ebvo_tgt_veridical.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, vp, vp, C.POINTER(StereoCalib),
                                        C.POINTER(TgtParams), vp, vp, vp, vp, vp, vp, vp, i64, C.POINTER(i64)]
     lib.ebvo_tgt_evaluate_rows.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, dbl, vp, vp, C.POINTER(GtStage)]
+    lib.ebvo_temporal_keep_stages.argtypes = [vp, i32, i32]
+    lib.ebvo_temporal_stage_size.argtypes = [vp, i32, i32, C.POINTER(i64)]
+    lib.ebvo_temporal_fetch_stage.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+    lib.ebvo_temporal_gt_stage_rows.argtypes = [vp, i32, i32, vp, i32]
+    lib.ebvo_tgt_grid_rows.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, dbl, vp, vp, vp, dbl, vp, C.POINTER(GtStage)]
     lib.ebvo_undistort.argtypes = [vp, vp, i32, i32, ssz, vp, vp, i32, vp, ssz]
     lib.ebvo_stereo_set_undistort.argtypes = [vp, C.POINTER(UndistortParams)]
     lib.ebvo_stereo_fetch_end.argtypes = [vp, i32, C.POINTER(StereoView)]

@@ -979,8 +979,9 @@ class Context:
         return d
 
     def temporal_gt_metrics(self, slot: int = 0) -> list:
-        """One dict per stage of get_Temporal_Edge_Pairs_from_Quads under the reference's names; `present` only for
-        Orientation, NCC and (after stages = 1) Edge Clustering."""
+        """One dict per stage of get_Temporal_Edge_Pairs_from_Quads under the reference's names; `present` for Orientation,
+        NCC and (after stages = 1) Edge Clustering, and after temporal_keep_stages for Location Proximity and (stages = 1)
+        the four interior stages as well."""
         arr = (_lib.GtStage * _lib.TGT_NUM_STAGES)()
         rc = self.lib.ebvo_temporal_gt_metrics(self._ctx, slot, arr)
         if rc < 0:
@@ -989,10 +990,58 @@ class Context:
 
     def temporal_gt_flags(self, stage: int, n: int, slot: int = 0) -> np.ndarray:
         """b_is_TP per quad of a present stage, in the stage's CSR order; n: the stage's quad count (n_candidates, n_kept
-        or n_final of the match)."""
+        or n_final of the match; n_sift, n_bnb_ncc, n_bnb_sift, n_bnb_sift for the interior stages of a kept trail)."""
         out = np.zeros(n, dtype=np.uint8)
         self._check(self.lib.ebvo_temporal_gt_flags(self._ctx, slot, stage, ptr(out)), "ebvo_temporal_gt_flags")
         return out
+
+    def temporal_keep_stages(self, on: bool = True, slot: int = 0):
+        """Per-slot switch read by the slot's NEXT temporal match (ebvo_temporal_keep_stages): that match leaves its interior
+        stage lists behind, and temporal_set_gt then evaluates every stage the match ran instead of three."""
+        self._check(self.lib.ebvo_temporal_keep_stages(self._ctx, slot, int(bool(on))), "ebvo_temporal_keep_stages")
+
+    def temporal_fetch_stage(self, stage: int, slot: int = 0) -> dict:
+        """The list after the SIFT filter, after either best-nearly-best test or after the refinement (stage = the EBVO_TGT_*
+        id) of a match that kept its trail with stages = 1: row_ptr over the keyframe mates, cf_index, and the centres the
+        evaluation reads (left, right: the mate's edges before the refinement, the refined centres at it)."""
+        n = C.c_int64()
+        self._check(self.lib.ebvo_temporal_stage_size(self._ctx, slot, stage, C.byref(n)), "ebvo_temporal_stage_size")
+        n_kf = self._tq_n_kf[slot]
+        out = dict(row_ptr=np.zeros(n_kf + 1, dtype=np.int32), cf_index=np.zeros(n.value, dtype=np.int32),
+                   left=np.zeros(n.value, dtype=EDGE_DTYPE), right=np.zeros(n.value, dtype=EDGE_DTYPE))
+        self._check(self.lib.ebvo_temporal_fetch_stage(self._ctx, slot, stage, *(ptr(out[k]) for k in (
+            "row_ptr", "cf_index", "left", "right"))), "ebvo_temporal_fetch_stage")
+        return out
+
+    def temporal_gt_stage_rows(self, stage: int, slot: int = 0) -> np.ndarray:
+        """(n, tp) of every keyframe mate at a present stage of the armed slot ([n_kf, 2] int32, zero on rows outside the
+        evaluation)."""
+        n_kf = self.temporal_gt_size(slot)["n_kf"]
+        out = np.zeros((n_kf, 2), dtype=np.int32)
+        self._check(self.lib.ebvo_temporal_gt_stage_rows(self._ctx, slot, stage, ptr(out), n_kf), "ebvo_temporal_gt_stage_rows")
+        return out
+
+    def tgt_grid_rows(self, kf_left, kf_right, cf_left, cf_right, img_w, img_h, row_on, proj_left, proj_right, cell_size=15,
+                      grid_radius: float = 30.0, tp_dist: float = 2.0):
+        """The grid stage ("Location Proximity") evaluated on host arrays without forming its list (ebvo_tgt_grid_rows).
+        Returns (n_tp [n_kf, 2] int32, stage dict)."""
+        kf_left, kf_right, cf_left, cf_right = (_edges(a) for a in (kf_left, kf_right, cf_left, cf_right))
+        n_kf, n_cf = len(kf_left), len(cf_left)
+        pl = np.ascontiguousarray(proj_left, dtype=np.float64).reshape(-1, 2)
+        pr = np.ascontiguousarray(proj_right, dtype=np.float64).reshape(-1, 2)
+        if row_on is not None:
+            row_on = np.ascontiguousarray(row_on, dtype=np.uint8)
+        if len(kf_right) != n_kf or len(cf_right) != n_cf or len(pl) != n_kf or len(pr) != n_kf or \
+                (row_on is not None and len(row_on) != n_kf):
+            raise ValueError("tgt_grid_rows: the arrays do not describe the same mates")
+        n_tp, g = np.zeros((n_kf, 2), dtype=np.int32), _lib.GtStage()
+        self._check(self.lib.ebvo_tgt_grid_rows(self._ctx, ptr(kf_left), ptr(kf_right), n_kf, ptr(cf_left), ptr(cf_right), n_cf,
+                                                int(img_w), int(img_h), int(cell_size), float(grid_radius), ptr(row_on), ptr(pl),
+                                                ptr(pr), float(tp_dist), ptr(n_tp), C.byref(g)), "ebvo_tgt_grid_rows")
+        d = self._tgt_stage_dict(g)
+        d.pop("name")
+        d.pop("stage")
+        return n_tp, d
 
     def tgt_veridical(self, kf_left, kf_right, cf_left, cf_right, img_w, img_h, R, t, calib, kf_gamma=None, cell_size=15,
                       **params) -> dict:

@@ -14,7 +14,7 @@ const char *const g_kernel_names[K_NUM] = {
     "toed_conv",   "toed_nms",   "toed_rowscan", "toed_compact", "toed_finalize", "toed_exact_centre", "toed_exact_mags", "cand_boxes", "epi_lines",
     "cand_count",  "scan",       "cand_fill",    "edge_patches", "ncc_pairs",     "ncc_stored", "misc", "sobel", "gn_refine", "sift",
     "gt_misc",     "gt_pool",    "gt_census",    "gt_rows",      "tgt_project",   "tgt_veridical", "tgt_rows",
-    "pose_cascade"};
+    "pose_cascade", "tgt_grid_rows"};
 
 // ------------------------------------------------------------------------------------------
 int ebvo_fail_hip(ebvo_ctx *ctx, hipError_t e, const char *what, const char *file, int line)
@@ -1168,6 +1168,7 @@ extern "C" int ebvo_stereo_upload_slot(ebvo_ctx *ctx, int slot, const uint8_t *i
         ctx->sw_tag[0] = ctx->sw_tag[1] = 0; // ... and so are the TOED results of the resident stage-wise calls
     s.tq_n = -1;
     s.tq_final.n = -1;
+    s.tq_trail = Slot::TqTrail();
     s.sift_left_valid = false;
     if ((rc = drain_fetch(ctx, s))) // a result copy of the previous pair still reads the buffers / an asynchronous upload writes them
         return rc;
@@ -1215,6 +1216,7 @@ extern "C" int ebvo_stereo_upload_async(ebvo_ctx *ctx, int slot, const uint8_t *
         ctx->sw_tag[0] = ctx->sw_tag[1] = 0;
     s.tq_n = -1;
     s.tq_final.n = -1;
+    s.tq_trail = Slot::TqTrail();
     s.sift_left_valid = false;
     s.pull = false;
     if (!ctx->ingest_stream) // (the pull form makes no runtime call at all)
@@ -2905,6 +2907,7 @@ extern "C" int ebvo_stereo_finalize_submit(ebvo_ctx *ctx, int slot, const ebvo_f
     s.have_final = s.have_refined = false; // the refinement buffers are reused
     s.tq_n = -1;
     s.tq_final.n = -1;
+    s.tq_trail = Slot::TqTrail();
     s.sift_left_valid = false;
     s.n_final = 0;
     s.final_has_rows = calib != nullptr;
@@ -3380,6 +3383,10 @@ static int temporal_chain(ebvo_ctx *ctx, Slot &s, const ebvo_temporal_params &P,
                  o_frp = carve(sizeof(int32_t) * nk1), o_fsrc = carve(sizeof(int32_t) * nK), o_fcf = carve(sizeof(int32_t) * nK),
                  o_fL = carve(sizeof(ebvo_edge) * nK), o_fR = carve(sizeof(ebvo_edge) * nK), o_fd = carve(sizeof(double) * 4 * nK),
                  o_fvalid = carve(nK);
+    // the stage trail (ebvo_temporal_keep_stages), behind everything else: room for the SIFT-stage list, which the BNB-SIFT
+    // compaction overwrites
+    Slot::TqTrail &T = s.tq_trail;
+    const size_t o_trp = T.on ? carve(sizeof(int32_t) * nk1) : 0, o_tcf = T.on ? carve(sizeof(int32_t) * nK) : 0;
     if ((rc = ebvo_grow(ctx, s, s.tq_chain, off + 64)))
         return rc;
     char *base = (char *)s.tq_chain.p;
@@ -3423,11 +3430,23 @@ static int temporal_chain(ebvo_ctx *ctx, Slot &s, const ebvo_temporal_params &P,
         }
         return glue_gather_enqueue(ctx, s, idx, *total, g);
     };
-    auto finish_empty = [&]() -> int { // nothing left: an empty final list
+    auto trail_set = [&](int stage, const int32_t *t_rp, const int32_t *t_cf, int64_t n) {
+        T.rp[stage - EBVO_TGT_SIFT] = t_rp;
+        T.cf[stage - EBVO_TGT_SIFT] = t_cf;
+        T.n[stage - EBVO_TGT_SIFT] = n;
+    };
+    // nothing left: an empty final list; the stages from `first_unreached` on ran on empty rows (the trail lists them empty)
+    auto finish_empty = [&](int first_unreached) -> int {
         s.tq_final.rp = (int32_t *)(base + o_frp);
         EBVO_HIP(ctx, hipMemsetAsync(s.tq_final.rp, 0, sizeof(int32_t) * nk1, st));
         EBVO_HIP(ctx, hipStreamSynchronize(st));
         s.tq_final.n = 0;
+        if (T.on)
+        {
+            for (int k = first_unreached; k <= EBVO_TGT_REFINE; ++k)
+                trail_set(k, s.tq_final.rp, nullptr, 0);
+            T.lists = true;
+        }
         return EBVO_OK;
     };
     // 0. the quads that passed the NCC filter
@@ -3440,7 +3459,7 @@ static int temporal_chain(ebvo_ctx *ctx, Slot &s, const ebvo_temporal_params &P,
             return rc;
     }
     if (n0 == 0)
-        return finish_empty();
+        return finish_empty(EBVO_TGT_SIFT);
     // 1. apply_SIFT_filtering_quads (:471-515): the smaller of the four descriptor distances of the left edges AND of the right
     // edges below the threshold; the distances become the quad's SIFT scores
     if ((rc = mate_descriptors(ctx, s, cfL, cfR, n_cf, cf_Ld, cf_Rd)) ||
@@ -3453,7 +3472,14 @@ static int temporal_chain(ebvo_ctx *ctx, Slot &s, const ebvo_temporal_params &P,
         return rc;
     counts->n_sift = n1;
     if (n1 == 0)
-        return finish_empty();
+        return finish_empty(EBVO_TGT_SIFT);
+    if (T.on)
+    {
+        int32_t *t_rp = (int32_t *)(base + o_trp), *t_cf = (int32_t *)(base + o_tcf);
+        EBVO_HIP(ctx, hipMemcpyAsync(t_rp, B.rp, sizeof(int32_t) * nk1, hipMemcpyDeviceToDevice, st));
+        EBVO_HIP(ctx, hipMemcpyAsync(t_cf, B.cf, sizeof(int32_t) * (size_t)n1, hipMemcpyDeviceToDevice, st));
+        trail_set(EBVO_TGT_SIFT, t_rp, t_cf, n1);
+    }
     // 2. apply_best_nearly_best_filtering_quads on the left NCC scores, then on the left SIFT scores (:517-570): rows of two or
     // more quads come out sorted by the score
     int32_t n2 = 0, n3 = 0;
@@ -3463,8 +3489,13 @@ static int temporal_chain(ebvo_ctx *ctx, Slot &s, const ebvo_temporal_params &P,
     if ((rc = glue_bnb_enqueue(ctx, s, A.rp, n_kf, A.siftL, P.bnb_sift, 0 | 2, cnt, order)) || (rc = compact(A, B, &n3, true)))
         return rc;
     counts->n_bnb_sift = n3;
+    if (T.on) // both lists stay where they are: nothing below writes set A, B's offsets or B's mates
+    {
+        trail_set(EBVO_TGT_BNB_NCC, A.rp, A.cf, n2);
+        trail_set(EBVO_TGT_BNB_SIFT, B.rp, B.cf, n3);
+    }
     if (n3 == 0)
-        return finish_empty();
+        return finish_empty(EBVO_TGT_BNB_SIFT);
     // 3. apply_photometric_refinement_quads (:572-634): both cameras of every quad, keyframe image against the current image
     // (undistorted), gradients of the current image; the quad's centres move where the refinement is valid
     const size_t n3z = (size_t)n3;
@@ -3534,6 +3565,13 @@ static int temporal_chain(ebvo_ctx *ctx, Slot &s, const ebvo_temporal_params &P,
     s.tq_final.sR = F.sR;
     s.tq_final.valid = F.valid;
     s.tq_final.n = n4;
+    if (T.on)
+    {
+        trail_set(EBVO_TGT_REFINE, B.rp, B.cf, n3);
+        T.cenL = cenL;
+        T.cenR = cenR;
+        T.lists = true;
+    }
     return EBVO_OK;
 }
 
@@ -3632,6 +3670,8 @@ extern "C" int ebvo_temporal_match_submit(ebvo_ctx *ctx, int slot, const ebvo_te
         return rc_f;
     s.tq_n = -1;
     s.tgt_armed = false; // the ground truth was given for the match that is replaced here
+    s.tq_trail = Slot::TqTrail();
+    s.tq_trail.on = s.tq_keep;
     s.tq_n_kf = ctx->kf_n;
     s.tq_kf_gen = ctx->kf_gen;
     s.tq_final = Slot::TqFinal();
@@ -3657,6 +3697,34 @@ extern "C" int ebvo_temporal_match_submit(ebvo_ctx *ctx, int slot, const ebvo_te
         return rc;
     }
     s.tq_in_flight = true;
+    return EBVO_OK;
+}
+
+// the chain did not run (no quads at all): every interior stage of a kept trail is an empty list over the zeroed offsets
+static void trail_all_empty(Slot &s, const int32_t *zero_rp)
+{
+    if (!s.tq_trail.on)
+        return;
+    for (int k = 0; k < 4; ++k)
+    {
+        s.tq_trail.rp[k] = zero_rp;
+        s.tq_trail.cf[k] = nullptr;
+        s.tq_trail.n[k] = 0;
+    }
+    s.tq_trail.lists = true;
+}
+
+extern "C" int ebvo_temporal_keep_stages(ebvo_ctx *ctx, int slot, int on)
+{
+    Slot *sp;
+    if (get_slot(ctx, slot, &sp))
+        return EBVO_ERR_ARG;
+    if (sp->tq_in_flight)
+    {
+        ctx->last_error = "a temporal match is in flight in the slot (ebvo_temporal_match_wait first)";
+        return EBVO_ERR_STATE;
+    }
+    sp->tq_keep = on != 0; // read by the next ebvo_temporal_match_submit; the slot's match and armed state stay
     return EBVO_OK;
 }
 
@@ -3692,6 +3760,7 @@ extern "C" int ebvo_temporal_match_wait(ebvo_ctx *ctx, int slot, ebvo_temporal_c
         {
             s.tq_final.rp = rp;
             s.tq_final.n = 0;
+            trail_all_empty(s, rp);
         }
         return EBVO_OK;
     }
@@ -3720,6 +3789,7 @@ extern "C" int ebvo_temporal_match_wait(ebvo_ctx *ctx, int slot, ebvo_temporal_c
         {
             s.tq_final.rp = rp; // the scanned counts: all zero
             s.tq_final.n = 0;
+            trail_all_empty(s, rp);
         }
         return EBVO_OK;
     }
@@ -4972,7 +5042,9 @@ static int tgt_armed_slot(ebvo_ctx *ctx, int slot, Slot **out)
     return EBVO_OK;
 }
 
-// the three stages the slot's match leaves behind: the position of their (n, tp) rows, totals and flag segments
+// the stages the slot's match leaves behind: the position of their (n, tp) rows and totals.  The three of every match come
+// first; a match that kept its trail (ebvo_temporal_keep_stages) adds the grid stage and, with stages = 1, the four interior
+// lists behind them.
 static int tgt_stage_pos(const Slot &s, int stage)
 {
     if (stage == EBVO_TGT_ORIENTATION)
@@ -4981,7 +5053,16 @@ static int tgt_stage_pos(const Slot &s, int stage)
         return 1;
     if (stage == EBVO_TGT_CLUSTER && s.tq_final.n >= 0)
         return 2;
+    if (stage == EBVO_TGT_GRID && s.tq_trail.on)
+        return 3;
+    if (stage >= EBVO_TGT_SIFT && stage <= EBVO_TGT_REFINE && s.tq_trail.on && s.tq_trail.lists)
+        return 4 + (stage - EBVO_TGT_SIFT);
     return -1;
+}
+
+static int tgt_positions(const Slot &s)
+{
+    return s.tq_trail.on ? 8 : 3;
 }
 
 // host prefix of the per-row counts (they come to the host for the sizes anyway); false: more quads than an int32 row offset holds
@@ -5033,20 +5114,37 @@ extern "C" int ebvo_temporal_set_gt(ebvo_ctx *ctx, int slot, const double R[9], 
     s.tgt_armed = false;
     const int n_kf = s.tq_n_kf, n_cf = s.n_final;
     const size_t nz = (size_t)n_kf, nq = (size_t)s.tq_n, nfin = (size_t)(s.tq_final.n > 0 ? s.tq_final.n : 0);
+    const Slot::TqTrail &T = s.tq_trail;
+    const size_t npos = (size_t)tgt_positions(s);
+    // flag segments: candidates, candidates (the NCC stage reads them through keep), final quads, then the trail's four lists
+    {
+        const int64_t n_of[EBVO_TGT_NUM_STAGES] = {0, (int64_t)nq, (int64_t)nq, T.n[0], T.n[1], T.n[2], T.n[3], (int64_t)nfin};
+        const int order[EBVO_TGT_NUM_STAGES] = {EBVO_TGT_ORIENTATION, EBVO_TGT_NCC, EBVO_TGT_CLUSTER, EBVO_TGT_GRID, EBVO_TGT_SIFT,
+                                                EBVO_TGT_BNB_NCC, EBVO_TGT_BNB_SIFT, EBVO_TGT_REFINE};
+        size_t run = 0;
+        for (int k : order)
+        {
+            s.tgt_flag_off[k] = run;
+            s.tgt_flag_n[k] = tgt_stage_pos(s, k) >= 0 ? n_of[k] : 0;
+            run += (size_t)s.tgt_flag_n[k];
+        }
+    }
+    const size_t n_flags = s.tgt_flag_off[EBVO_TGT_REFINE] + (size_t)s.tgt_flag_n[EBVO_TGT_REFINE];
     int rc;
     if ((rc = gt_grow(ctx, s, s.tgt_geom, sizeof(double) * 9 * nz + 64)) || (rc = gt_grow(ctx, s, s.tgt_u8, 3 * nz + 64)) ||
-        (rc = gt_grow(ctx, s, s.tgt_i32, sizeof(int32_t) * 2 * (nz + 1))) || (rc = gt_grow(ctx, s, s.tgt_rows, sizeof(int32_t) * 6 * nz + 64)) ||
-        (rc = gt_grow(ctx, s, s.tgt_flags, 2 * nq + nfin + 64)) || (rc = gt_grow(ctx, s, s.tgt_tot, sizeof(unsigned long long) * 8 * 3)))
+        (rc = gt_grow(ctx, s, s.tgt_i32, sizeof(int32_t) * 2 * (nz + 1))) ||
+        (rc = gt_grow(ctx, s, s.tgt_rows, sizeof(int32_t) * 2 * npos * nz + 64)) || (rc = gt_grow(ctx, s, s.tgt_flags, n_flags + 64)) ||
+        (rc = gt_grow(ctx, s, s.tgt_tot, sizeof(unsigned long long) * 8 * npos)))
         return rc;
     hipStream_t st = s.stream;
     double *pl = (double *)s.tgt_geom.p, *pr = pl + 2 * nz, *ol = pr + 2 * nz, *orr = ol + nz, *gamma = orr + nz;
     uint8_t *in = (uint8_t *)s.tgt_u8.p, *on = in + nz, *is_tp = on + nz;
     int32_t *cnt = (int32_t *)s.tgt_i32.p, *rp = cnt + nz + 1;
-    EBVO_HIP(ctx, hipMemsetAsync(s.tgt_tot.p, 0, sizeof(unsigned long long) * 8 * 3, st));
+    EBVO_HIP(ctx, hipMemsetAsync(s.tgt_tot.p, 0, sizeof(unsigned long long) * 8 * npos, st));
     EBVO_HIP(ctx, hipMemsetAsync(cnt, 0, sizeof(int32_t) * 2 * (nz + 1), st));
     if (nz)
     {
-        EBVO_HIP(ctx, hipMemsetAsync(s.tgt_rows.p, 0, sizeof(int32_t) * 6 * nz, st));
+        EBVO_HIP(ctx, hipMemsetAsync(s.tgt_rows.p, 0, sizeof(int32_t) * 2 * npos * nz, st));
         EBVO_HIP(ctx, hipMemsetAsync(in, 0, 3 * nz, st));
         if (kf_gamma)
             EBVO_HIP(ctx, hipMemcpyAsync(gamma, kf_gamma, sizeof(double) * 3 * nz, hipMemcpyHostToDevice, st));
@@ -5116,6 +5214,30 @@ extern "C" int ebvo_temporal_set_gt(ebvo_ctx *ctx, int slot, const double R[9], 
                 rc = gt_totals_enqueue(ctx, s, rows + 4 * nz, on, n_kf, tot + 16);
             if (rc)
                 return rc;
+        }
+        if (T.on)
+        {
+            // "Location Proximity" on the match's own grid and radius, then the trail's lists: mates by index, the last one
+            // by its refined centres
+            int pos = tgt_stage_pos(s, EBVO_TGT_GRID);
+            if ((rc = tgt_grid_rows_enqueue(ctx, s, ctx->kf_L, ctx->kf_R, n_kf, cfL, cfR, s.tq_cells.p, n_cf, cell,
+                                            tgt_cell_radius(s.tq_params.grid_radius, cell), gw, gh, on, pl, pr, P.tp_dist,
+                                            rows + 2 * nz * pos, tot + 8 * pos)))
+                return rc;
+            for (int k = EBVO_TGT_SIFT; k <= EBVO_TGT_REFINE && T.lists; ++k)
+            {
+                const int t = k - EBVO_TGT_SIFT;
+                pos = tgt_stage_pos(s, k);
+                const bool refined = k == EBVO_TGT_REFINE;
+                if (T.n[t] > 0)
+                    rc = tgt_rows_enqueue(ctx, s, T.rp[t], refined ? T.cenL : nullptr, refined ? T.cenR : nullptr, refined ? nullptr : T.cf[t],
+                                          cfL, cfR, nullptr, pl, pr, on, n_kf, T.n[t], P.tp_dist, rows + 2 * nz * pos,
+                                          flags + s.tgt_flag_off[k], tot + 8 * pos);
+                else
+                    rc = gt_totals_enqueue(ctx, s, rows + 2 * nz * pos, on, n_kf, tot + 8 * pos);
+                if (rc)
+                    return rc;
+            }
         }
         EBVO_HIP(ctx, hipStreamSynchronize(st));
     }
@@ -5192,11 +5314,12 @@ extern "C" int ebvo_temporal_gt_metrics(ebvo_ctx *ctx, int slot, ebvo_gt_stage *
     Slot &s = *sp;
     EBVO_HIP(ctx, hipSetDevice(ctx->device));
     const size_t nz = (size_t)s.tgt_n_kf;
-    std::vector<int32_t> rows(6 * nz + 1);
-    unsigned long long tot[24];
+    const size_t npos = (size_t)tgt_positions(s);
+    std::vector<int32_t> rows(2 * npos * nz + 1);
+    unsigned long long tot[8 * 8];
     if (nz)
-        EBVO_HIP(ctx, hipMemcpyAsync(rows.data(), s.tgt_rows.p, sizeof(int32_t) * 6 * nz, hipMemcpyDeviceToHost, s.stream));
-    EBVO_HIP(ctx, hipMemcpyAsync(tot, s.tgt_tot.p, sizeof tot, hipMemcpyDeviceToHost, s.stream));
+        EBVO_HIP(ctx, hipMemcpyAsync(rows.data(), s.tgt_rows.p, sizeof(int32_t) * 2 * npos * nz, hipMemcpyDeviceToHost, s.stream));
+    EBVO_HIP(ctx, hipMemcpyAsync(tot, s.tgt_tot.p, sizeof(unsigned long long) * 8 * npos, hipMemcpyDeviceToHost, s.stream));
     EBVO_HIP(ctx, hipStreamSynchronize(s.stream));
     for (int k = 0; k < EBVO_TGT_NUM_STAGES; ++k)
     {
@@ -5223,13 +5346,14 @@ extern "C" int ebvo_temporal_gt_flags(ebvo_ctx *ctx, int slot, int stage, uint8_
         return rc;
     Slot &s = *sp;
     const int pos = tgt_stage_pos(s, stage);
-    if (pos < 0)
+    if (pos < 0 || stage == EBVO_TGT_GRID)
     {
-        ctx->last_error = "the slot's match did not form this stage";
+        ctx->last_error = pos < 0 ? "the slot's match did not form this stage"
+                                  : "the grid stage keeps no list of quads (ebvo_temporal_gt_stage_rows has its per-row counts)";
         return EBVO_ERR_STATE;
     }
     EBVO_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t nq = (size_t)s.tq_n, nfin = (size_t)(s.tq_final.n > 0 ? s.tq_final.n : 0), n = pos == 2 ? nfin : nq;
+    const size_t n = (size_t)s.tgt_flag_n[stage];
     if (!n || !is_tp)
         return EBVO_OK;
     const bool walked = s.tgt_n_kf > 0 && s.n_final > 0 && !s.tq_empty;
@@ -5238,7 +5362,7 @@ extern "C" int ebvo_temporal_gt_flags(ebvo_ctx *ctx, int slot, int stage, uint8_
         memset(is_tp, 0, n);
         return EBVO_OK;
     }
-    const uint8_t *flags = (const uint8_t *)s.tgt_flags.p + (size_t)pos * nq;
+    const uint8_t *flags = (const uint8_t *)s.tgt_flags.p + s.tgt_flag_off[stage];
     if (stage != EBVO_TGT_NCC)
     {
         EBVO_HIP(ctx, hipMemcpyAsync(is_tp, flags, n, hipMemcpyDeviceToHost, s.stream));
@@ -5255,6 +5379,198 @@ extern "C" int ebvo_temporal_gt_flags(ebvo_ctx *ctx, int slot, int stage, uint8_
     for (size_t k = 0; k < n; ++k)
         if (keep[k])
             is_tp[o++] = f[k];
+    return EBVO_OK;
+}
+
+extern "C" int ebvo_temporal_gt_stage_rows(ebvo_ctx *ctx, int slot, int stage, int32_t *rows_n_tp, int32_t cap_rows)
+{
+    Slot *sp;
+    if (!rows_n_tp || stage < 0 || stage >= EBVO_TGT_NUM_STAGES || cap_rows < 0)
+        return EBVO_ERR_ARG;
+    if (int rc = tgt_armed_slot(ctx, slot, &sp))
+        return rc;
+    Slot &s = *sp;
+    const int pos = tgt_stage_pos(s, stage);
+    if (pos < 0)
+    {
+        ctx->last_error = "the slot's match did not form this stage";
+        return EBVO_ERR_STATE;
+    }
+    if (cap_rows < s.tgt_n_kf)
+    {
+        ctx->last_error = "ebvo_temporal_gt_stage_rows: the slot has " + std::to_string(s.tgt_n_kf) + " keyframe mates";
+        return EBVO_ERR_CAPACITY;
+    }
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nz = (size_t)s.tgt_n_kf;
+    if (!nz)
+        return EBVO_OK;
+    EBVO_HIP(ctx, hipMemcpyAsync(rows_n_tp, (const int32_t *)s.tgt_rows.p + 2 * nz * (size_t)pos, sizeof(int32_t) * 2 * nz,
+                                 hipMemcpyDeviceToHost, s.stream));
+    EBVO_HIP(ctx, hipStreamSynchronize(s.stream));
+    return EBVO_OK;
+}
+
+// the interior stage of a match that kept its trail: 0 .. 3, or a negative status with the last error set
+static int tgt_trail_stage(ebvo_ctx *ctx, int slot, int stage, Slot **out)
+{
+    if (stage < EBVO_TGT_SIFT || stage > EBVO_TGT_REFINE)
+    {
+        if (ctx)
+            ctx->last_error = stage == EBVO_TGT_ORIENTATION || stage == EBVO_TGT_NCC
+                                  ? "this stage's list is what ebvo_temporal_fetch returns (the NCC stage: its quads with keep)"
+                              : stage == EBVO_TGT_CLUSTER ? "this stage's list is what ebvo_temporal_fetch_final returns"
+                              : stage == EBVO_TGT_GRID
+                                  ? "the grid stage keeps no list of quads (ebvo_temporal_gt_stage_rows has its per-row counts)"
+                                  : "no such stage";
+        return EBVO_ERR_ARG;
+    }
+    if (!ctx)
+        return EBVO_ERR_ARG;
+    if (int rc = tgt_matched_slot(ctx, slot, out))
+        return rc;
+    if (!(*out)->tq_trail.on || !(*out)->tq_trail.lists)
+    {
+        ctx->last_error = "the slot's match kept no stage trail (ebvo_temporal_keep_stages, then a match with stages = 1)";
+        return EBVO_ERR_STATE;
+    }
+    return stage - EBVO_TGT_SIFT;
+}
+
+extern "C" int ebvo_temporal_stage_size(ebvo_ctx *ctx, int slot, int stage, int64_t *n)
+{
+    Slot *sp;
+    const int t = tgt_trail_stage(ctx, slot, stage, &sp);
+    if (t < 0)
+        return t;
+    if (n)
+        *n = sp->tq_trail.n[t];
+    return EBVO_OK;
+}
+
+extern "C" int ebvo_temporal_fetch_stage(ebvo_ctx *ctx, int slot, int stage, int32_t *row_ptr, int32_t *cf_index, ebvo_edge *left,
+                                         ebvo_edge *right)
+{
+    Slot *sp;
+    const int t = tgt_trail_stage(ctx, slot, stage, &sp);
+    if (t < 0)
+        return t;
+    Slot &s = *sp;
+    const Slot::TqTrail &T = s.tq_trail;
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = s.stream;
+    const size_t n = (size_t)T.n[t], ncz = (size_t)s.n_final;
+    if (row_ptr)
+        EBVO_HIP(ctx, hipMemcpyAsync(row_ptr, T.rp[t], sizeof(int32_t) * ((size_t)s.tq_n_kf + 1), hipMemcpyDeviceToHost, st));
+    std::vector<int32_t> cf(n);
+    std::vector<ebvo_edge> mates[2];
+    const bool refined = stage == EBVO_TGT_REFINE, gather = !refined && (left || right);
+    if (n)
+    {
+        EBVO_HIP(ctx, hipMemcpyAsync(cf.data(), T.cf[t], sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+        if (refined)
+        {
+            if (left)
+                EBVO_HIP(ctx, hipMemcpyAsync(left, T.cenL, sizeof(ebvo_edge) * n, hipMemcpyDeviceToHost, st));
+            if (right)
+                EBVO_HIP(ctx, hipMemcpyAsync(right, T.cenR, sizeof(ebvo_edge) * n, hipMemcpyDeviceToHost, st));
+        }
+        else if (gather)
+        {
+            // before the refinement the centres of a quad are its current-frame mate's edges
+            const ebvo_edge *cfL, *cfR;
+            final_mates(s, &cfL, &cfR);
+            mates[0].resize(ncz);
+            mates[1].resize(ncz);
+            EBVO_HIP(ctx, hipMemcpyAsync(mates[0].data(), cfL, sizeof(ebvo_edge) * ncz, hipMemcpyDeviceToHost, st));
+            EBVO_HIP(ctx, hipMemcpyAsync(mates[1].data(), cfR, sizeof(ebvo_edge) * ncz, hipMemcpyDeviceToHost, st));
+        }
+    }
+    EBVO_HIP(ctx, hipStreamSynchronize(st));
+    for (size_t k = 0; k < n; ++k)
+    {
+        if (cf_index)
+            cf_index[k] = cf[k];
+        if (gather && left)
+            left[k] = mates[0][(size_t)cf[k]];
+        if (gather && right)
+            right[k] = mates[1][(size_t)cf[k]];
+    }
+    return EBVO_OK;
+}
+
+extern "C" int ebvo_tgt_grid_rows(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *kf_right, int n_kf, const ebvo_edge *cf_left,
+                                  const ebvo_edge *cf_right, int n_cf, int img_w, int img_h, int cell_size, double grid_radius,
+                                  const uint8_t *row_on, const double *proj_left, const double *proj_right, double tp_dist,
+                                  int32_t *n_tp, ebvo_gt_stage *stage_out)
+{
+    if (!ctx || !stage_out || n_kf < 0 || n_cf < 0 || img_w < 1 || img_h < 1 || cell_size < 1 ||
+        !(grid_radius >= 0 && std::isfinite(grid_radius)) || !(tp_dist >= 0) ||
+        (n_kf > 0 && (!kf_left || !kf_right || !proj_left || !proj_right)) || (n_cf > 0 && (!cf_left || !cf_right)))
+        return EBVO_ERR_ARG;
+    const int64_t gw64 = ((int64_t)img_w + cell_size - 1) / cell_size, gh64 = ((int64_t)img_h + cell_size - 1) / cell_size;
+    if (gw64 * gh64 > (1 << 26) || gw64 > 30000 || gh64 > 30000) // the cells of a mate are 16-bit
+        return EBVO_ERR_ARG;
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    int rc;
+    Slot *sp;
+    if ((rc = gt_host_slot(ctx, &sp)))
+        return rc;
+    Slot &s = *sp;
+    memset(stage_out, 0, sizeof *stage_out);
+    stage_out->stage = EBVO_TGT_GRID;
+    stage_out->present = 1;
+    const int gw = (int)gw64, gh = (int)gh64;
+    const size_t nz = (size_t)n_kf, ncz = (size_t)n_cf;
+    // one buffer of the call's own: the four mate lists, both projections, the totals, the (n, tp) rows, row_on, the grid
+    const size_t o_kfR = sizeof(ebvo_edge) * nz, o_cfL = 2 * sizeof(ebvo_edge) * nz, o_cfR = o_cfL + sizeof(ebvo_edge) * ncz,
+                 o_pl = o_cfR + sizeof(ebvo_edge) * ncz, o_pr = o_pl + sizeof(double) * 2 * nz, o_tot = o_pr + sizeof(double) * 2 * nz,
+                 o_rows = o_tot + sizeof(unsigned long long) * 8, o_on = o_rows + sizeof(int32_t) * 2 * (nz + 1),
+                 o_grid = (o_on + nz + 63) & ~(size_t)63, total = o_grid + match_temporal_grid_bytes(n_cf, gw * gh) + 64;
+    if ((rc = gt_grow(ctx, s, s.tgt_up, total)))
+        return rc;
+    hipStream_t st = s.stream;
+    char *base = (char *)s.tgt_up.p;
+    ebvo_edge *kfL = (ebvo_edge *)base, *kfR = (ebvo_edge *)(base + o_kfR), *cfL = (ebvo_edge *)(base + o_cfL), *cfR = (ebvo_edge *)(base + o_cfR);
+    double *pl = (double *)(base + o_pl), *pr = (double *)(base + o_pr);
+    unsigned long long *d_tot = (unsigned long long *)(base + o_tot);
+    int32_t *d_rows = (int32_t *)(base + o_rows);
+    uint8_t *on = (uint8_t *)(base + o_on);
+    EBVO_HIP(ctx, hipMemsetAsync(d_tot, 0, sizeof(unsigned long long) * 8, st));
+    if (n_kf)
+    {
+        EBVO_HIP(ctx, hipMemcpyAsync(kfL, kf_left, sizeof(ebvo_edge) * nz, hipMemcpyHostToDevice, st));
+        EBVO_HIP(ctx, hipMemcpyAsync(kfR, kf_right, sizeof(ebvo_edge) * nz, hipMemcpyHostToDevice, st));
+        EBVO_HIP(ctx, hipMemcpyAsync(pl, proj_left, sizeof(double) * 2 * nz, hipMemcpyHostToDevice, st));
+        EBVO_HIP(ctx, hipMemcpyAsync(pr, proj_right, sizeof(double) * 2 * nz, hipMemcpyHostToDevice, st));
+        if (row_on)
+            EBVO_HIP(ctx, hipMemcpyAsync(on, row_on, nz, hipMemcpyHostToDevice, st));
+        else
+            EBVO_HIP(ctx, hipMemsetAsync(on, 1, nz, st));
+        EBVO_HIP(ctx, hipMemsetAsync(d_rows, 0, sizeof(int32_t) * 2 * nz, st));
+    }
+    if (n_kf > 0 && n_cf > 0)
+    {
+        EBVO_HIP(ctx, hipMemcpyAsync(cfL, cf_left, sizeof(ebvo_edge) * ncz, hipMemcpyHostToDevice, st));
+        EBVO_HIP(ctx, hipMemcpyAsync(cfR, cf_right, sizeof(ebvo_edge) * ncz, hipMemcpyHostToDevice, st));
+        if ((rc = match_temporal_cells_enqueue(ctx, s, cfL, cfR, n_cf, cell_size, gw, gh, base + o_grid)) ||
+            (rc = tgt_grid_rows_enqueue(ctx, s, kfL, kfR, n_kf, cfL, cfR, base + o_grid, n_cf, cell_size, tgt_cell_radius(grid_radius, cell_size),
+                                        gw, gh, on, pl, pr, tp_dist, d_rows, d_tot)))
+            return rc;
+    }
+    else if ((rc = gt_totals_enqueue(ctx, s, d_rows, on, n_kf, d_tot))) // no current-frame mates: the rows that are on are empty
+        return rc;
+    std::vector<int32_t> rows(2 * nz + 1);
+    unsigned long long tot[5] = {0, 0, 0, 0, 0};
+    if (n_kf)
+        EBVO_HIP(ctx, hipMemcpyAsync(rows.data(), d_rows, sizeof(int32_t) * 2 * nz, hipMemcpyDeviceToHost, st));
+    EBVO_HIP(ctx, hipMemcpyAsync(tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, st));
+    EBVO_HIP(ctx, hipStreamSynchronize(st));
+    tgt_stage_doubles(rows.data(), row_on, n_kf, stage_out);
+    if ((rc = tgt_totals_agree(ctx, *stage_out, tot)))
+        return rc;
+    if (n_tp && n_kf)
+        memcpy(n_tp, rows.data(), sizeof(int32_t) * 2 * nz);
     return EBVO_OK;
 }
 

@@ -40,6 +40,7 @@ enum KernelId
     K_TGT_VERIDICAL, // tgt_veridical<count> and <fill>
     K_TGT_ROWS,      // tgt_rows
     K_POSE_CASCADE,  // pose_cascade (the constraint cascade; the other pose kernels run under K_MISC)
+    K_TGT_GRID,      // tgt_grid_rows
     K_NUM
 };
 static_assert(K_NUM <= EBVO_MAX_KERNELS, "grow EBVO_MAX_KERNELS");
@@ -193,6 +194,8 @@ struct Slot
     int32_t tgt_n_rows = 0;      // keyframe mates with a veridical quad
     int64_t tgt_n_ver = 0;       // veridical quads
     std::vector<uint8_t> tgt_h_on; // host copy of row_on[]: a veridical quad and kf_is_tp
+    size_t tgt_flag_off[EBVO_TGT_NUM_STAGES] = {0}; // where a stage's flag segment starts in tgt_flags, and its quads
+    int64_t tgt_flag_n[EBVO_TGT_NUM_STAGES] = {0};
     bool sift_left_valid = false;                      // sift_desc holds the descriptors of every left TOED edge of this pair
     struct TqFinal                                     // the quads that leave the chain (pointers into tq_chain)
     {
@@ -202,6 +205,17 @@ struct Slot
         uint8_t *valid = nullptr;
         int64_t n = -1;
     } tq_final;
+    // ebvo_temporal_keep_stages: what the match leaves of its interior stages.  Pointers into tq_chain (or, for a list that
+    // is empty, any run of n_kf + 1 zeroed row offsets); k = stage - EBVO_TGT_SIFT
+    struct TqTrail
+    {
+        bool on = false;    // the match was submitted with the switch on
+        bool lists = false; // ... and with stages = 1: the four lists below are set
+        const int32_t *rp[4] = {nullptr, nullptr, nullptr, nullptr}, *cf[4] = {nullptr, nullptr, nullptr, nullptr};
+        const ebvo_edge *cenL = nullptr, *cenR = nullptr; // the refined centres of the last list
+        int64_t n[4] = {0, 0, 0, 0};
+    } tq_trail;
+    bool tq_keep = false; // the switch: read by the next ebvo_temporal_match_submit
     int tq_n_kf = 0;
     int64_t tq_n = -1;                       // -1: none
     // ebvo_temporal_match_submit / _wait: the candidate and NCC stages are enqueued for a capacity of quads (what the last
@@ -631,6 +645,10 @@ int tgt_veridical_enqueue(ebvo_ctx *ctx, Slot &s, int n_kf, const uint8_t *d_in,
                           int32_t *d_cnt, const int32_t *d_row_ptr, int32_t *d_idx, int64_t cap, uint8_t *d_on);
 // (n, tp) per row of a CSR list of quads (centres d_cenL[k] / d_cenR[k], or d_cfL / d_cfR [d_col_idx[k]]; d_keep optional),
 // the per-quad b_is_TP byte (0 for a quad outside the list or on a row that is off) and the five integer totals
+// the grid stage ("Location Proximity") without its list: (n, tp) of every keyframe mate whose row is on, and the stage totals
+int tgt_grid_rows_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, int n_kf, const ebvo_edge *d_cfL,
+                          const ebvo_edge *d_cfR, const void *d_grid, int n_cf, int cell, int sr, int gw, int gh, const uint8_t *d_on,
+                          const double *d_pl, const double *d_pr, double tp_dist, int32_t *d_rows, unsigned long long *d_tot);
 int tgt_rows_enqueue(ebvo_ctx *ctx, Slot &s, const int32_t *d_row_ptr, const ebvo_edge *d_cenL, const ebvo_edge *d_cenR,
                      const int32_t *d_col_idx, const ebvo_edge *d_cfL, const ebvo_edge *d_cfR, const uint8_t *d_keep,
                      const double *d_pl, const double *d_pr, const uint8_t *d_on, int n_kf, int64_t n_quads, double tp_dist,

@@ -9,7 +9,9 @@
 // tgt_project: one thread per keyframe mate.  tgt_veridical: sixteen lanes per keyframe mate walk the grid cells of the
 // current-frame mates that match_kernels.hip builds (the layout and the order of temporal_candidates_kernel: dy outer, dx
 // inner, ascending mate index within a cell; a ballot ranks the survivors of a step).  tgt_rows: eight lanes per row of a
-// CSR list of quads.  No floating-point value is accumulated on the device: the kernels produce integer (n, tp) per row
+// CSR list of quads.  tgt_grid_rows: the grid stage of the chain (apply_spatial_grid_filtering_quads, :335-383), which
+// temporal_candidates_kernel fuses with the orientation test and so never lists, counted and evaluated per keyframe mate
+// with the same sixteen-lane walk.  No floating-point value is accumulated on the device: the kernels produce integer (n, tp) per row
 // and a byte per quad, the stage totals are gt_totals' integer atomics, and the four doubles of a stage are summed on the
 // host in keyframe index order (ebvo_capi.hip: tgt_stage_doubles).
 //
@@ -227,6 +229,70 @@ __global__ __launch_bounds__(256) void tgt_rows_kernel(const int32_t *__restrict
     }
 }
 
+// "Location Proximity": the output of apply_spatial_grid_filtering_quads (src/Temporal_Matches.cpp:335-383) evaluated by
+// :242-257 without forming it.  The walk is temporal_candidates_kernel's (match_kernels.hip) less its orientation test:
+// sixteen lanes per keyframe mate, the query cells of the mate's own edges (not clipped), the neighbours inside the grid,
+// a current-frame mate counted when its right cell is in the right grid and within sr cells of the right query cell.
+// Every counted mate is a quad of the row; it is a true positive when both its edges lie < tp_dist from the row's
+// projections.  A row that is off walks nothing and writes (0, 0).
+__global__ __launch_bounds__(256) void tgt_grid_rows_kernel(const ebvo_edge *__restrict__ kfL, const ebvo_edge *__restrict__ kfR,
+                                                            int n_kf, const ebvo_edge *__restrict__ cfL,
+                                                            const ebvo_edge *__restrict__ cfR, const MateCells *__restrict__ cells,
+                                                            const int32_t *__restrict__ cell_start,
+                                                            const int32_t *__restrict__ cell_list, int cell, int sr, int gw, int gh,
+                                                            const uint8_t *__restrict__ on, const double *__restrict__ pl,
+                                                            const double *__restrict__ pr, double tp_dist, int32_t *__restrict__ out)
+{
+    const int lane = threadIdx.x & 63, e = lane & 15, gshift = lane & 48;
+    const int groups = (gridDim.x * blockDim.x) >> 4;
+    // the four groups of a wave advance together (the ballots below are wave-wide): a group past the end, or of a row that
+    // is off, walks nothing
+    for (int w0 = ((blockIdx.x * blockDim.x + threadIdx.x) >> 6) * 4; w0 < n_kf; w0 += groups)
+    {
+        const int i0 = w0 + (lane >> 4);
+        const bool have = i0 < n_kf;
+        const int i = have ? i0 : 0;
+        const bool live = have && on[i] != 0;
+        const ebvo_edge kl = kfL[i], kr = kfR[i];
+        const double plx = pl[(size_t)i * 2], ply = pl[(size_t)i * 2 + 1], prx = pr[(size_t)i * 2], pry = pr[(size_t)i * 2 + 1];
+        const int qlx = (int)kl.x / cell, qly = (int)kl.y / cell, qrx = (int)kr.x / cell, qry = (int)kr.y / cell;
+        const int dy0 = max(-sr, -qly), dy1 = live ? min(sr, gh - 1 - qly) : dy0 - 1;
+        const int dx0 = max(-sr, -qlx), dx1 = min(sr, gw - 1 - qlx);
+        int n = 0, tp = 0;
+        for (int dy = dy0; dy <= dy1; ++dy)
+            for (int dx = dx0; dx <= dx1; ++dx)
+            {
+                const int ny = qly + dy, nx = qlx + dx;
+                const bool in_grid = live && ny >= 0 && ny < gh && nx >= 0 && nx < gw;
+                const int a = in_grid ? cell_start[ny * gw + nx] : 0, b = in_grid ? cell_start[ny * gw + nx + 1] : 0;
+                for (int k0 = a; __any(k0 < b); k0 += 16)
+                {
+                    const int k = k0 + e;
+                    bool in = false, hit = false;
+                    if (k < b)
+                    {
+                        const int j = cell_list[k];
+                        const MateCells m = cells[j];
+                        in = m.rx >= 0 && abs(m.rx - qrx) <= sr && abs(m.ry - qry) <= sr; // right_set.count(cf_idx), :357
+                        if (in)
+                        {
+                            const ebvo_edge l = cfL[j], r = cfR[j];
+                            const double dxl = l.x - plx, dyl = l.y - ply, dxr = r.x - prx, dyr = r.y - pry;
+                            hit = sqrt(dxl * dxl + dyl * dyl) < tp_dist && sqrt(dxr * dxr + dyr * dyr) < tp_dist; // :246-248, strict
+                        }
+                    }
+                    n += __popcll((__ballot(in) >> gshift) & 0xffffull);
+                    tp += __popcll((__ballot(hit) >> gshift) & 0xffffull);
+                }
+            }
+        if (have && e == 0)
+        {
+            out[(size_t)i * 2] = n;
+            out[(size_t)i * 2 + 1] = tp;
+        }
+    }
+}
+
 int tgt_grid(const ebvo_ctx *ctx, int64_t items, int per_block)
 {
     int64_t g = (items + per_block - 1) / per_block;
@@ -286,6 +352,23 @@ int tgt_veridical_enqueue(ebvo_ctx *ctx, Slot &s, int n_kf, const uint8_t *d_in,
         hipLaunchKernelGGL(tgt_veridical_kernel<false>, grid, dim3(256), 0, s.stream, A, d_cnt, d_row_ptr, d_idx, cap, d_on);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
+}
+
+int tgt_grid_rows_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, int n_kf, const ebvo_edge *d_cfL,
+                          const ebvo_edge *d_cfR, const void *d_grid, int n_cf, int cell, int sr, int gw, int gh, const uint8_t *d_on,
+                          const double *d_pl, const double *d_pr, double tp_dist, int32_t *d_rows, unsigned long long *d_tot)
+{
+    if (n_kf > 0)
+    {
+        const MateCells *cells;
+        const int32_t *cell_start, *cell_list;
+        match_temporal_grid_view(d_grid, n_cf, gw * gh, &cells, &cell_start, &cell_list);
+        ProfScope ps(ctx, s, K_TGT_GRID);
+        hipLaunchKernelGGL(tgt_grid_rows_kernel, dim3(tgt_grid(ctx, n_kf, 16)), dim3(256), 0, s.stream, d_kfL, d_kfR, n_kf, d_cfL, d_cfR,
+                           cells, cell_start, cell_list, cell, sr, gw, gh, d_on, d_pl, d_pr, tp_dist, d_rows);
+        EBVO_HIP(ctx, hipGetLastError());
+    }
+    return gt_totals_enqueue(ctx, s, d_rows, d_on, n_kf, d_tot);
 }
 
 int tgt_rows_enqueue(ebvo_ctx *ctx, Slot &s, const int32_t *d_row_ptr, const ebvo_edge *d_cenL, const ebvo_edge *d_cenR,

@@ -1018,9 +1018,21 @@ inline CameraPose relative_pose(const CameraPose &source, const CameraPose &targ
     return rel;
 }
 
+// The slot's NEXT temporal match keeps (on) or drops (off) its stage trail (ebvo_temporal_keep_stages): with it, evaluate()
+// below returns every stage of get_Temporal_Edge_Pairs_from_Quads.  The match's own results are the same either way.
+inline int temporal_keep_stages(const Context &c, int slot, bool on)
+{
+    const int rc = ebvo_temporal_keep_stages(c.get(), slot, on ? 1 : 0);
+    if (rc != EBVO_OK)
+        report(c, rc, "ebvo_temporal_keep_stages");
+    return rc;
+}
+
 // build_Veridical_Quads + Evaluate_Temporal_Edge_Pairs_on_Quads (src/Temporal_Matches.cpp:57-166, :220-292) on the temporal
 // match of `slot`: arms it with the relative pose of the two GT camera poses (keyframe, current frame) and returns the
-// stages the match formed ("Orientation", "NCC", and "Edge Clustering" after stages = 1) under the reference's names.
+// stages the match formed under the reference's names, in its order: "Orientation", "NCC", and "Edge Clustering" after
+// stages = 1; a match made after temporal_keep_stages(c, slot, true) also gives "Location Proximity" and, after stages = 1,
+// "SIFT", "BNB-NCC", "BNB-SIFT" and "Photometric Refinement" -- the reference's eight.
 // kf_gamma (n_kf x 3) / kf_is_tp (n_kf): the keyframe mates' GT 3-D points and b_is_TP, or nullptr (ebvo_hip.h).
 inline FrameEvaluationMetrics evaluate(const Context &c, int slot, const CameraPose &keyframe_gt_pose, const CameraPose &current_gt_pose,
                                        const ebvo_stereo_calib &calib, const ebvo_tgt_params *params = nullptr,

@@ -852,13 +852,38 @@ int ebvo_temporal_gt_size(ebvo_ctx *ctx, int slot, int32_t *n_kf, int32_t *n_row
  * indices).  Any pointer may be NULL. */
 int ebvo_temporal_gt_fetch(ebvo_ctx *ctx, int slot, uint8_t *in_image, double *proj_left, double *proj_right,
                            double *orient_left, double *orient_right, int32_t *ver_row_ptr, int32_t *ver_idx);
-/* stages[EBVO_TGT_NUM_STAGES], indexed by stage id: ORIENTATION, NCC and (after stages = 1) CLUSTER are filled, every other
- * stage has present = 0.  Returns the stage count (> 0) or a negative status. */
+/* stages[EBVO_TGT_NUM_STAGES], indexed by stage id: ORIENTATION, NCC and (after stages = 1) CLUSTER are filled for every
+ * match; a match that kept its stage trail (ebvo_temporal_keep_stages below) fills GRID as well and, after stages = 1, SIFT,
+ * BNB_NCC, BNB_SIFT and REFINE: all eight.  Every other stage has present = 0.  Returns the stage count (> 0) or a negative
+ * status. */
 int ebvo_temporal_gt_metrics(ebvo_ctx *ctx, int slot, ebvo_gt_stage *stages);
 /* per-quad b_is_TP of a present stage in that stage's CSR order (ORIENTATION: ebvo_temporal_fetch's candidates; NCC: those
- * with keep; CLUSTER: ebvo_temporal_fetch_final's quads); 0 on rows outside the evaluation.  What
- * Quad_for_Pose_Solution::b_is_veridical reads.  A stage that is not present: EBVO_ERR_STATE. */
+ * with keep; SIFT, BNB_NCC, BNB_SIFT, REFINE: ebvo_temporal_fetch_stage's quads; CLUSTER: ebvo_temporal_fetch_final's quads);
+ * 0 on rows outside the evaluation.  What Quad_for_Pose_Solution::b_is_veridical reads.  A stage that is not present, and
+ * GRID, which keeps no list of quads: EBVO_ERR_STATE. */
 int ebvo_temporal_gt_flags(ebvo_ctx *ctx, int slot, int stage, uint8_t *is_tp);
+/* per-row (n, tp) of a present stage of the armed slot: rows_n_tp [n_kf][2], zero on rows outside the evaluation.  cap_rows:
+ * the rows the caller's array holds; fewer than the slot's keyframe mates: EBVO_ERR_CAPACITY, nothing written. */
+int ebvo_temporal_gt_stage_rows(ebvo_ctx *ctx, int slot, int stage, int32_t *rows_n_tp, int32_t cap_rows);
+
+/* The stage trail.  ebvo_temporal_keep_stages sets a per-slot switch (default 0) that the NEXT ebvo_temporal_match /
+ * _submit of the slot reads; the slot's present match and armed state are not touched (EBVO_ERR_STATE while a match of the
+ * slot is in flight).  A match submitted with the switch on leaves, besides its own results (which are the same bits either
+ * way), what the ground-truth evaluation of the remaining stages needs: with stages = 1 the lists after the SIFT filter,
+ * after either best-nearly-best test and after the refinement -- one device-to-device copy of the SIFT-stage list, the
+ * others stay where the chain left them -- and the grid stage is counted by ebvo_temporal_set_gt on the match's own grid
+ * without forming its list (about ten quads per candidate).  A stage the chain did not reach because an earlier one left
+ * nothing is an empty list.  A new match, upload, run or finalisation of the slot drops the trail.
+ * ebvo_temporal_stage_size / ebvo_temporal_fetch_stage: stage = EBVO_TGT_SIFT, _BNB_NCC, _BNB_SIFT or _REFINE (any other:
+ * EBVO_ERR_ARG, the last error names the call that returns that stage's list) of a match that kept its trail with stages = 1
+ * (otherwise EBVO_ERR_STATE); no ground truth is needed.  row_ptr [n_kf + 1] over the keyframe mates in the chain's own
+ * order (the best-nearly-best tests sort a row by score), cf_index [n] the current-frame mate of every quad, left / right
+ * [n] the centres the evaluation reads: the mate's edges before REFINE, the refined centres at REFINE.  Any pointer may be
+ * NULL. */
+int ebvo_temporal_keep_stages(ebvo_ctx *ctx, int slot, int on);
+int ebvo_temporal_stage_size(ebvo_ctx *ctx, int slot, int stage, int64_t *n);
+int ebvo_temporal_fetch_stage(ebvo_ctx *ctx, int slot, int stage, int32_t *row_ptr, int32_t *cf_index, ebvo_edge *left,
+                              ebvo_edge *right);
 /* The kernels behind it on host arrays, on slot 0's stream (EBVO_ERR_STATE while work of slot 0 is in flight) with buffers
  * of their own: slot 0's results and armed state are not touched.  ebvo_tgt_veridical: keyframe mates (kf_gamma may be
  * NULL) and current-frame mates in, the arrays of ebvo_temporal_gt_fetch out (any may be NULL); the grid of the
@@ -873,6 +898,15 @@ int ebvo_tgt_veridical(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge 
 int ebvo_tgt_evaluate_rows(ebvo_ctx *ctx, const int32_t *row_ptr, const ebvo_edge *left_centres, const ebvo_edge *right_centres,
                            int n_kf, const uint8_t *row_on, const double *proj_left, const double *proj_right, double tp_dist,
                            int32_t *n_tp, uint8_t *is_tp, ebvo_gt_stage *stage_out);
+/* The grid stage ("Location Proximity") on host arrays, under the same rules: per keyframe mate whose row is on (row_on
+ * NULL: all) the current-frame mates that apply_spatial_grid_filtering_quads (src/Temporal_Matches.cpp:335-383) pairs with
+ * it -- in the grid cells within ceil(grid_radius / cell_size) cells of the mate's own left AND right cell -- are counted,
+ * and those with both edges < tp_dist from the row's projections are the true positives; no list is formed.  n_tp
+ * [n_kf][2] (may be NULL) and the stage record.  cell_size >= 1; grid_radius finite and >= 0; tp_dist >= 0 and not NaN. */
+int ebvo_tgt_grid_rows(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *kf_right, int n_kf, const ebvo_edge *cf_left,
+                       const ebvo_edge *cf_right, int n_cf, int img_w, int img_h, int cell_size, double grid_radius,
+                       const uint8_t *row_on, const double *proj_left, const double *proj_right, double tp_dist, int32_t *n_tp,
+                       ebvo_gt_stage *stage_out);
 
 /* ---------------------------------------------------------------------------------------- */
 /* Device-resident stereo pipeline: TOED(left) + TOED(right) + candidates + NCC of one pair,  */

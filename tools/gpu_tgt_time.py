@@ -1,8 +1,10 @@
 """What the temporal ground truth costs on the half-scale EuRoC pair of the temporal tests (240 x 376, keyframe 0 against
 frame 2, stages = 1): host wall milliseconds per ebvo_temporal_set_gt (projection, veridical count and fill, the rows of
 three stages; synchronous) and per ebvo_temporal_gt_metrics, mean of 10, next to ebvo_temporal_match for scale, and the
-device time per launch of the three kernels from the library's profiler.  The measurement is a child process under its own
-time limit; a child that fails ends the run.  Prints one JSON line."""
+device time per launch of the three kernels from the library's profiler.  Then the same with the stage trail kept
+(ebvo_temporal_keep_stages): the match with the switch on, ebvo_temporal_set_gt over eight stages instead of three, and the
+device time of tgt_grid_rows.  The measurement is a child process under its own time limit; a child that fails ends the
+run.  Prints one JSON line."""
 import json
 import os
 import subprocess
@@ -61,6 +63,25 @@ def child():
         prof = ctx.profile_get()
         out["kernel_us_per_launch"] = {k: round(prof[k][0] / prof[k][1] * 1e3, 1) for k in
                                        ("tgt_project", "tgt_veridical", "tgt_rows", "gt_misc") if prof[k][1]}
+        # the same slot with the stage trail kept: eight stages
+        ctx.temporal_keep_stages(True)
+        ms_match_on, (counts_on, _) = timed(lambda: ctx.temporal_match(stages=1, fetch=False), 10)
+        ms_arm8, _ = timed(lambda: ctx.temporal_set_gt(R, t, calib), 10)
+        ms_metrics8, m8 = timed(ctx.temporal_gt_metrics, 10)
+        assert counts_on == counts and sum(s["present"] for s in m8) == 8
+        out.update(temporal_match_trail_ms=ms_match_on, set_gt_8_ms=ms_arm8, gt_metrics_8_ms=ms_metrics8)
+        out["stages_8"] = {s["name"]: dict(sum_n=s["sum_n"], sum_tp=s["sum_tp"], recall=round(s["recall"], 4)) for s in m8}
+        ctx.profile_reset()
+        ctx.profile_enable(True)
+        for _ in range(10):
+            ctx.temporal_set_gt(R, t, calib)
+        ctx.profile_enable(False)
+        prof = ctx.profile_get()
+        out["kernel_us_per_launch_8"] = {k: round(prof[k][0] / prof[k][1] * 1e3, 1) for k in
+                                         ("tgt_grid_rows", "tgt_rows", "gt_misc") if prof[k][1]}
+        ctx.temporal_keep_stages(False)
+        ms_match_off, _ = timed(lambda: ctx.temporal_match(stages=1, fetch=False), 10)    # off again, after on: the order
+        out["temporal_match_again_ms"] = ms_match_off
     print(json.dumps(out))
 
 
