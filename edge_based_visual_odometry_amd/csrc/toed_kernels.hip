@@ -23,11 +23,12 @@
 //   toed_finalize_kernel K3c: dense per-edge epilogue (sub-pixel position, atan2, records)
 // Hybrid mode (second half of the file; same bits out):
 //   toed_screen_fused_kernel   S1+S2: separable fp32 screen and relaxed NMS of a 12 x 30-pixel tile, all in LDS
-//   toed_compact_phase_kernel (offsets of a row: the counts of the rows in front of it, summed by the row's own block)
-//                              S2b/c: candidate ranks and the four phase lists, ordered, no atomics
+//   toed_compact_phase_kernel (offsets of a row: the counts of the rows in front of it, summed by the row's own wave)
+//                              S2b/c: candidate ranks and the four phase lists, ordered, no atomics; one wave per grid row,
+//                              eight flag bytes per lane, no LDS
 //   toed_exact_centre_kernel   S3b: the nine exact responses of every candidate; marks its NMS neighbours
 //   toed_need_{count,compact}_kernel
-//                              S3c-0..1: the distinct neighbour grid points, by phase
+//                              S3c-0..1: the distinct neighbour grid points, by phase (a wave per row, a bitmap word per lane)
 //   toed_exact_mags_kernel     S3c-3: exact gradient magnitude of every distinct neighbour point
 //   toed_exact_decide_kernel   S3d: exact NMS + sub-pixel fit;  toed_cand_scatter_kernel S4: edge records
 #include <cstring>
@@ -889,13 +890,77 @@ __global__ __launch_bounds__(256) void toed_screen_fused_kernel(ImgBatch B, cons
     }
 }
 
-// S2c: one block per interpolated row: ordered compaction of the candidates (rank t -> pixel) and, in the same pass,
+// ---- word-wise list building, one wave per grid row (toed_compact_phase_kernel, toed_need_compact_kernel) ----------
+// The three pieces below stay inside the wave: DPP moves within a row of 16 lanes, v_readlane between the rows.  No LDS,
+// no ds_bpermute, no barrier.  All 64 lanes of the wave must call the first two.
+template <int CTRL>
+__device__ inline int dpp_i32(int v)
+{
+    return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true);
+}
+
+// a[k] := the sum of a[k] over the wave, k = 0..3, the same (scalar) value in every lane
+__device__ inline void wave_sum4(int a[4])
+{
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+    {
+        int v = a[k];
+        v += dpp_i32<0xB1>(v);  // quad_perm:[1,0,3,2]
+        v += dpp_i32<0x4E>(v);  // quad_perm:[2,3,0,1]
+        v += dpp_i32<0x141>(v); // row_half_mirror
+        v += dpp_i32<0x140>(v); // row_mirror: every lane holds the sum of its row of 16
+        a[k] = __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) + __builtin_amdgcn_readlane(v, 32) +
+               __builtin_amdgcn_readlane(v, 48);
+    }
+}
+
+// Exclusive scan over the wave of a packed pair `even | odd << 16` (the wave's sums must stay below 65,536 each: at most
+// 16 set bits of a parity per lane here).  Returns the packed sums of the lanes in front; `total` is the wave's packed sum.
+__device__ inline unsigned wave_excl_scan_pair(unsigned x, unsigned &total)
+{
+    int v = (int)x;
+    v += dpp_i32<0x111>(v); // row_shr:1 (lanes without a source read 0)
+    v += dpp_i32<0x112>(v); // row_shr:2
+    v += dpp_i32<0x114>(v); // row_shr:4
+    v += dpp_i32<0x118>(v); // row_shr:8: inclusive within the row of 16
+    const int t0 = __builtin_amdgcn_readlane(v, 15), t1 = __builtin_amdgcn_readlane(v, 31),
+              t2 = __builtin_amdgcn_readlane(v, 47), t3 = __builtin_amdgcn_readlane(v, 63);
+    const int row = (int)(threadIdx.x & 63) >> 4;
+    const int front = (row > 0 ? t0 : 0) + (row > 1 ? t1 : 0) + (row > 2 ? t2 : 0);
+    total = (unsigned)(t0 + t1 + t2 + t3);
+    return (unsigned)(v + front) - x;
+}
+
+// emit(b) for every set bit b of `m`, in ascending order; the loop runs as long as any lane of the wave has a bit left
+template <class Emit>
+__device__ inline void walk_set_bits(unsigned m, Emit emit)
+{
+    while (__any(m != 0u))
+    {
+        if (m)
+        {
+            const int b = __ffs((int)m) - 1;
+            m &= m - 1u;
+            emit(b);
+        }
+    }
+}
+
+// S2c: one WAVE per interpolated row: ordered compaction of the candidates (rank t -> pixel) and, in the same pass,
 // the four phase lists in raster order (no atomics: every row knows its offset in its phase's list).
 // Round 4: the offsets are no longer a launch of their own (toed_rowscan_phase_kernel: one block per image, ~5 us of latency
-// in front of this kernel): every block adds up the per-row counts in front of its row itself (a few hundred ints, four sums:
-// row parity x column parity), and the block of the first row also adds up ALL rows and publishes what the scan kernel did:
+// in front of this kernel): every wave adds up the per-row counts in front of its row itself (a few hundred ints, four sums:
+// row parity x column parity), and the wave of the first row also adds up ALL rows and publishes what the scan kernel did:
 // counts[2] (candidates; 0 if they do not fit), counts[3] = 0, counts[4] (their real number), the lengths of the four phase
 // lists, and zeroed lengths for the lists the exact stage appends to.
+// Round 7: word-wise.  A block of four waves used to own a row and every lane one flag byte: ten turns for a 2482-wide row,
+// each with two barriers, an LDS round trip and three serial 4-way sums, and the row sums went through 24 ds_bpermute a
+// call.  Now wave w of block b owns row 10 + 4b + w, a lane takes eight flag bytes with one 8-byte load (a turn = 512
+// columns), folds them into an 8-bit mask, and one packed wave scan (wave_excl_scan_pair) gives its offsets in the
+// all-candidates order and in the two phase lists of the row; the lane then walks its set bits in column order.  The first
+// column of a lane is even, so bit parity = column parity.  The load of a lane that owns at least one column < 2W - 10
+// ends at column <= 2W - 4 of its own row: it never leaves the row, let alone the flag array; the other lanes load nothing.
 // The candidate arrays hold `cap` (= max_h * max_w) entries; the screen can flag up to four times that on an image made of
 // ties (a fine checkerboard).  Then counts[4] keeps the real total and every list length is published as zero: the exact
 // stage runs empty, nothing is written past a buffer, and the host re-runs the image on the strict path (toed_sync,
@@ -903,44 +968,35 @@ __global__ __launch_bounds__(256) void toed_screen_fused_kernel(ImgBatch B, cons
 __global__ __launch_bounds__(256) void toed_compact_phase_kernel(ImgBatch B, int h, int w, int cap)
 {
     const int W2 = 2 * w, H2 = 2 * h;
-    const int i = 10 + blockIdx.x;
+    const int lane = threadIdx.x & 63;
+    const int i = __builtin_amdgcn_readfirstlane(10 + (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6));
     if (i >= H2 - 10)
         return;
-    const uint8_t *flag = B.flag[blockIdx.y] + (size_t)i * W2;
+    const uint8_t *flag = B.flag[blockIdx.y] + (size_t)i * W2 + 10;
     const int32_t *cnt = B.row_cnt[blockIdx.y]; // [2][H2]: candidates of a row in even / odd columns
     int32_t *src = B.src[blockIdx.y];
     int32_t *lists = B.lists[blockIdx.y];
-    __shared__ int w_all[4], w_par[2][4], s_sum[4][4];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    // sums over the rows in front of this one (and, in the first block, over all rows): [row parity][column parity]
+    // sums over the rows in front of this one (and, in the first row's wave, over all rows): [row parity][column parity]
     auto sum_rows = [&](int r_end, int out[4]) {
-        int a[4] = {0, 0, 0, 0};
-        for (int r = threadIdx.x; r < r_end; r += 256)
+        int se = 0, so = 0; // the rows of a lane have the lane's parity (stride 64)
+        for (int r = lane; r < r_end; r += 64)
         {
-            a[(r & 1) * 2 + 0] += cnt[r];
-            a[(r & 1) * 2 + 1] += cnt[H2 + r];
+            se += cnt[r];
+            so += cnt[H2 + r];
         }
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            for (int d = 32; d > 0; d >>= 1)
-                a[k] += __shfl_down(a[k], d);
-        __syncthreads(); // (s_sum may still be read from the previous call)
-        if (lane == 0)
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                s_sum[wid][k] = a[k];
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            out[k] = s_sum[0][k] + s_sum[1][k] + s_sum[2][k] + s_sum[3][k];
+        out[0] = lane & 1 ? 0 : se;
+        out[1] = lane & 1 ? 0 : so;
+        out[2] = lane & 1 ? se : 0;
+        out[3] = lane & 1 ? so : 0;
+        wave_sum4(out);
     };
     int pre[4];
     sum_rows(i, pre);
-    if (blockIdx.x == 0)
+    if (i == 10)
     {
         int tot[4];
         sum_rows(H2, tot);
-        if (threadIdx.x == 0)
+        if (lane == 0)
         {
             const int all = tot[0] + tot[1] + tot[2] + tot[3];
             const bool over = all > cap;
@@ -955,50 +1011,45 @@ __global__ __launch_bounds__(256) void toed_compact_phase_kernel(ImgBatch B, int
         }
     }
     int base_all = pre[0] + pre[1] + pre[2] + pre[3];
-    int base_ph[2] = {pre[(i & 1) * 2], pre[(i & 1) * 2 + 1]};
-    const int par = threadIdx.x & 1; // column parity (j0 is even)
-    const unsigned long long pmask = par ? 0xaaaaaaaaaaaaaaaaull : 0x5555555555555555ull;
-    for (int j0 = 10; j0 < W2 - 10; j0 += 256)
+    int base_e = pre[(i & 1) * 2], base_o = pre[(i & 1) * 2 + 1];
+    int32_t *list_e = lists + (size_t)((i & 1) << 1) * cap; // the list of the odd columns follows it
+    const int ncol = W2 - 20; // columns 10 .. 2W - 11
+    for (int c0 = 0; c0 < ncol; c0 += 512)
     {
-        const int j = j0 + threadIdx.x;
-        const int f = (j < W2 - 10) ? flag[j] : 0;
-        const unsigned long long m_all = __ballot(f != 0);
-        const unsigned long long below = (1ull << lane) - 1ull;
-        if (lane == 0)
+        const int c = c0 + 8 * lane; // the lane's first column, less 10
+        unsigned mask = 0;
+        if (c < ncol)
         {
-            w_all[wid] = __popcll(m_all);
-            w_par[0][wid] = __popcll(m_all & 0x5555555555555555ull);
-            w_par[1][wid] = __popcll(m_all & 0xaaaaaaaaaaaaaaaaull);
+            unsigned long long x;
+            __builtin_memcpy(&x, flag + c, 8);
+            // byte != 0 -> its top bit -> bit k of a nibble (the four products of the multiply land on distinct bits)
+            const unsigned lo = (unsigned)x, hi = (unsigned)(x >> 32);
+            const unsigned tl = ((((lo & 0x7f7f7f7fu) + 0x7f7f7f7fu) | lo) >> 7) & 0x01010101u;
+            const unsigned th = ((((hi & 0x7f7f7f7fu) + 0x7f7f7f7fu) | hi) >> 7) & 0x01010101u;
+            mask = ((tl * 0x01020408u) >> 24) | (((th * 0x01020408u) >> 24) << 4);
+            if (ncol - c < 8)
+                mask &= (1u << (ncol - c)) - 1u;
         }
-        __syncthreads();
-        int pre_all = 0, tot_all = 0, pre_ph = 0, tot_ph[2] = {0, 0};
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-        {
-            if (k < wid)
-            {
-                pre_all += w_all[k];
-                pre_ph += w_par[par][k];
-            }
-            tot_all += w_all[k];
-            tot_ph[0] += w_par[0][k];
-            tot_ph[1] += w_par[1][k];
-        }
-        if (f)
-        {
-            const int r_all = base_all + pre_all + __popcll(m_all & below);
+        unsigned total;
+        const unsigned front = wave_excl_scan_pair((unsigned)__popc(mask & 0x55u) | ((unsigned)__popc(mask & 0xaau) << 16), total);
+        int r_all = base_all + (int)(front & 0xffffu) + (int)(front >> 16);
+        int p_e = base_e + (int)(front & 0xffffu), p_o = base_o + (int)(front >> 16);
+        const int o0 = i * W2 + 10 + c;
+        walk_set_bits(mask, [&](int b) {
+            const int par = b & 1;
             if (r_all < cap)
             {
-                src[2 * r_all] = i * W2 + j;
+                src[2 * r_all] = o0 + b;
                 src[2 * r_all + 1] = -1;
-                const int ph = ((i & 1) << 1) | par;
-                lists[(size_t)ph * cap + base_ph[par] + pre_ph + __popcll(m_all & pmask & below)] = r_all;
+                list_e[(par ? p_o : p_e) + (cap & -par)] = r_all;
             }
-        }
-        base_all += tot_all;
-        base_ph[0] += tot_ph[0];
-        base_ph[1] += tot_ph[1];
-        __syncthreads();
+            ++r_all;
+            p_o += par;
+            p_e += par ^ 1;
+        });
+        base_all += (int)(total & 0xffffu) + (int)(total >> 16);
+        base_e += (int)(total & 0xffffu);
+        base_o += (int)(total >> 16);
     }
 }
 
@@ -1446,85 +1497,64 @@ __global__ __launch_bounds__(256) void toed_need_count_kernel(ExactBatch E, int 
     }
 }
 
-// S3c-1: one block per grid row: the marked points of the row, in column order, into the list of their phase.  The row's
+// S3c-1: one WAVE per grid row: the marked points of the row, in column order, into the list of their phase.  The row's
 // offsets in the two lists (even / odd columns) of its row parity are the marked points of the rows of that parity in front
-// of it -- added up here by the block itself from toed_need_count_kernel's per-row counts (round 3: a scan launch of one
-// block per image between the two).  The blocks of the last two rows (one per row parity) also publish the list lengths,
+// of it -- added up here by the wave itself from toed_need_count_kernel's per-row counts (round 3: a scan launch of one
+// block per image between the two).  The waves of the last two rows (one per row parity) also publish the list lengths,
 // lcount[4..7], and add them to counts[3] (diagnostics: distinct neighbour points; zeroed by toed_compact_phase_kernel).
+// Round 7: word-wise, like toed_compact_phase_kernel: a lane owns one 32-bit word of the row's bitmap (a turn = 2048
+// columns), counts its even and odd bits, takes the packed wave scan and walks its set bits in column order.  No LDS, no
+// barrier.  (Before: a block per row, one bit per lane, two barriers and an LDS round trip per 256 columns.)
 __global__ __launch_bounds__(256) void toed_need_compact_kernel(ExactBatch E, int h, int w, int cap)
 {
     const int W2 = 2 * w, H2 = 2 * h, wpr = (W2 + 31) >> 5;
-    const int I = blockIdx.x, im = blockIdx.y;
+    const int im = blockIdx.y, lane = threadIdx.x & 63;
+    const int I = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + (int)(threadIdx.x >> 6));
+    if (I >= H2)
+        return;
     const int32_t *__restrict__ cnt = E.need_cnt[im];
-    const bool last = I >= H2 - 2; // wave-uniform, block-uniform
+    const bool last = I >= H2 - 2; // wave-uniform
     const int mine0 = cnt[I], mine1 = cnt[H2 + I];
     if (!last && mine0 + mine1 == 0)
         return;
-    const uint32_t *__restrict__ bits = E.needbits[im];
-    int32_t *__restrict__ lists = E.lists[im];
-    __shared__ int w_par[2][4], s_sum[4][2];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    int a0 = 0, a1 = 0;
-    for (int r = (I & 1) + 2 * threadIdx.x; r < I; r += 512)
+    const uint32_t *__restrict__ bits = E.needbits[im] + (size_t)I * wpr;
+    int a[4] = {0, 0, 0, 0}; // [2], [3] stay zero: the rows of the other parity feed other lists
+    for (int r = (I & 1) + 2 * lane; r < I; r += 128)
     {
-        a0 += cnt[r];
-        a1 += cnt[H2 + r];
+        a[0] += cnt[r];
+        a[1] += cnt[H2 + r];
     }
-    for (int d = 32; d > 0; d >>= 1)
+    wave_sum4(a);
+    int base_e = a[0], base_o = a[1];
+    if (last && lane == 0)
     {
-        a0 += __shfl_down(a0, d);
-        a1 += __shfl_down(a1, d);
-    }
-    if (lane == 0)
-    {
-        s_sum[wid][0] = a0;
-        s_sum[wid][1] = a1;
-    }
-    __syncthreads();
-    int base_ph[2] = {s_sum[0][0] + s_sum[1][0] + s_sum[2][0] + s_sum[3][0], s_sum[0][1] + s_sum[1][1] + s_sum[2][1] + s_sum[3][1]};
-    if (last && threadIdx.x == 0)
-    {
-        const int n0 = base_ph[0] + mine0, n1 = base_ph[1] + mine1;
+        const int n0 = base_e + mine0, n1 = base_o + mine1;
         E.lcount[im][4 + 2 * (I & 1) + 0] = n0; // phase (row parity I & 1, column parity 0)
         E.lcount[im][4 + 2 * (I & 1) + 1] = n1;
         atomicAdd(const_cast<int32_t *>(E.counts[im]) + 3, n0 + n1);
     }
     if (mine0 + mine1 == 0)
         return;
-    const int par = threadIdx.x & 1; // column parity (J0 is a multiple of 256)
-    const unsigned long long pmask = par ? 0xaaaaaaaaaaaaaaaaull : 0x5555555555555555ull;
-    for (int J0 = 0; J0 < W2; J0 += 256)
+    int32_t *__restrict__ list_e = E.lists[im] + (size_t)(4 + ((I & 1) << 1)) * cap; // the list of the odd columns follows it
+    for (int k0 = 0; k0 < wpr; k0 += 64)
     {
-        const int J = J0 + threadIdx.x;
-        const int o = I * W2 + J;
-        const bool f = J < W2 && ((bits[(size_t)I * wpr + (J >> 5)] >> (J & 31)) & 1u);
-        const unsigned long long m_all = __ballot(f);
-        const unsigned long long below = (1ull << lane) - 1ull;
-        if (lane == 0)
-        {
-            w_par[0][wid] = __popcll(m_all & 0x5555555555555555ull);
-            w_par[1][wid] = __popcll(m_all & 0xaaaaaaaaaaaaaaaaull);
-        }
-        __syncthreads();
-        int pre_ph = 0, tot_ph[2] = {0, 0};
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-        {
-            if (k < wid)
-                pre_ph += w_par[par][k];
-            tot_ph[0] += w_par[0][k];
-            tot_ph[1] += w_par[1][k];
-        }
-        if (f)
-        {
-            const int ph = ((I & 1) << 1) | par;
-            const int pos = base_ph[par] + pre_ph + __popcll(m_all & pmask & below);
+        const int k = k0 + lane;
+        unsigned v = k < wpr ? bits[k] : 0u;
+        if (W2 - 32 * k < 32) // the row's last word (or past it): columns >= 2W do not exist
+            v &= W2 - 32 * k > 0 ? (1u << (W2 - 32 * k)) - 1u : 0u;
+        unsigned total;
+        const unsigned front = wave_excl_scan_pair((unsigned)__popc(v & 0x55555555u) | ((unsigned)__popc(v & 0xaaaaaaaau) << 16), total);
+        int p_e = base_e + (int)(front & 0xffffu), p_o = base_o + (int)(front >> 16);
+        const int o0 = I * W2 + 32 * k;
+        walk_set_bits(v, [&](int b) {
+            const int par = b & 1, pos = par ? p_o : p_e;
             if (pos < cap)
-                lists[(size_t)(4 + ph) * cap + pos] = o;
-        }
-        base_ph[0] += tot_ph[0];
-        base_ph[1] += tot_ph[1];
-        __syncthreads();
+                list_e[pos + (cap & -par)] = o0 + b;
+            p_o += par;
+            p_e += par ^ 1;
+        });
+        base_e += (int)(total & 0xffffu);
+        base_o += (int)(total >> 16);
     }
 }
 
@@ -1918,7 +1948,7 @@ int toed_enqueue(ebvo_ctx *ctx, Slot &s, int n_img, int h, int w, hipEvent_t ev_
             return EBVO_OK;
         {
             ProfScope ps(ctx, s, K_COMPACT);
-            hipLaunchKernelGGL(toed_compact_phase_kernel, dim3(H2 - 20, n_img), dim3(256), 0, s.stream, B, h, w, cap);
+            hipLaunchKernelGGL(toed_compact_phase_kernel, dim3((H2 - 20 + 3) / 4, n_img), dim3(256), 0, s.stream, B, h, w, cap);
         }
         if (stop == 2)
             return EBVO_OK;
@@ -1960,7 +1990,7 @@ int toed_enqueue(ebvo_ctx *ctx, Slot &s, int n_img, int h, int w, hipEvent_t ev_
             {
                 ProfScope ps(ctx, s, K_COMPACT); // the lists of the distinct neighbour points
                 hipLaunchKernelGGL(toed_need_count_kernel, dim3((H2 + 3) / 4, n_img), dim3(256), 0, s.stream, E, h, w);
-                hipLaunchKernelGGL(toed_need_compact_kernel, dim3(H2, n_img), dim3(256), 0, s.stream, E, h, w, cap);
+                hipLaunchKernelGGL(toed_need_compact_kernel, dim3((H2 + 3) / 4, n_img), dim3(256), 0, s.stream, E, h, w, cap);
             }
             if (stop == 4)
                 return EBVO_OK;
