@@ -56,6 +56,7 @@ ABI_SYMBOLS = (
     "ebvo_tgt_grid_rows",
     "ebvo_pose_from_quads_gt", "ebvo_temporal_estimate_pose_gt", "ebvo_pose_constraint_metrics",
     "ebvo_temporal_pose_constraint_metrics",
+    "ebvo_pose_refine_default_params", "ebvo_pose_refine_from_quads", "ebvo_temporal_refine_pose",
 )
 
 
@@ -125,6 +126,21 @@ class PoseResult(C.Structure):
 
 
 POSE_OK, POSE_INSUFFICIENT, POSE_DRAW_CAP = 0, 1, 2
+
+
+class PoseRefineParams(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("iterations", C.c_int32), ("huber_px", C.c_double), ("step_eps", C.c_double),
+                ("block_threads", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PoseRefined(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("status", C.c_int32), ("stop_reason", C.c_int32),
+                ("rounds_run", C.c_int32), ("steps_kept", C.c_int32), ("n_quads", C.c_int64), ("fit_quads", C.c_int64),
+                ("inliers", C.c_int64), ("cost_first", C.c_double), ("cost_last", C.c_double)]
+
+
+REFINE_OK, REFINE_NOTHING, REFINE_PIVOT = 0, 1, 2
+(REFINE_STOP_EPS, REFINE_STOP_CAP, REFINE_STOP_COST, REFINE_STOP_PIVOT, REFINE_STOP_FEW) = range(5)
 
 # stage ids (ebvo_hip.h EBVO_PC_*) and the names of Solution_Constraints_Application (src/MotionTracker.cpp:299-378)
 PC_STAGE_NAMES = ("Baseline", "Normalized Length Constraint", "T1 Angle Similarity Constraint", "T2 Angle Similarity Constraint",
@@ -331,6 +347,14 @@ def load_library() -> C.CDLL:
     lib.ebvo_temporal_pose_constraint_metrics.restype = i32
     lib.ebvo_temporal_pose_constraint_metrics.argtypes = [vp, i32, C.POINTER(StereoCalib), C.POINTER(PoseParams), i32,
                                                           C.POINTER(PoseCascadeRun), vp, vp]
+    lib.ebvo_pose_refine_default_params.restype = None
+    lib.ebvo_pose_refine_default_params.argtypes = [C.POINTER(PoseRefineParams)]
+    lib.ebvo_pose_refine_from_quads.restype = i32
+    lib.ebvo_pose_refine_from_quads.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, C.POINTER(StereoCalib), C.POINTER(PoseParams),
+                                                C.POINTER(PoseRefineParams), vp, vp, C.POINTER(PoseRefined), vp]
+    lib.ebvo_temporal_refine_pose.restype = i32
+    lib.ebvo_temporal_refine_pose.argtypes = [vp, i32, C.POINTER(StereoCalib), C.POINTER(PoseParams), C.POINTER(PoseRefineParams),
+                                              vp, vp, i32, C.POINTER(PoseRefined), vp]
     lib.ebvo_gt_default_params.restype = None
     lib.ebvo_gt_default_params.argtypes = [C.POINTER(GtParams)]
     lib.ebvo_stereo_set_gt.argtypes = [vp, i32, vp, i32, i32, ssz, C.POINTER(StereoCalib), C.POINTER(GtParams)]

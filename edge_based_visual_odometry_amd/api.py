@@ -7,6 +7,7 @@ like calls to the reference: ``get_Third_Order_Edges``, ``apply_NCC_Filtering`` 
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass
 
 import numpy as np
@@ -64,6 +65,28 @@ def cascade_mean(runs) -> list:
             out.append(dict(name=ref["name"], recall=sum_recall / float(count), precision=sum_precision / float(count),
                             veridical=sum_veridical / float(count)))
     return out
+
+
+def pose_error(R, t, R_gt, t_gt) -> dict:
+    """Error of a relative pose against the true one (host arithmetic; the twin of ebvo::pose_error in adapters.hpp):
+    rot_deg = the angle of E = R_gt^T R as atan2(|vee(E - E^T)| / 2, (tr E - 1) / 2) in degrees, trans_abs = |t - t_gt|,
+    trans_dir_deg = the angle between t and t_gt in degrees (NaN when either is zero)."""
+    R = np.asarray(R, dtype=np.float64).reshape(3, 3)
+    R_gt = np.asarray(R_gt, dtype=np.float64).reshape(3, 3)
+    t = np.asarray(t, dtype=np.float64).reshape(3)
+    t_gt = np.asarray(t_gt, dtype=np.float64).reshape(3)
+    E = R_gt.T @ R
+    vee = (E[2, 1] - E[1, 2], E[0, 2] - E[2, 0], E[1, 0] - E[0, 1])
+    s = math.sqrt(vee[0] * vee[0] + vee[1] * vee[1] + vee[2] * vee[2]) / 2.0
+    c = (E[0, 0] + E[1, 1] + E[2, 2] - 1.0) / 2.0
+    d = t - t_gt
+    na, nb = math.sqrt(float(t @ t)), math.sqrt(float(t_gt @ t_gt))
+    if na == 0.0 or nb == 0.0:
+        direction = math.nan
+    else:
+        x = np.cross(t, t_gt)
+        direction = math.degrees(math.atan2(math.sqrt(float(x @ x)), float(t @ t_gt)))
+    return dict(rot_deg=math.degrees(math.atan2(s, c)), trans_abs=math.sqrt(float(d @ d)), trans_dir_deg=direction)
 
 
 class Context:
@@ -813,6 +836,60 @@ class Context:
         self._check(self.lib.ebvo_temporal_pose_constraint_metrics(self._ctx, slot, C.byref(cal), C.byref(p), n_runs, runs, ptr(idx),
                                                                    ptr(stage)), "ebvo_temporal_pose_constraint_metrics")
         return self._cascade_runs(runs, idx, stage, details)
+
+    # -- inlier refit of the relative pose (Gauss-Newton over both cameras; the contract is in ebvo_hip.h) ----------------
+    def _refine_params(self, params):
+        """splits **params into ebvo_pose_params (only max_reproj_error is read) and ebvo_pose_refine_params"""
+        rp = _lib.PoseRefineParams()
+        self.lib.ebvo_pose_refine_default_params(C.byref(rp))
+        mine = {name for name, _ in rp._fields_}
+        for k in [k for k in params if k in mine]:
+            setattr(rp, k, params.pop(k))
+        return self.pose_params(**params), rp
+
+    @staticmethod
+    def _start_pose(R, t):
+        R = np.ascontiguousarray(R, dtype=np.float64).reshape(9)
+        t = np.ascontiguousarray(t, dtype=np.float64).reshape(3)
+        return R, t
+
+    @staticmethod
+    def _refined_dict(r, inlier) -> dict:
+        out = {k: getattr(r, k) for k in ("status", "stop_reason", "rounds_run", "steps_kept", "n_quads", "fit_quads", "inliers",
+                                          "cost_first", "cost_last")}
+        out["R"] = np.array(r.R[:], dtype=np.float64).reshape(3, 3)
+        out["t"] = np.array(r.t[:], dtype=np.float64)
+        out["inlier"] = inlier
+        return out
+
+    def pose_refine_from_quads(self, kf_left, kf_right, row_ptr, cf_left, cf_right, calib, R, t, row_listed=None, kf_is_tp=None,
+                               **params) -> dict:
+        """Refit of the start pose (R, t) on its inliers among the host quads (ebvo_pose_refine_from_quads); row_listed /
+        kf_is_tp select rows as in pose_from_quads_gt.  params: max_reproj_error and the fields of ebvo_pose_refine_params
+        (rounds, iterations, huber_px, step_eps, block_threads).  Returns the fields of ebvo_pose_refined, R (3x3), t and
+        `inlier` (uint8 per quad in the full CSR order, under the returned pose)."""
+        kfL, kfR, rp_, cfL, cfR, listed, tp = self._gt_quads(kf_left, kf_right, row_ptr, cf_left, cf_right, row_listed, kf_is_tp)
+        p, rp = self._refine_params(dict(params))
+        cal, r = self._calib(calib), _lib.PoseRefined()
+        R, t = self._start_pose(R, t)
+        inlier = np.zeros(int(rp_[-1]), dtype=np.uint8)
+        self._check(self.lib.ebvo_pose_refine_from_quads(self._ctx, ptr(kfL), ptr(kfR), len(kfL), ptr(rp_), ptr(cfL), ptr(cfR),
+                                                         ptr(listed), ptr(tp), C.byref(cal), C.byref(p), C.byref(rp), ptr(R), ptr(t),
+                                                         C.byref(r), ptr(inlier)), "ebvo_pose_refine_from_quads")
+        return self._refined_dict(r, inlier)
+
+    def temporal_refine_pose(self, calib, R, t, slot: int = 0, gt_rows: bool = False, **params) -> dict:
+        """The same on the slot's final quads (ebvo_temporal_refine_pose); gt_rows: over the ground-truth rows of an armed
+        slot, as temporal_estimate_pose_gt selects them."""
+        p, rp = self._refine_params(dict(params))
+        cal, r = self._calib(calib), _lib.PoseRefined()
+        R, t = self._start_pose(R, t)
+        n_kf, n = C.c_int32(), C.c_int64()
+        self._check(self.lib.ebvo_temporal_final_size(self._ctx, slot, C.byref(n_kf), C.byref(n)), "ebvo_temporal_final_size")
+        inlier = np.zeros(n.value, dtype=np.uint8)
+        self._check(self.lib.ebvo_temporal_refine_pose(self._ctx, slot, C.byref(cal), C.byref(p), C.byref(rp), ptr(R), ptr(t),
+                                                       1 if gt_rows else 0, C.byref(r), ptr(inlier)), "ebvo_temporal_refine_pose")
+        return self._refined_dict(r, inlier)
 
     # -- ground-truth evaluation from a disparity map (Find_Stereo_GT_Locations, get_Stereo_Edge_GT_Pairs,
     # -- Evaluate_Stereo_Edge_Correspondences) ---------------------------------------------------------------

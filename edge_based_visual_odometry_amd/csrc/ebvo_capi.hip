@@ -175,7 +175,7 @@ static void slot_destroy(Slot *s)
                        &s->keep,         &s->patches_raw,  &s->patches_norm,   &s->patches_flag,   &s->patches_norm_r,
                        &s->patches_flag_r, &s->pair_left,  &s->sincos,         &s->scratch_b,      &s->scratch_c,
                        &s->scratch_d,    &s->fetch_pack,   &s->pose_in,        &s->pose_geom,      &s->pose_order,
-                       &s->pose_draw,    &s->pose_hyp,       &s->pose_sel,       &s->pose_casc,       &s->gt_disp,        &s->gt_geom,        &s->gt_flags,
+                       &s->pose_draw,    &s->pose_hyp,       &s->pose_sel,       &s->pose_casc,       &s->pose_refit,     &s->gt_disp,        &s->gt_geom,        &s->gt_flags,
                        &s->gt_boxes,     &s->gt_pool_i32,  &s->gt_pool_idx,    &s->gt_rows,        &s->gt_tot,
                        &s->gt_up,        &s->tgt_geom,     &s->tgt_i32,        &s->tgt_idx,        &s->tgt_u8,
                        &s->tgt_rows,     &s->tgt_flags,    &s->tgt_tot,        &s->tgt_up};
@@ -4171,6 +4171,101 @@ extern "C" int ebvo_temporal_pose_constraint_metrics(ebvo_ctx *ctx, int slot, co
     const uint8_t *tp = (const uint8_t *)s.tgt_flags.p + 2 * (size_t)s.tq_n;
     return pose_cascade_run(ctx, s, ctx->kf_L, ctx->kf_R, F.rp, s.tq_n_kf, F.L, F.R, (int)F.n, on, s.tgt_n_rows, tp, cal, p, n_runs, runs,
                             draw_idx, draw_stage);
+}
+
+// ---- inlier refit of the relative pose (pose_refit_kernels.hip) ----------------------------------------------------------
+extern "C" void ebvo_pose_refine_default_params(ebvo_pose_refine_params *p)
+{
+    if (!p)
+        return;
+    p->rounds = 2;
+    p->iterations = 10;
+    p->huber_px = 1.5;
+    p->step_eps = 1e-10;
+    p->block_threads = 0;
+    p->reserved = 0;
+}
+
+static bool pose_refine_args_ok(const ebvo_pose_refine_params *rp, const double *R0, const double *t0, const ebvo_pose_refined *out)
+{
+    if (!rp || !R0 || !t0 || !out)
+        return false;
+    for (int i = 0; i < 9; ++i)
+        if (!std::isfinite(R0[i]))
+            return false;
+    for (int i = 0; i < 3; ++i)
+        if (!std::isfinite(t0[i]))
+            return false;
+    const int bt = rp->block_threads;
+    return rp->rounds >= 1 && rp->rounds <= 16 && rp->iterations >= 0 && rp->iterations <= 100 && rp->huber_px > 0 && rp->step_eps >= 0 &&
+           (bt == 0 || bt == 256 || bt == 512 || bt == 1024);
+}
+
+extern "C" int ebvo_pose_refine_from_quads(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *kf_right, int n_kf,
+                                           const int32_t *row_ptr, const ebvo_edge *cf_left, const ebvo_edge *cf_right,
+                                           const uint8_t *row_listed, const uint8_t *kf_is_tp, const ebvo_stereo_calib *cal,
+                                           const ebvo_pose_params *p, const ebvo_pose_refine_params *rp, const double R0[9],
+                                           const double t0[3], ebvo_pose_refined *out, uint8_t *inlier)
+{
+    ebvo_pose_result unused;
+    if (!ctx || !pose_args_ok(cal, p, &unused) || !pose_refine_args_ok(rp, R0, t0, out))
+        return EBVO_ERR_ARG;
+    PoseHostQuads q;
+    if (int rc = pose_host_quads_check(ctx, kf_left, kf_right, n_kf, row_ptr, cf_left, cf_right, row_listed, kf_is_tp, &q))
+        return rc;
+    Slot &s = *ctx->slots[0];
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    if (q.n_sel < 2) // nothing to upload or launch
+    {
+        memset(out, 0, sizeof *out);
+        memcpy(out->R, R0, sizeof out->R);
+        memcpy(out->t, t0, sizeof out->t);
+        out->status = 1;
+        out->stop_reason = 4;
+        out->n_quads = q.n_sel;
+        if (inlier && q.n > 0)
+            memset(inlier, 0, (size_t)q.n);
+        return EBVO_OK;
+    }
+    if (int rc = pose_host_quads_upload(ctx, s, kf_left, kf_right, n_kf, row_ptr, cf_left, cf_right, row_listed, kf_is_tp, nullptr, &q))
+        return rc;
+    return pose_refit_run(ctx, s, q.kfL, q.kfR, q.rp, n_kf, q.cfL, q.cfR, q.n, row_listed || kf_is_tp ? q.on : nullptr, cal, p, rp, R0, t0,
+                          out, inlier);
+}
+
+extern "C" int ebvo_temporal_refine_pose(ebvo_ctx *ctx, int slot, const ebvo_stereo_calib *cal, const ebvo_pose_params *p,
+                                         const ebvo_pose_refine_params *rp, const double R0[9], const double t0[3], int gt_rows,
+                                         ebvo_pose_refined *out, uint8_t *inlier)
+{
+    ebvo_pose_result unused;
+    Slot *sp;
+    if (!ctx || !pose_args_ok(cal, p, &unused) || !pose_refine_args_ok(rp, R0, t0, out) || (gt_rows != 0 && gt_rows != 1))
+        return EBVO_ERR_ARG;
+    if (gt_rows)
+    {
+        if (int rc = pose_gt_slot(ctx, slot, &sp))
+            return rc;
+    }
+    else
+    {
+        if (get_slot(ctx, slot, &sp))
+            return EBVO_ERR_ARG;
+        Slot &s = *sp;
+        if (s.tq_final.n < 0 || s.in_flight || s.fin_in_flight || s.tq_in_flight || s.tq_kf_gen != ctx->kf_gen)
+        {
+            ctx->last_error = s.tq_final.n < 0 ? "the slot holds no final quads (ebvo_temporal_match with stages = 1 first)"
+                              : s.tq_kf_gen != ctx->kf_gen ? "the keyframe was replaced since the slot's quads were matched"
+                                                           : "the slot has work in flight (wait for it first)";
+            return EBVO_ERR_STATE;
+        }
+        if (s.tq_final.n > INT32_MAX)
+            return EBVO_ERR_ARG;
+    }
+    Slot &s = *sp;
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    const Slot::TqFinal &F = s.tq_final;
+    const uint8_t *on = gt_rows ? (const uint8_t *)s.tgt_u8.p + (size_t)s.tgt_n_kf : nullptr; // row_on[], as the GT search
+    return pose_refit_run(ctx, s, ctx->kf_L, ctx->kf_R, F.rp, s.tq_n_kf, F.L, F.R, (int)F.n, on, cal, p, rp, R0, t0, out, inlier);
 }
 
 // the slot's page-locked result arena holds at least `bytes` (a re-allocation waits for copies still heading into the old one).

@@ -90,6 +90,20 @@ __device__ static inline void stereo_gamma_tangent(const FinalCalib &C, const eb
     G[1] = rho1 * g1[1];
     G[2] = rho1 * g1[2];
 }
+
+// score_Pose_Hypothesis for one quad: cv::norm(K (R Gamma + t) / z - left centre) < thr
+__device__ static inline bool pose_inlier(const double *Rt, const double *K, const double *G, double ux, double uy, double thr)
+{
+    double h[3], p[3];
+    mv3(Rt, G, h);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        h[i] = h[i] + Rt[9 + i];
+    mv3(K, h, p);
+    const double x = p[0] / p[2], y = p[1] / p[2];
+    const double dx = x - ux, dy = y - uy;
+    return sqrt(dx * dx + dy * dy) < thr;
+}
 #endif
 
 static inline double cof3_host(const double *m, int i, int j)

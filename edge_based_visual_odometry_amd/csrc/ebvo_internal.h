@@ -175,6 +175,7 @@ struct Slot
                                                                  // order, one batch of draws, its hypotheses
     GrowBuf pose_sel, pose_casc; // ground-truth rows: the compacted selection and what is scattered back; the cascade's draws,
                                  // counters and stage bytes
+    GrowBuf pose_refit;          // inlier refit (pose_refit_kernels.hip): seven planes per quad, the fit set, the mask, the result
     // ground-truth evaluation (gt_kernels.hip, ebvo_stereo_set_gt): armed = the buffers below describe the resident pair
     GrowBuf gt_disp, gt_geom, gt_flags, gt_boxes, gt_pool_i32, gt_pool_idx, gt_rows, gt_tot;
     GrowBuf gt_up; // everything ebvo_gt_locate / ebvo_gt_evaluate_rows need (host-array calls: they touch nothing else of slot 0)
@@ -669,6 +670,24 @@ int pose_cascade_run(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_
                      int32_t *draw_idx, uint8_t *draw_stage);
 // status 1 for every run: n selected quads, nothing launched, no random number drawn
 void pose_cascade_insufficient(ebvo_ctx *ctx, const ebvo_pose_params *p, int64_t n, int n_runs, ebvo_pose_cascade_run *runs);
+// what pose_refit_kernel leaves: the pose (R row-major, then t) and the fields of ebvo_pose_refined it forms
+struct PoseRefitOut
+{
+    double Rt[12];
+    double cost_first, cost_last;
+    int32_t status, stop, rounds_run, steps_kept, fit, inliers;
+};
+// The refit over n >= 2 selected quads (compacted when d_map != NULL: d_map[k] = the full CSR index, n_full quads in all).
+// inlier (host, may be NULL): n_full bytes.  Waits for the result.
+int pose_refit_device(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, const int32_t *d_rp, int n_kf,
+                      const ebvo_edge *d_cfL, const ebvo_edge *d_cfR, int n, const int32_t *d_map, int n_full,
+                      const ebvo_stereo_calib *cal, double thr, const ebvo_pose_refine_params *rp, const double *R0, const double *t0,
+                      PoseRefitOut *res, uint8_t *inlier);
+// ... over every quad (d_on == NULL) or the rows with d_on[i] != 0, compacted as pose_run_gt compacts them
+int pose_refit_run(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, const int32_t *d_rp, int n_kf,
+                   const ebvo_edge *d_cfL, const ebvo_edge *d_cfR, int n, const uint8_t *d_on, const ebvo_stereo_calib *cal,
+                   const ebvo_pose_params *p, const ebvo_pose_refine_params *rp, const double *R0, const double *t0,
+                   ebvo_pose_refined *out, uint8_t *inlier);
 int misc_fp64_peak(ebvo_ctx *ctx, Slot &s, int iters, double *tf_muladd, double *tf_fma);
 
 #endif

@@ -195,19 +195,7 @@ __global__ void pose_hyp_kernel(const int32_t *__restrict__ draws, int nb, const
     }
 }
 
-// score_Pose_Hypothesis for one quad: cv::norm(K (R Gamma + t) / z - left centre) < thr
-__device__ static inline bool pose_inlier(const double *Rt, const double *K, const double *G, double ux, double uy, double thr)
-{
-    double h[3], p[3];
-    mv3(Rt, G, h);
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        h[i] = h[i] + Rt[9 + i];
-    mv3(K, h, p);
-    const double x = p[0] / p[2], y = p[1] / p[2];
-    const double dx = x - ux, dy = y - uy;
-    return sqrt(dx * dx + dy * dy) < thr;
-}
+// pose_inlier (score_Pose_Hypothesis for one quad) is in ebvo_geom.h: the refit (pose_refit_kernels.hip) selects with it too
 
 // grid (quad chunks of 256, hypothesis tiles of POSE_TILE_H); counts[] zeroed before
 __global__ __launch_bounds__(256) void pose_score_kernel(const double *__restrict__ hyp, const uint8_t *__restrict__ ok, int nb,
@@ -838,5 +826,52 @@ int pose_cascade_run(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_
             }
         }
     }
+    return EBVO_OK;
+}
+
+// ---- inlier refit (pose_refit_kernels.hip) over every quad or over the ground-truth rows -----------------------------------
+int pose_refit_run(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, const int32_t *d_rp, int n_kf,
+                   const ebvo_edge *d_cfL, const ebvo_edge *d_cfR, int n, const uint8_t *d_on, const ebvo_stereo_calib *cal,
+                   const ebvo_pose_params *p, const ebvo_pose_refine_params *rp, const double *R0, const double *t0,
+                   ebvo_pose_refined *out, uint8_t *inlier)
+{
+    ebvo_pose_refined r;
+    memset(&r, 0, sizeof r);
+    memcpy(r.R, R0, sizeof r.R);
+    memcpy(r.t, t0, sizeof r.t);
+    r.status = 1;
+    r.stop_reason = 4;
+    r.n_quads = n;
+    PoseSel S;
+    if (d_on)
+    {
+        if (int rc = pose_select(ctx, s, d_kfL, d_kfR, d_rp, n_kf, d_cfL, d_cfR, n, d_on, nullptr, false, &S))
+            return rc;
+        r.n_quads = S.n;
+    }
+    if (r.n_quads < 2) // nothing to fit: nothing launched
+    {
+        if (inlier && n > 0)
+            memset(inlier, 0, (size_t)n);
+        *out = r;
+        return EBVO_OK;
+    }
+    PoseRefitOut o;
+    if (int rc = d_on ? pose_refit_device(ctx, s, S.kfL, S.kfR, S.rp, S.n_rows, S.cfL, S.cfR, S.n, S.map, n, cal, p->max_reproj_error, rp,
+                                          R0, t0, &o, inlier)
+                      : pose_refit_device(ctx, s, d_kfL, d_kfR, d_rp, n_kf, d_cfL, d_cfR, n, nullptr, n, cal, p->max_reproj_error, rp, R0,
+                                          t0, &o, inlier))
+        return rc;
+    memcpy(r.R, o.Rt, sizeof r.R);
+    memcpy(r.t, o.Rt + 9, sizeof r.t);
+    r.status = o.status;
+    r.stop_reason = o.stop;
+    r.rounds_run = o.rounds_run;
+    r.steps_kept = o.steps_kept;
+    r.fit_quads = o.fit;
+    r.inliers = o.inliers;
+    r.cost_first = o.cost_first;
+    r.cost_last = o.cost_last;
+    *out = r;
     return EBVO_OK;
 }

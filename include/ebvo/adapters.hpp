@@ -26,6 +26,7 @@
 
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <fstream>
@@ -848,6 +849,12 @@ class MotionTrackerHIP
         size_t dynamic_max_iter = 0;
         std::vector<uint8_t> inliers; // per final quad (CSR order of TemporalMatcherHIP::Quads) when asked for
         ebvo_pose_result pose{};      // every field of the search
+        ebvo_pose_refined refined{};  // what refine_Relative_Pose left: the refitted pose and every field of the refit
+    };
+    struct Refine_Options
+    {
+        ebvo_pose_refine_params p;
+        Refine_Options() { ebvo_pose_refine_default_params(&p); }
     };
 
     struct Quad_Pair_Evaluation_Metrics // include/MotionTracker.h
@@ -882,6 +889,28 @@ class MotionTrackerHIP
         state.best_minimal_inlier_count = (size_t)r.best_inliers;
         state.dynamic_max_iter = (size_t)r.dynamic_max_iter;
         return r.status != 1;
+    }
+
+    // The inlier refit (this project's own; the reference never fits its best hypothesis): Gauss-Newton over both cameras
+    // from the start pose in state.R / state.t (what the search left there) on the quads the search ran on.  The refitted
+    // pose and the refit's fields are left in state.refined, state.R / state.t stay the start pose; state.inliers holds the
+    // inliers of the refitted pose when asked for.  Returns true when the pose was refined (refined.status == 0).
+    bool refine_Relative_Pose(int slot, const Ransac_Options &opt, const Refine_Options &refine_opt, Ransac_State &state,
+                              bool gt_rows = false, bool want_inliers = false)
+    {
+        state.refined = ebvo_pose_refined{};
+        int32_t n_kf = 0;
+        int64_t n_final = 0;
+        last_status = ebvo_temporal_final_size(ctx_->get(), slot, &n_kf, &n_final);
+        if (!report(*ctx_, last_status, "ebvo_temporal_final_size"))
+            return false;
+        if (want_inliers)
+            state.inliers.assign((size_t)n_final, 0);
+        last_status = ebvo_temporal_refine_pose(ctx_->get(), slot, &calib_, &opt.p, &refine_opt.p, state.R.data(), state.t.data(),
+                                                gt_rows ? 1 : 0, &state.refined, want_inliers ? state.inliers.data() : nullptr);
+        if (!report(*ctx_, last_status, "ebvo_temporal_refine_pose"))
+            return false;
+        return state.refined.status == 0;
     }
 
     // n_runs calls of the reference's Solution_Constraints_Application (src/Pipeline.cpp:198-203 makes 20) in one device
@@ -947,6 +976,32 @@ class MotionTrackerHIP
     Context::Ptr ctx_;
     ebvo_stereo_calib calib_;
 };
+
+// The error of a relative pose (row-major R, t) against the true one, on the host: the angle of E = R_gt^T R as
+// atan2(|vee(E - E^T)| / 2, (tr E - 1) / 2) in degrees, |t - t_gt|, and the angle between t and t_gt in degrees (NaN when
+// either is zero).  The metric of the reference's commented-out evaluate_Pose_Accuracy.
+struct PoseError
+{
+    double rot_deg, trans_abs, trans_dir_deg;
+};
+inline PoseError pose_error(const double *R, const double *t, const double *R_gt, const double *t_gt)
+{
+    double E[9];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j)
+            E[i * 3 + j] = R_gt[i] * R[j] + R_gt[3 + i] * R[3 + j] + R_gt[6 + i] * R[6 + j];
+    const double deg = 180.0 / 3.14159265358979323846;
+    const double v[3] = {E[7] - E[5], E[2] - E[6], E[3] - E[1]};
+    const double d[3] = {t[0] - t_gt[0], t[1] - t_gt[1], t[2] - t_gt[2]};
+    const double x[3] = {t[1] * t_gt[2] - t[2] * t_gt[1], t[2] * t_gt[0] - t[0] * t_gt[2], t[0] * t_gt[1] - t[1] * t_gt[0]};
+    auto norm = [](const double *a) { return std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]); };
+    PoseError e;
+    e.rot_deg = std::atan2(norm(v) / 2.0, (E[0] + E[4] + E[8] - 1.0) / 2.0) * deg;
+    e.trans_abs = norm(d);
+    e.trans_dir_deg = norm(t) == 0.0 || norm(t_gt) == 0.0 ? std::nan("")
+                                                          : std::atan2(norm(x), t[0] * t_gt[0] + t[1] * t_gt[1] + t[2] * t_gt[2]) * deg;
+    return e;
+}
 
 // Frame_Evaluation_Metrics (include/Stereo_Matches.h): what get_Stereo_Edge_Pairs returns on a dataset with ground truth --
 // one (name, recall / precision / pair precision / ambiguity) entry per stage the chain ran, in pipeline order.

@@ -39,7 +39,9 @@ extern "C" {
                               ebvo_temporal_estimate_pose, ebvo_pose_from_quads, ebvo_temporal_final_size,
                               ebvo_debug_set key 20; and with the additive pose stage under ground truth:
                               ebvo_pose_from_quads_gt, ebvo_temporal_estimate_pose_gt, ebvo_pose_constraint_metrics,
-                              ebvo_temporal_pose_constraint_metrics */
+                              ebvo_temporal_pose_constraint_metrics; and with the additive inlier refit:
+                              ebvo_pose_refine_params / _refined, ebvo_pose_refine_default_params,
+                              ebvo_pose_refine_from_quads, ebvo_temporal_refine_pose */
 
 typedef struct ebvo_ctx ebvo_ctx;
 
@@ -716,6 +718,67 @@ int ebvo_pose_constraint_metrics(ebvo_ctx *ctx, const ebvo_edge *kf_left, const 
  * (what ebvo_temporal_gt_flags returns). */
 int ebvo_temporal_pose_constraint_metrics(ebvo_ctx *ctx, int slot, const ebvo_stereo_calib *cal, const ebvo_pose_params *p,
                                           int n_runs, ebvo_pose_cascade_run *runs, int32_t *draw_idx, uint8_t *draw_stage);
+
+/* ---- inlier refit of the relative pose (this project's own: the reference never fits its best minimal hypothesis) ---- */
+/* Gauss-Newton on the reprojection error of BOTH cameras over the inliers of a start pose (usually the search's R, t).  This
+ * comment is the arithmetic contract; tests/oracle_pose_refit.py restates it and the device matches it bit for bit.  fp64,
+ * no FMA, IEEE division and sqrt; mv3 / dot3 / cross3 are those of csrc/ebvo_geom.h, (a b + c d) + e f.
+ * Inputs: the selected quads in CSR order (every quad, or the quads of the rows that are listed and TP, compacted as the
+ *   search compacts them), k = 0 .. n - 1; per quad Gamma_k (the keyframe mate's 3-D point, as the search forms it), the CF left
+ *   centre u_k and the CF right centre ub_k; the start pose; the calibration with K_right := K_left (K below).
+ * Model: RG = mv3(R, Gamma), X = RG + t.  Camera 0: Y = X, A = I, centre u.  Camera 1: Y = mv3(R21, X) + T21, A = R21, centre ub.
+ *   p = mv3(K, Y), pi = (p0 / p2, p1 / p2), r = pi - centre, rho = sqrt(rx rx + ry ry).
+ *   Huber, delta = huber_px: rho <= delta: w = 1, cost (rho rho) 0.5; else w = delta / rho, cost delta (rho - delta 0.5).
+ *   ip = 1 / p2, jx_j = ip (K_0j - pi_x K_2j), jy_j = ip (K_1j - pi_y K_2j); camera 1: jx_j <- (jx_0 A_0j + jx_1 A_1j) + jx_2 A_2j,
+ *   the same for jy.  Jacobian rows under R <- Exp(w) R, t <- t + v: Jx = [cross3(RG, jx) | jx], Jy = [cross3(RG, jy) | jy].
+ *   The 28 terms of a camera: w (Jx_i Jx_j + Jy_i Jy_j) for i <= j row-major (21), w (Jx_i rx + Jy_i ry) (6), the cost.  A
+ *   camera whose rho is not < +inf contributes +0.0 to all 28.  A quad's term is left + right.
+ * Sums: virtual lane v = k mod 1024 adds its quads' terms in ascending k from +0.0 (a quad outside the fit set adds +0.0);
+ *   within each group of 64 consecutive lanes x[l] += x[l + s], l < s, s = 32 .. 1; the 16 group sums by the same tree,
+ *   s = 8 .. 1.  The result depends on no launch geometry.
+ * A round: the fit set S = the quads the search's own inlier test accepts under the current pose (max_reproj_error of `p`,
+ *   camera 0 only); |S| < 3 ends the refit with stop reason 4.  For it = 0 .. iterations: the 28 sums over S; if it > 0 and
+ *   not cost <= cost_prev (NaN included) the previous pose is restored, stop reason 2; if it == iterations, stop reason 1;
+ *   H d = -g by Cholesky (L_jj = sqrt(H_jj - sum_k L_jk L_jk), the subtractions in ascending k, a pivot not > 0: stop
+ *   reason 3 and the pose is kept; L_ij = (H_ij - sum_k L_ik L_jk) / L_jj; forward and back substitution the same way, k
+ *   ascending); R <- Exp(d_0..2) R by the 3 x 3 product in mv3 order with no re-orthonormalisation, t <- t + d_3..5;
+ *   max |d| < step_eps: stop reason 0.  `rounds` rounds are run, each re-selecting S under the current pose.
+ * Exp(w): th2 = (w0 w0 + w1 w1) + w2 w2; th2 == 0: I.  Else th = sqrt(th2), a = sin(th) / th, sh = sin(th 0.5),
+ *   b = (2 (sh sh)) / th2, E = (I + a W) + b (W W) with W = [w]x; both sines from ebvo_sincos (csrc/ebvo_math.h).
+ * block_threads is a developer switch: a block of 256 or 512 threads owns virtual lanes v, v + block_threads, ...; same bits. */
+typedef struct ebvo_pose_refine_params
+{
+    int32_t rounds, iterations;    /* 2, 10 */
+    double huber_px, step_eps;     /* 1.5 (+inf = least squares), 1e-10 */
+    int32_t block_threads, reserved; /* 0 (= 1024), 256, 512 or 1024 */
+} ebvo_pose_refine_params;
+typedef struct ebvo_pose_refined
+{
+    double R[9], t[3];
+    int32_t status;      /* 0 refined / 1 nothing to fit (fewer than 2 selected quads: nothing launched; or |S| < 3 under the
+                            start pose) / 2 the first solve had a non-positive pivot; 1 and 2 return the start pose */
+    int32_t stop_reason; /* of the last round run: 0 eps, 1 step cap, 2 cost rose, 3 pivot, 4 |S| < 3 */
+    int32_t rounds_run, steps_kept; /* steps applied and not taken back */
+    int64_t n_quads, fit_quads /* |S| of the last round */, inliers /* under the returned pose; 0 when nothing was launched */;
+    double cost_first, cost_last; /* of the last round that formed its sums: at its first pose and at the last pose it kept */
+} ebvo_pose_refined;
+void ebvo_pose_refine_default_params(ebvo_pose_refine_params *p);
+/* On host arrays, as ebvo_pose_from_quads_gt (row_listed / kf_is_tp: n_kf bytes each, NULL = all set).  `p`: only
+ * max_reproj_error is read, the ranges of ebvo_pose_params apply to all of it.  Accepted: 1 <= rounds <= 16,
+ * 0 <= iterations <= 100, huber_px > 0 (+inf allowed), step_eps >= 0, no NaN, R0 and t0 finite, block_threads in its set;
+ * anything else: EBVO_ERR_ARG, nothing touched.  inlier (may be NULL): n bytes in the full CSR order, 1 = inlier of the
+ * returned pose, zero on quads not selected.  Slot 0's stream without touching slot 0's results; the context's rand() stream
+ * is not touched. */
+int ebvo_pose_refine_from_quads(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *kf_right, int n_kf, const int32_t *row_ptr,
+                                const ebvo_edge *cf_left, const ebvo_edge *cf_right, const uint8_t *row_listed, const uint8_t *kf_is_tp,
+                                const ebvo_stereo_calib *cal, const ebvo_pose_params *p, const ebvo_pose_refine_params *rp,
+                                const double R0[9], const double t0[3], ebvo_pose_refined *out, uint8_t *inlier);
+/* On the slot's final quads: gt_rows = 0 every quad (the state rules of ebvo_temporal_estimate_pose), gt_rows = 1 the
+ * ground-truth rows of an armed slot (those of ebvo_temporal_estimate_pose_gt).  inlier (may be NULL): n_final bytes.  The
+ * slot's results, its armed state, ebvo_temporal_gt_metrics and the rand() stream are unchanged. */
+int ebvo_temporal_refine_pose(ebvo_ctx *ctx, int slot, const ebvo_stereo_calib *cal, const ebvo_pose_params *p,
+                              const ebvo_pose_refine_params *rp, const double R0[9], const double t0[3], int gt_rows,
+                              ebvo_pose_refined *out, uint8_t *inlier);
 
 /* ---- ground-truth evaluation from a disparity map (the reference's has_gt() == true branch, is_left = true) ------- */
 /* Find_Stereo_GT_Locations (src/Stereo_Matches.cpp:133-200), get_Stereo_Edge_GT_Pairs (:202-268) and

@@ -1,6 +1,7 @@
 """Microseconds per pose call (ebvo_temporal_estimate_pose / ebvo_pose_from_quads) at the EuRoC frame-loop size (the resident
 chain's final quads of the half-size EuRoC frames: keyframe 0, frame 2) and on 20k synthetic quads (30 % outliers), with the
-number of device batches each call needed (draws / batch size, rounded up).  Prints one JSON line."""
+number of device batches each call needed (draws / batch size, rounded up); and per inlier refit of the pose each search found
+(ebvo_temporal_refine_pose / ebvo_pose_refine_from_quads, default parameters) on the same quads.  Prints one JSON line."""
 import json
 import math
 import os
@@ -27,6 +28,11 @@ def timed(fn, reps):
     return (time.perf_counter() - t0) / reps * 1e6, r
 
 
+def refit_fields(us, r):
+    return dict(us_per_call=round(us, 1), status=int(r["status"]), stop_reason=int(r["stop_reason"]), rounds_run=int(r["rounds_run"]),
+                steps_kept=int(r["steps_kept"]), fit_quads=int(r["fit_quads"]), inliers=int(r["inliers"]))
+
+
 def main():
     out = {}
     with Context(512, 1280, device=0) as ctx:
@@ -34,11 +40,17 @@ def main():
         us, r = timed(lambda: ctx.temporal_estimate_pose(calib), 50)
         out["euroc_resident"] = dict(n_quads=int(r["n_quads"]), us_per_call=round(us, 1), draws=int(r["draws"]),
                                      hypotheses=int(r["hypotheses"]), batches=math.ceil(r["draws"] / BATCH))
+        pose = r
+        us, r = timed(lambda: ctx.temporal_refine_pose(calib, pose["R"], pose["t"]), 50)
+        out["euroc_resident"]["refit"] = refit_fields(us, r)
         K = rig("euroc")
         kf_l, kf_r, rp, cf_l, cf_r, _ = op.synthetic_quads(20000, 0.3, (K[0], K[2], K[3]), R_GT, T_GT, seed=1)
         us, r = timed(lambda: ctx.pose_from_quads(kf_l, kf_r, rp, cf_l, cf_r, K), 10)
         out["synthetic_20k_host_arrays"] = dict(n_quads=int(r["n_quads"]), us_per_call=round(us, 1), draws=int(r["draws"]),
                                                 hypotheses=int(r["hypotheses"]), batches=math.ceil(r["draws"] / BATCH))
+        pose = r
+        us, r = timed(lambda: ctx.pose_refine_from_quads(kf_l, kf_r, rp, cf_l, cf_r, K, pose["R"], pose["t"]), 10)
+        out["synthetic_20k_host_arrays"]["refit"] = refit_fields(us, r)
     print(json.dumps(out))
 
 
