@@ -54,6 +54,8 @@ ABI_SYMBOLS = (
     "ebvo_temporal_gt_flags", "ebvo_tgt_veridical", "ebvo_tgt_evaluate_rows",
     "ebvo_temporal_keep_stages", "ebvo_temporal_stage_size", "ebvo_temporal_fetch_stage", "ebvo_temporal_gt_stage_rows",
     "ebvo_tgt_grid_rows",
+    "ebvo_tprior_default_params", "ebvo_temporal_set_prior", "ebvo_temporal_clear_prior", "ebvo_temporal_prior_fetch",
+    "ebvo_tprior_candidates",
     "ebvo_pose_from_quads_gt", "ebvo_temporal_estimate_pose_gt", "ebvo_pose_constraint_metrics",
     "ebvo_temporal_pose_constraint_metrics",
     "ebvo_pose_refine_default_params", "ebvo_pose_refine_from_quads", "ebvo_temporal_refine_pose",
@@ -182,6 +184,10 @@ GT_NUM_STAGES = 12
 
 class TgtParams(C.Structure):
     _fields_ = [("orient_thr_deg", C.c_double), ("tp_dist", C.c_double), ("search_radius", C.c_double), ("img_margin", C.c_double)]
+
+
+class TpriorParams(C.Structure):
+    _fields_ = [("img_margin", C.c_double), ("use_orientation", C.c_int32)]
 
 
 # stage ids (ebvo_hip.h EBVO_TGT_*) and the names of src/Temporal_Matches.cpp:186-215
@@ -379,6 +385,13 @@ def load_library() -> C.CDLL:
     lib.ebvo_temporal_fetch_stage.argtypes = [vp, i32, i32, vp, vp, vp, vp]
     lib.ebvo_temporal_gt_stage_rows.argtypes = [vp, i32, i32, vp, i32]
     lib.ebvo_tgt_grid_rows.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, dbl, vp, vp, vp, dbl, vp, C.POINTER(GtStage)]
+    lib.ebvo_tprior_default_params.restype = None
+    lib.ebvo_tprior_default_params.argtypes = [C.POINTER(TpriorParams)]
+    lib.ebvo_temporal_set_prior.argtypes = [vp, i32, vp, vp, C.POINTER(StereoCalib), C.POINTER(TpriorParams)]
+    lib.ebvo_temporal_clear_prior.argtypes = [vp, i32]
+    lib.ebvo_temporal_prior_fetch.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    lib.ebvo_tprior_candidates.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, dbl, dbl, vp, vp, C.POINTER(StereoCalib),
+                                           C.POINTER(TpriorParams), vp, vp, vp, vp, vp, vp, vp, i64, C.POINTER(i64)]
     lib.ebvo_undistort.argtypes = [vp, vp, i32, i32, ssz, vp, vp, i32, vp, ssz]
     lib.ebvo_stereo_set_undistort.argtypes = [vp, C.POINTER(UndistortParams)]
     lib.ebvo_stereo_fetch_end.argtypes = [vp, i32, C.POINTER(StereoView)]

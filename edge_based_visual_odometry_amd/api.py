@@ -89,6 +89,22 @@ def pose_error(R, t, R_gt, t_gt) -> dict:
     return dict(rot_deg=math.degrees(math.atan2(s, c)), trans_abs=math.sqrt(float(d @ d)), trans_dir_deg=direction)
 
 
+def predict_pose(T_prev, T_prev2=None):
+    """Constant-velocity prediction of the next pose keyframe -> frame, for Context.temporal_set_prior (host arithmetic; the
+    twin of ebvo::predict_pose in adapters.hpp).  T_prev = (R, t) of frame k, T_prev2 = (R, t) of frame k - 1, both
+    keyframe -> frame: the motion of the last step, T_k T_{k-1}^-1, is applied once more to T_k.  With one earlier pose only
+    (T_prev2 None) the prediction is that pose itself.  Returns (R [3, 3], t [3])."""
+    Rk = np.asarray(T_prev[0], dtype=np.float64).reshape(3, 3)
+    tk = np.asarray(T_prev[1], dtype=np.float64).reshape(3)
+    if T_prev2 is None:
+        return Rk.copy(), tk.copy()
+    Rj = np.asarray(T_prev2[0], dtype=np.float64).reshape(3, 3)
+    tj = np.asarray(T_prev2[1], dtype=np.float64).reshape(3)
+    Rd = Rk @ Rj.T                      # T_k T_{k-1}^-1 = (Rd, tk - Rd tj)
+    td = tk - Rd @ tj
+    return Rd @ Rk, Rd @ tk + td
+
+
 class Context:
     """One HIP device workspace (``ebvo_ctx``).  Not thread-safe; one per process and GPU."""
 
@@ -1143,6 +1159,70 @@ class Context:
             self._check(self.lib.ebvo_tgt_veridical(*head, *(ptr(out[k]) for k in names), ptr(out["ver_idx"]), n_ver.value,
                                                     C.byref(n_ver)), "ebvo_tgt_veridical")
         out["n_veridical"] = n_ver.value
+        return out
+
+    # -- temporal matching under a pose prior (this project's own stage: the search is centred on the predicted projections) --
+    def tprior_params(self, **kw) -> _lib.TpriorParams:
+        """ebvo_tprior_params: img_margin = 0, use_orientation = 1, with `kw` applied."""
+        p = _lib.TpriorParams()
+        self.lib.ebvo_tprior_default_params(C.byref(p))
+        fields = {name for name, _ in p._fields_}
+        for k, v in kw.items():
+            if k not in fields:
+                raise TypeError(f"tprior: unknown parameter {k!r}")
+            setattr(p, k, v)
+        return p
+
+    def temporal_set_prior(self, R, t, calib, slot: int = 0, **params):
+        """Give the slot's NEXT temporal match the relative pose keyframe -> current frame it is expected to find
+        (ebvo_temporal_set_prior; the convention of temporal_set_gt and of temporal_estimate_pose's result).  One-shot: the
+        next successful match consumes it; temporal_set_keyframe drops it.  params: img_margin, use_orientation."""
+        R, t = self._pose(R, t)
+        p, cal = self.tprior_params(**params), self._calib(calib)
+        self._check(self.lib.ebvo_temporal_set_prior(self._ctx, slot, ptr(R), ptr(t), C.byref(cal), C.byref(p)),
+                    "ebvo_temporal_set_prior")
+
+    def temporal_clear_prior(self, slot: int = 0):
+        self._check(self.lib.ebvo_temporal_clear_prior(self._ctx, slot), "ebvo_temporal_clear_prior")
+
+    def temporal_prior_fetch(self, slot: int = 0) -> dict:
+        """Per keyframe mate of a match made under a prior: live, proj_left / proj_right [n, 2], orient_left / orient_right."""
+        n = self._tq_n_kf.get(slot, 0)
+        out = dict(live=np.zeros(n, dtype=np.uint8), proj_left=np.zeros((n, 2)), proj_right=np.zeros((n, 2)),
+                   orient_left=np.zeros(n), orient_right=np.zeros(n))
+        self._check(self.lib.ebvo_temporal_prior_fetch(self._ctx, slot, *(ptr(out[k]) for k in (
+            "live", "proj_left", "proj_right", "orient_left", "orient_right"))), "ebvo_temporal_prior_fetch")
+        return out
+
+    def tprior_candidates(self, kf_left, kf_right, cf_left, cf_right, img_w, img_h, R, t, calib, cell_size=15,
+                          grid_radius: float = 30.0, orient_thr_deg: float = 10.0, cap=None, **params) -> dict:
+        """The candidate stage under a pose prior on host arrays (ebvo_tprior_candidates): the arrays of temporal_prior_fetch
+        plus the candidate lists row_ptr / col_idx and n_candidates.  cap: room of col_idx (None: sized by a first call)."""
+        kf_left, kf_right, cf_left, cf_right = (_edges(a) for a in (kf_left, kf_right, cf_left, cf_right))
+        if len(kf_left) != len(kf_right) or len(cf_left) != len(cf_right):
+            raise ValueError("tprior_candidates: the arrays do not describe the same mates")
+        R, t = self._pose(R, t)
+        p, cal = self.tprior_params(**params), self._calib(calib)
+        n, n_cf = len(kf_left), len(cf_left)
+        out = dict(live=np.zeros(n, dtype=np.uint8), proj_left=np.zeros((n, 2)), proj_right=np.zeros((n, 2)),
+                   orient_left=np.zeros(n), orient_right=np.zeros(n), row_ptr=np.zeros(n + 1, dtype=np.int32))
+        names = ("live", "proj_left", "proj_right", "orient_left", "orient_right", "row_ptr")
+        head = (self._ctx, ptr(kf_left), ptr(kf_right), n, ptr(cf_left), ptr(cf_right), n_cf, int(img_w), int(img_h), int(cell_size),
+                float(grid_radius), float(orient_thr_deg), ptr(R), ptr(t), C.byref(cal), C.byref(p))
+        n_cand = C.c_int64()
+        if cap is None:
+            self._check(self.lib.ebvo_tprior_candidates(*head, *(ptr(out[k]) for k in names), None, 0, C.byref(n_cand)),
+                        "ebvo_tprior_candidates")
+            cap = n_cand.value
+        out["col_idx"] = np.zeros(cap, dtype=np.int32)
+        rc = self.lib.ebvo_tprior_candidates(*head, *(ptr(out[k]) for k in names), ptr(out["col_idx"]), cap, C.byref(n_cand))
+        out["n_candidates"] = n_cand.value
+        if rc == _lib.EBVO_ERR_CAPACITY:
+            err = _lib.EbvoError(rc, "ebvo_tprior_candidates", f"{n_cand.value} candidates, room for {cap}")
+            err.n_candidates = n_cand.value
+            raise err
+        self._check(rc, "ebvo_tprior_candidates")
+        out["col_idx"] = out["col_idx"][:n_cand.value]
         return out
 
     def tgt_evaluate_rows(self, row_ptr, left_centres, right_centres, row_on, proj_left, proj_right, tp_dist: float = 2.0):

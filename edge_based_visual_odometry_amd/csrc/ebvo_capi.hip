@@ -178,7 +178,8 @@ static void slot_destroy(Slot *s)
                        &s->pose_draw,    &s->pose_hyp,       &s->pose_sel,       &s->pose_casc,       &s->pose_refit,     &s->gt_disp,        &s->gt_geom,        &s->gt_flags,
                        &s->gt_boxes,     &s->gt_pool_i32,  &s->gt_pool_idx,    &s->gt_rows,        &s->gt_tot,
                        &s->gt_up,        &s->tgt_geom,     &s->tgt_i32,        &s->tgt_idx,        &s->tgt_u8,
-                       &s->tgt_rows,     &s->tgt_flags,    &s->tgt_tot,        &s->tgt_up};
+                       &s->tgt_rows,     &s->tgt_flags,    &s->tgt_tot,        &s->tgt_up,
+                       &s->tq_prior_geom, &s->tq_prior_live};
     for (GrowBuf *b : bufs)
         free_buf(*b);
     (void)hipFree(s->d_total);
@@ -3254,6 +3255,8 @@ extern "C" int ebvo_temporal_set_keyframe(ebvo_ctx *ctx, int slot)
     EBVO_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc_f = drain_fetch(ctx, s))
         return rc_f;
+    for (Slot *o : ctx->slots) // a pending pose prior (ebvo_temporal_set_prior) was given for the keyframe that goes
+        o->tq_prior_next.on = false;
     const size_t n = (size_t)s.n_final;
     if (n > ctx->kf_cap)
     {
@@ -3575,6 +3578,39 @@ static int temporal_chain(ebvo_ctx *ctx, Slot &s, const ebvo_temporal_params &P,
     return EBVO_OK;
 }
 
+// where the arrays of a match made under a prior lie in the slot's two buffers
+static TemporalPrior temporal_prior_view(const Slot &s)
+{
+    const size_t nz = (size_t)s.tq_n_kf;
+    TemporalPrior Q;
+    Q.live = (const uint8_t *)s.tq_prior_live.p;
+    Q.pl = (const double *)s.tq_prior_geom.p;
+    Q.pr = Q.pl + 2 * nz;
+    Q.ol = Q.pr + 2 * nz;
+    Q.orr = Q.ol + nz;
+    Q.use_orientation = s.tq_prior.P.use_orientation != 0;
+    return Q;
+}
+
+// The projection of the slot's prior (s.tq_prior) for the s.tq_n_kf keyframe mates, enqueued on the slot's stream: live,
+// both projections and both mapped orientations, against the CURRENT frame's size.
+static int temporal_prior_enqueue(ebvo_ctx *ctx, Slot &s, TemporalPrior *out)
+{
+    const size_t nz = (size_t)s.tq_n_kf;
+    int rc;
+    if ((rc = ebvo_grow(ctx, s, s.tq_prior_geom, sizeof(double) * 6 * nz + 64)) || (rc = ebvo_grow(ctx, s, s.tq_prior_live, nz + 64)))
+        return rc;
+    const TemporalPrior Q = temporal_prior_view(s);
+    const Slot::TqPrior &pr = s.tq_prior;
+    if ((rc = tprior_project_enqueue(ctx, s, ctx->kf_L, ctx->kf_R, s.tq_n_kf, pr.R, pr.t, &pr.calib, pr.P.img_margin, s.cur_w, s.cur_h,
+                                     const_cast<uint8_t *>(Q.live), const_cast<double *>(Q.pl), const_cast<double *>(Q.pr),
+                                     const_cast<double *>(Q.ol), const_cast<double *>(Q.orr))))
+        return rc;
+    if (out)
+        *out = Q;
+    return EBVO_OK;
+}
+
 // Candidate quads + NCC of the slot's final mates against the keyframe's.  The buffers indexed by candidate quad are sized
 // for a CAPACITY (s.tq_cap: what the last frame needed, with headroom), every kernel takes the number of quads from the
 // device (the last entry of the scanned row offsets), and the two counts -- candidates, kept -- travel to page-locked memory
@@ -3602,9 +3638,19 @@ static int temporal_stage0_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_temporal_p
     if ((rc = ebvo_grow(ctx, s, s.tq_cells, match_temporal_grid_bytes(n_cf, gw * gh))))
         return rc;
     void *grid = s.tq_cells.p;
+    // under a pose prior (ebvo_temporal_set_prior) the projection comes first on the slot's stream, and both passes of the
+    // walk take their query points from it
+    TemporalPrior prior_q;
+    const TemporalPrior *prior = nullptr;
+    if (s.tq_prior.on)
+    {
+        if ((rc = temporal_prior_enqueue(ctx, s, &prior_q)))
+            return rc;
+        prior = &prior_q;
+    }
     if ((rc = match_temporal_cells_enqueue(ctx, s, cfL, cfR, n_cf, cell, gw, gh, grid)) ||
         (rc = match_temporal_candidates_enqueue(ctx, s, ctx->kf_L, ctx->kf_R, n_kf, cfL, cfR, grid, n_cf, cell, sr, gw, gh,
-                                                p->orient_thr_deg, cnt, nullptr, nullptr, 0)) ||
+                                                p->orient_thr_deg, cnt, nullptr, nullptr, 0, prior)) ||
         (rc = ebvo_device_scan(ctx, s, cnt, rp, n_kf, nullptr, 1, n_kf + 1)))
         return rc;
     if (size_first)
@@ -3626,7 +3672,7 @@ static int temporal_stage0_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_temporal_p
     uint8_t *cfLf = (uint8_t *)s.patches_flag.p;
     const int32_t *d_nq = rp + n_kf;
     if ((rc = match_temporal_candidates_enqueue(ctx, s, ctx->kf_L, ctx->kf_R, n_kf, cfL, cfR, grid, n_cf, cell, sr, gw, gh,
-                                                p->orient_thr_deg, nullptr, rp, col, s.tq_cap)) ||
+                                                p->orient_thr_deg, nullptr, rp, col, s.tq_cap, prior)) ||
         (rc = match_expand_rows_enqueue(ctx, s, rp, n_kf, s.tq_cap, quad_kf)) ||
         (rc = match_patches_enqueue(ctx, s, ncc_img(s, 0), h, w, w, cfL, n_cf, nullptr, 0, nullptr, cfLn, cfLf)) ||
         (rc = match_patches_enqueue(ctx, s, s.im[1].img, h, w, w, cfR, n_cf, nullptr, 0, nullptr, cfRn, flagR)) ||
@@ -3678,16 +3724,28 @@ extern "C" int ebvo_temporal_match_submit(ebvo_ctx *ctx, int slot, const ebvo_te
     s.tq_params = *p;
     s.tq_empty = ctx->kf_n == 0 || s.n_final == 0;
     s.h_tq_tot[0] = s.h_tq_tot[1] = 0;
+    // the pending prior becomes this match's; it stays pending until the submission has succeeded
+    s.tq_prior = s.tq_prior_next;
     if (s.tq_empty)
     {
-        // no quads at all: zeroed row offsets, nothing else to run
+        // no quads at all: zeroed row offsets, nothing else to run (under a prior: the projection, for ebvo_temporal_prior_fetch)
         const size_t nk1 = (size_t)ctx->kf_n + 1;
         int rc = ebvo_grow(ctx, s, s.tq_i32, sizeof(int32_t) * (2 * nk1 + 2) + 16);
         if (rc)
             return rc;
         EBVO_HIP(ctx, hipMemsetAsync(s.tq_i32.p, 0, sizeof(int32_t) * 2 * nk1, s.stream));
+        if (s.tq_prior.on)
+        {
+            const TemporalGridScope grid_scope(ctx, s);
+            if ((rc = temporal_prior_enqueue(ctx, s, nullptr)))
+            {
+                (void)hipStreamSynchronize(s.stream);
+                return rc;
+            }
+        }
         EBVO_HIP(ctx, hipEventRecord(s.ev_tq, s.stream));
         s.tq_in_flight = true;
+        s.tq_prior_next.on = false;
         return EBVO_OK;
     }
     int rc = temporal_stage0_enqueue(ctx, s, p, s.tq_cap == 0);
@@ -3697,6 +3755,7 @@ extern "C" int ebvo_temporal_match_submit(ebvo_ctx *ctx, int slot, const ebvo_te
         return rc;
     }
     s.tq_in_flight = true;
+    s.tq_prior_next.on = false;
     return EBVO_OK;
 }
 
@@ -5315,9 +5374,11 @@ extern "C" int ebvo_temporal_set_gt(ebvo_ctx *ctx, int slot, const double R[9], 
             // "Location Proximity" on the match's own grid and radius, then the trail's lists: mates by index, the last one
             // by its refined centres
             int pos = tgt_stage_pos(s, EBVO_TGT_GRID);
+            // (a match made under a pose prior searched around the prior's projections: those cells are counted)
+            const TemporalPrior prior_q = s.tq_prior.on ? temporal_prior_view(s) : TemporalPrior{};
             if ((rc = tgt_grid_rows_enqueue(ctx, s, ctx->kf_L, ctx->kf_R, n_kf, cfL, cfR, s.tq_cells.p, n_cf, cell,
                                             tgt_cell_radius(s.tq_params.grid_radius, cell), gw, gh, on, pl, pr, P.tp_dist,
-                                            rows + 2 * nz * pos, tot + 8 * pos)))
+                                            rows + 2 * nz * pos, tot + 8 * pos, s.tq_prior.on ? &prior_q : nullptr)))
                 return rc;
             for (int k = EBVO_TGT_SIFT; k <= EBVO_TGT_REFINE && T.lists; ++k)
             {
@@ -5765,6 +5826,207 @@ extern "C" int ebvo_tgt_veridical(ebvo_ctx *ctx, const ebvo_edge *kf_left, const
     EBVO_HIP(ctx, hipStreamSynchronize(st));
     if (ver_row_ptr)
         memcpy(ver_row_ptr, h_rp.data(), sizeof(int32_t) * (nz + 1));
+    return EBVO_OK;
+}
+
+// ---- temporal matching under a pose prior ---------------------------------------------------------------------------------
+extern "C" void ebvo_tprior_default_params(ebvo_tprior_params *p)
+{
+    if (!p)
+        return;
+    p->img_margin = 0.0;
+    p->use_orientation = 1;
+}
+
+static bool tprior_args_ok(const double *R, const double *t, const ebvo_stereo_calib *calib, const ebvo_tprior_params *P)
+{
+    if (!tgt_pose_ok(R, t, calib) || !(P->img_margin >= 0 && std::isfinite(P->img_margin)))
+        return false;
+    for (int k = 0; k < 9; ++k)
+        if (!std::isfinite(R[k]))
+            return false;
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(t[k]))
+            return false;
+    return true;
+}
+
+extern "C" int ebvo_temporal_set_prior(ebvo_ctx *ctx, int slot, const double R[9], const double t[3], const ebvo_stereo_calib *calib,
+                                       const ebvo_tprior_params *params)
+{
+    ebvo_tprior_params P;
+    ebvo_tprior_default_params(&P);
+    if (params)
+        P = *params;
+    Slot *sp;
+    if (get_slot(ctx, slot, &sp) || !tprior_args_ok(R, t, calib, &P))
+        return EBVO_ERR_ARG;
+    if (sp->tq_in_flight)
+    {
+        ctx->last_error = "a temporal match is in flight in the slot (ebvo_temporal_match_wait first)";
+        return EBVO_ERR_STATE;
+    }
+    Slot::TqPrior &N = sp->tq_prior_next; // read by the next ebvo_temporal_match_submit; the slot's match stays
+    N.on = true;
+    memcpy(N.R, R, sizeof N.R);
+    memcpy(N.t, t, sizeof N.t);
+    N.calib = *calib;
+    N.P = P;
+    return EBVO_OK;
+}
+
+extern "C" int ebvo_temporal_clear_prior(ebvo_ctx *ctx, int slot)
+{
+    Slot *sp;
+    if (get_slot(ctx, slot, &sp))
+        return EBVO_ERR_ARG;
+    if (sp->tq_in_flight)
+    {
+        ctx->last_error = "a temporal match is in flight in the slot (ebvo_temporal_match_wait first)";
+        return EBVO_ERR_STATE;
+    }
+    sp->tq_prior_next.on = false;
+    return EBVO_OK;
+}
+
+extern "C" int ebvo_temporal_prior_fetch(ebvo_ctx *ctx, int slot, uint8_t *live, double *proj_left, double *proj_right,
+                                         double *orient_left, double *orient_right)
+{
+    Slot *sp;
+    if (get_slot(ctx, slot, &sp))
+        return EBVO_ERR_ARG;
+    Slot &s = *sp;
+    if (s.tq_n < 0 || s.in_flight || s.tq_in_flight || !s.tq_prior.on)
+    {
+        ctx->last_error = s.in_flight || s.tq_in_flight ? "the slot has work in flight (wait for it first)"
+                          : s.tq_n < 0                  ? "the slot holds no temporal match (ebvo_temporal_match first)"
+                                                        : "the slot's match was made without a prior (ebvo_temporal_set_prior before the match)";
+        return EBVO_ERR_STATE;
+    }
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nz = (size_t)s.tq_n_kf;
+    if (!nz)
+        return EBVO_OK;
+    const TemporalPrior Q = temporal_prior_view(s);
+    const struct
+    {
+        void *dst;
+        const void *src;
+        size_t bytes;
+    } copies[] = {{live, Q.live, nz}, {proj_left, Q.pl, sizeof(double) * 2 * nz}, {proj_right, Q.pr, sizeof(double) * 2 * nz},
+                  {orient_left, Q.ol, sizeof(double) * nz}, {orient_right, Q.orr, sizeof(double) * nz}};
+    for (const auto &c : copies)
+        if (c.dst)
+            EBVO_HIP(ctx, hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, s.stream));
+    EBVO_HIP(ctx, hipStreamSynchronize(s.stream));
+    return EBVO_OK;
+}
+
+extern "C" int ebvo_tprior_candidates(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *kf_right, int n_kf,
+                                      const ebvo_edge *cf_left, const ebvo_edge *cf_right, int n_cf, int img_w, int img_h, int cell_size,
+                                      double grid_radius, double orient_thr_deg, const double R[9], const double t[3],
+                                      const ebvo_stereo_calib *calib, const ebvo_tprior_params *params, uint8_t *live, double *proj_left,
+                                      double *proj_right, double *orient_left, double *orient_right, int32_t *row_ptr, int32_t *col_idx,
+                                      int64_t cap, int64_t *n_candidates)
+{
+    ebvo_tprior_params P;
+    ebvo_tprior_default_params(&P);
+    if (params)
+        P = *params;
+    if (!ctx || n_kf < 0 || n_cf < 0 || img_w < 1 || img_h < 1 || cell_size < 1 || cap < 0 ||
+        !(grid_radius >= 0 && std::isfinite(grid_radius)) || !(orient_thr_deg >= 0) || !tprior_args_ok(R, t, calib, &P) ||
+        (n_kf > 0 && (!kf_left || !kf_right)) || (n_cf > 0 && (!cf_left || !cf_right)))
+        return EBVO_ERR_ARG;
+    const int64_t gw64 = ((int64_t)img_w + cell_size - 1) / cell_size, gh64 = ((int64_t)img_h + cell_size - 1) / cell_size;
+    if (gw64 * gh64 > (1 << 26) || gw64 > 30000 || gh64 > 30000) // the cells of a mate are 16-bit
+        return EBVO_ERR_ARG;
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    int rc;
+    Slot *sp;
+    if ((rc = gt_host_slot(ctx, &sp)))
+        return rc;
+    Slot &s = *sp;
+    if (n_candidates)
+        *n_candidates = 0;
+    const int gw = (int)gw64, gh = (int)gh64;
+    const size_t nz = (size_t)n_kf, ncz = (size_t)n_cf;
+    // one buffer of the call's own: mates, the six doubles per keyframe mate, counts and offsets, live, the grid, the list
+    const size_t o_kfR = sizeof(ebvo_edge) * nz, o_cfL = 2 * sizeof(ebvo_edge) * nz, o_cfR = o_cfL + sizeof(ebvo_edge) * ncz,
+                 o_geom = o_cfR + sizeof(ebvo_edge) * ncz, o_i32 = o_geom + sizeof(double) * 6 * nz,
+                 o_u8 = o_i32 + sizeof(int32_t) * 2 * (nz + 1), o_grid = (o_u8 + nz + 63) & ~(size_t)63,
+                 o_idx = (o_grid + match_temporal_grid_bytes(n_cf, gw * gh) + 63) & ~(size_t)63;
+    const size_t idx_room = sizeof(int32_t) * (size_t)((cap < (int64_t)nz * ncz ? cap : (int64_t)nz * ncz) + 1);
+    if ((rc = gt_grow(ctx, s, s.tgt_up, o_idx + idx_room)))
+        return rc;
+    hipStream_t st = s.stream;
+    char *base = (char *)s.tgt_up.p;
+    ebvo_edge *kfL = (ebvo_edge *)base, *kfR = (ebvo_edge *)(base + o_kfR), *cfL = (ebvo_edge *)(base + o_cfL), *cfR = (ebvo_edge *)(base + o_cfR);
+    double *pl = (double *)(base + o_geom), *pr = pl + 2 * nz, *ol = pr + 2 * nz, *orr = ol + nz;
+    int32_t *cnt = (int32_t *)(base + o_i32), *rp = cnt + nz + 1;
+    uint8_t *lv = (uint8_t *)(base + o_u8);
+    TemporalPrior Q;
+    Q.live = lv; Q.pl = pl; Q.pr = pr; Q.ol = ol; Q.orr = orr;
+    Q.use_orientation = P.use_orientation != 0;
+    std::vector<int32_t> h_cnt(nz + 1, 0), h_rp;
+    int32_t n_rows = 0;
+    EBVO_HIP(ctx, hipMemsetAsync(cnt, 0, sizeof(int32_t) * 2 * (nz + 1), st));
+    if (n_kf)
+    {
+        EBVO_HIP(ctx, hipMemcpyAsync(kfL, kf_left, sizeof(ebvo_edge) * nz, hipMemcpyHostToDevice, st));
+        EBVO_HIP(ctx, hipMemcpyAsync(kfR, kf_right, sizeof(ebvo_edge) * nz, hipMemcpyHostToDevice, st));
+        if ((rc = tprior_project_enqueue(ctx, s, kfL, kfR, n_kf, R, t, calib, P.img_margin, img_w, img_h, lv, pl, pr, ol, orr)))
+            return rc;
+    }
+    const bool walk = n_kf > 0 && n_cf > 0;
+    const int sr = tgt_cell_radius(grid_radius, cell_size);
+    if (walk)
+    {
+        EBVO_HIP(ctx, hipMemcpyAsync(cfL, cf_left, sizeof(ebvo_edge) * ncz, hipMemcpyHostToDevice, st));
+        EBVO_HIP(ctx, hipMemcpyAsync(cfR, cf_right, sizeof(ebvo_edge) * ncz, hipMemcpyHostToDevice, st));
+        if ((rc = match_temporal_cells_enqueue(ctx, s, cfL, cfR, n_cf, cell_size, gw, gh, base + o_grid)) ||
+            (rc = match_temporal_candidates_enqueue(ctx, s, kfL, kfR, n_kf, cfL, cfR, base + o_grid, n_cf, cell_size, sr, gw, gh,
+                                                    orient_thr_deg, cnt, nullptr, nullptr, 0, &Q)))
+            return rc;
+        EBVO_HIP(ctx, hipMemcpyAsync(h_cnt.data(), cnt, sizeof(int32_t) * nz, hipMemcpyDeviceToHost, st));
+    }
+    EBVO_HIP(ctx, hipStreamSynchronize(st));
+    if (!tgt_row_offsets(h_cnt, n_kf, h_rp, &n_rows))
+    {
+        ctx->last_error = "more candidate quads than a 32-bit row offset holds";
+        return EBVO_ERR_CAPACITY;
+    }
+    const int64_t n_cand = h_rp[n_kf];
+    if (n_candidates)
+        *n_candidates = n_cand;
+    if (col_idx && n_cand > cap)
+    {
+        ctx->last_error = "ebvo_tprior_candidates: " + std::to_string(n_cand) + " candidate quads";
+        return EBVO_ERR_CAPACITY;
+    }
+    if (walk && col_idx && n_cand > 0)
+    {
+        EBVO_HIP(ctx, hipMemcpyAsync(rp, h_rp.data(), sizeof(int32_t) * (nz + 1), hipMemcpyHostToDevice, st));
+        if ((rc = match_temporal_candidates_enqueue(ctx, s, kfL, kfR, n_kf, cfL, cfR, base + o_grid, n_cf, cell_size, sr, gw, gh,
+                                                    orient_thr_deg, nullptr, rp, (int32_t *)(base + o_idx), n_cand, &Q)))
+            return rc;
+        EBVO_HIP(ctx, hipMemcpyAsync(col_idx, base + o_idx, sizeof(int32_t) * (size_t)n_cand, hipMemcpyDeviceToHost, st));
+    }
+    if (nz)
+    {
+        const struct
+        {
+            void *dst;
+            const void *src;
+            size_t bytes;
+        } copies[] = {{live, lv, nz}, {proj_left, pl, sizeof(double) * 2 * nz}, {proj_right, pr, sizeof(double) * 2 * nz},
+                      {orient_left, ol, sizeof(double) * nz}, {orient_right, orr, sizeof(double) * nz}};
+        for (const auto &c : copies)
+            if (c.dst)
+                EBVO_HIP(ctx, hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, st));
+    }
+    EBVO_HIP(ctx, hipStreamSynchronize(st));
+    if (row_ptr)
+        memcpy(row_ptr, h_rp.data(), sizeof(int32_t) * (nz + 1));
     return EBVO_OK;
 }
 

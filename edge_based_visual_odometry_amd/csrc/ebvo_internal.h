@@ -102,6 +102,15 @@ struct PairResult
     int32_t pad;
 };
 
+// What a keyframe mate's search is centred on under a pose prior (ebvo_temporal_set_prior): device arrays per keyframe mate,
+// written by tprior_project_enqueue.  use_orientation: the orientation test compares ol / orr in place of the mate's own theta.
+struct TemporalPrior
+{
+    const uint8_t *live = nullptr;
+    const double *pl = nullptr, *pr = nullptr, *ol = nullptr, *orr = nullptr;
+    int use_orientation = 0;
+};
+
 struct ProfEvent
 {
     hipEvent_t a, b;
@@ -217,6 +226,17 @@ struct Slot
         int64_t n[4] = {0, 0, 0, 0};
     } tq_trail;
     bool tq_keep = false; // the switch: read by the next ebvo_temporal_match_submit
+    // ebvo_temporal_set_prior: the pose the NEXT match of the slot searches under (one-shot: a successful submit moves it
+    // into tq_prior), and the pose the slot's present match was made under.  tq_prior_geom: pl [n][2], pr [n][2], ol [n],
+    // orr [n] of that match; tq_prior_live: its live bytes.  They stay until the match is replaced.
+    struct TqPrior
+    {
+        bool on = false;
+        double R[9] = {0}, t[3] = {0};
+        ebvo_stereo_calib calib{};
+        ebvo_tprior_params P{};
+    } tq_prior_next, tq_prior;
+    GrowBuf tq_prior_geom, tq_prior_live;
     int tq_n_kf = 0;
     int64_t tq_n = -1;                       // -1: none
     // ebvo_temporal_match_submit / _wait: the candidate and NCC stages are enqueued for a capacity of quads (what the last
@@ -508,7 +528,7 @@ size_t match_temporal_grid_bytes(int n_cf, int n_cells);
 int match_temporal_candidates_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, int n_kf,
                                       const ebvo_edge *d_cfL, const ebvo_edge *d_cfR, const void *d_grid, int n_cf, int cell,
                                       int sr, int gw, int gh, double orient_thr, int32_t *d_cnt, const int32_t *d_row_ptr,
-                                      int32_t *d_col_idx, int64_t cap);
+                                      int32_t *d_col_idx, int64_t cap, const TemporalPrior *prior = nullptr);
 // where the three arrays a query reads lie inside a grid buffer of match_temporal_cells_enqueue
 void match_temporal_grid_view(const void *d_grid, int n_cf, int n_cells, const MateCells **cells, const int32_t **cell_start,
                               const int32_t **cell_list);
@@ -647,9 +667,16 @@ int tgt_veridical_enqueue(ebvo_ctx *ctx, Slot &s, int n_kf, const uint8_t *d_in,
 // (n, tp) per row of a CSR list of quads (centres d_cenL[k] / d_cenR[k], or d_cfL / d_cfR [d_col_idx[k]]; d_keep optional),
 // the per-quad b_is_TP byte (0 for a quad outside the list or on a row that is off) and the five integer totals
 // the grid stage ("Location Proximity") without its list: (n, tp) of every keyframe mate whose row is on, and the stage totals
+// prior != nullptr: the match searched under a pose prior -- the query cells are its projections', a mate that is not live has (0, 0)
 int tgt_grid_rows_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, int n_kf, const ebvo_edge *d_cfL,
                           const ebvo_edge *d_cfR, const void *d_grid, int n_cf, int cell, int sr, int gw, int gh, const uint8_t *d_on,
-                          const double *d_pl, const double *d_pr, double tp_dist, int32_t *d_rows, unsigned long long *d_tot);
+                          const double *d_pl, const double *d_pr, double tp_dist, int32_t *d_rows, unsigned long long *d_tot,
+                          const TemporalPrior *prior = nullptr);
+// the projection of a pose prior (ebvo_temporal_set_prior): tgt_project's arithmetic on the triangulated points, d_live = in the
+// image (one width and height for both cameras) and in front of both cameras
+int tprior_project_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, int n_kf, const double *R,
+                           const double *t, const ebvo_stereo_calib *calib, double margin, int img_w, int img_h, uint8_t *d_live,
+                           double *d_pl, double *d_pr, double *d_ol, double *d_or);
 int tgt_rows_enqueue(ebvo_ctx *ctx, Slot &s, const int32_t *d_row_ptr, const ebvo_edge *d_cenL, const ebvo_edge *d_cenR,
                      const int32_t *d_col_idx, const ebvo_edge *d_cfL, const ebvo_edge *d_cfR, const uint8_t *d_keep,
                      const double *d_pl, const double *d_pr, const uint8_t *d_on, int n_kf, int64_t n_quads, double tp_dist,

@@ -1737,7 +1737,11 @@ __global__ __launch_bounds__(256) void cell_sort_kernel(const int32_t *__restric
 // sixteen lanes per keyframe mate: lane e tests every sixteenth mate of a cell's segment, the survivors of a step are
 // ranked by a ballot so that the row keeps the order of the segment (one thread per mate walked ~900 dependent
 // look-ups in a row: 350 us per pass at EuRoC size)
-template <bool FILL>
+// PRIOR = false: the query points are the keyframe mate's own edges (the reference's search).  PRIOR = true
+// (ebvo_temporal_set_prior): they are the mate's projections through the predicted pose, Q.pl / Q.pr; a mate with
+// Q.live == 0 walks nothing and has an empty row; with Q.use_orientation the orientation test compares the mapped
+// orientations Q.ol / Q.orr in place of the mate's own.  Q is not read when PRIOR is false.
+template <bool FILL, bool PRIOR>
 __global__ __launch_bounds__(256) void temporal_candidates_kernel(const ebvo_edge *__restrict__ kfL,
                                                                   const ebvo_edge *__restrict__ kfR, int n_kf,
                                                                   const ebvo_edge *__restrict__ cfL,
@@ -1747,7 +1751,7 @@ __global__ __launch_bounds__(256) void temporal_candidates_kernel(const ebvo_edg
                                                                   const int32_t *__restrict__ cell_list, int cell, int sr, int gw,
                                                                   int gh, double orient_thr, int32_t *__restrict__ cnt,
                                                                   const int32_t *__restrict__ row_ptr,
-                                                                  int32_t *__restrict__ col_idx, int64_t cap)
+                                                                  int32_t *__restrict__ col_idx, int64_t cap, TemporalPrior Q)
 {
     const int lane = threadIdx.x & 63, e = lane & 15, gshift = lane & 48;
     const int groups = (gridDim.x * blockDim.x) >> 4;
@@ -1755,17 +1759,29 @@ __global__ __launch_bounds__(256) void temporal_candidates_kernel(const ebvo_edg
     for (int w0 = ((blockIdx.x * blockDim.x + threadIdx.x) >> 6) * 4; w0 < n_kf; w0 += groups)
     {
         const int i0 = w0 + (lane >> 4);
-        const bool live = i0 < n_kf;
-        const int i = live ? i0 : 0;
+        const bool have = i0 < n_kf;
+        const int i = have ? i0 : 0;
+        const bool live = have && (!PRIOR || Q.live[i] != 0);
         const ebvo_edge kl = kfL[i], kr = kfR[i];
         // the query cells are not clipped (include/Dataset.h:95-96); neighbour cells outside the grid hold nothing, so the
         // walk visits only the neighbours inside the grid, in the reference's order (dy outer, dx inner).  The bounds are
         // uniform over a group of sixteen lanes; the ballots below only read the group's own bits.
-        const int qlx = (int)kl.x / cell, qly = (int)kl.y / cell, qrx = (int)kr.x / cell, qry = (int)kr.y / cell;
+        int qlx, qly, qrx, qry;
+        double th_l = kl.theta, th_r = kr.theta;
+        if (PRIOR)
+        {
+            // a live mate's projections lie inside the image, so the casts are defined
+            qlx = live ? (int)Q.pl[(size_t)i * 2] / cell : 0, qly = live ? (int)Q.pl[(size_t)i * 2 + 1] / cell : 0;
+            qrx = live ? (int)Q.pr[(size_t)i * 2] / cell : 0, qry = live ? (int)Q.pr[(size_t)i * 2 + 1] / cell : 0;
+            if (Q.use_orientation)
+                th_l = Q.ol[i], th_r = Q.orr[i];
+        }
+        else
+            qlx = (int)kl.x / cell, qly = (int)kl.y / cell, qrx = (int)kr.x / cell, qry = (int)kr.y / cell;
         const int dy0 = max(-sr, -qly), dy1 = live ? min(sr, gh - 1 - qly) : dy0 - 1;
         const int dx0 = max(-sr, -qlx), dx1 = min(sr, gw - 1 - qlx);
         int c = 0;
-        int64_t o = (FILL && live) ? row_ptr[i] : 0;
+        int64_t o = (FILL && have) ? row_ptr[i] : 0;
         for (int dy = dy0; dy <= dy1; ++dy)
             for (int dx = dx0; dx <= dx1; ++dx)
             {
@@ -1784,8 +1800,8 @@ __global__ __launch_bounds__(256) void temporal_candidates_kernel(const ebvo_edg
                         // right_set.count(cf_idx): the mate's right edge is in the right grid (mate_cells_kernel leaves
                         // both right cells negative otherwise) and in a neighbour cell of the right query
                         const bool r_in_grid = m.rx >= 0;
-                        ok = r_in_grid && abs(m.rx - qrx) <= sr && abs(m.ry - qry) <= sr && orient_close(kl.theta, cfL[j].theta, orient_thr) &&
-                             orient_close(kr.theta, cfR[j].theta, orient_thr);
+                        ok = r_in_grid && abs(m.rx - qrx) <= sr && abs(m.ry - qry) <= sr && orient_close(th_l, cfL[j].theta, orient_thr) &&
+                             orient_close(th_r, cfR[j].theta, orient_thr);
                     }
                     const unsigned hits = (unsigned)((__ballot(ok) >> gshift) & 0xffffull);
                     if (FILL && ok)
@@ -1799,7 +1815,7 @@ __global__ __launch_bounds__(256) void temporal_candidates_kernel(const ebvo_edg
                     o += nh;
                 }
             }
-        if (!FILL && live && e == 0)
+        if (!FILL && have && e == 0)
             cnt[i] = c;
     }
 }
@@ -2489,19 +2505,29 @@ int match_temporal_cells_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_cfL,
 int match_temporal_candidates_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, int n_kf,
                                       const ebvo_edge *d_cfL, const ebvo_edge *d_cfR, const void *d_grid, int n_cf, int cell,
                                       int sr, int gw, int gh, double orient_thr, int32_t *d_cnt, const int32_t *d_row_ptr,
-                                      int32_t *d_col_idx, int64_t cap)
+                                      int32_t *d_col_idx, int64_t cap, const TemporalPrior *prior)
 {
     if (n_kf <= 0)
         return EBVO_OK;
     ProfScope ps(ctx, s, d_row_ptr ? K_CAND_FILL : K_CAND_COUNT);
     const TemporalGrid g = temporal_grid(const_cast<void *>(d_grid), n_cf, gw * gh);
     const unsigned nb = chain_grid_cap(s, blocks_for(n_kf, 16, 8192)); // 16 mates per block of 256 threads
-    if (d_row_ptr)
-        hipLaunchKernelGGL(temporal_candidates_kernel<true>, dim3(nb), dim3(256), 0, s.stream, d_kfL, d_kfR, n_kf, d_cfL, d_cfR,
-                           g.cells, g.start, g.sorted, cell, sr, gw, gh, orient_thr, d_cnt, d_row_ptr, d_col_idx, cap);
+    const TemporalPrior Q = prior ? *prior : TemporalPrior{};
+#define EBVO_TCAND_LAUNCH(FILL, PRIOR)                                                                                                     \
+    hipLaunchKernelGGL((temporal_candidates_kernel<FILL, PRIOR>), dim3(nb), dim3(256), 0, s.stream, d_kfL, d_kfR, n_kf, d_cfL, d_cfR,       \
+                       g.cells, g.start, g.sorted, cell, sr, gw, gh, orient_thr, d_cnt, d_row_ptr, d_col_idx, cap, Q)
+    if (prior)
+    {
+        if (d_row_ptr)
+            EBVO_TCAND_LAUNCH(true, true);
+        else
+            EBVO_TCAND_LAUNCH(false, true);
+    }
+    else if (d_row_ptr)
+        EBVO_TCAND_LAUNCH(true, false);
     else
-        hipLaunchKernelGGL(temporal_candidates_kernel<false>, dim3(nb), dim3(256), 0, s.stream, d_kfL, d_kfR, n_kf, d_cfL, d_cfR,
-                           g.cells, g.start, g.sorted, cell, sr, gw, gh, orient_thr, d_cnt, d_row_ptr, d_col_idx, cap);
+        EBVO_TCAND_LAUNCH(false, false);
+#undef EBVO_TCAND_LAUNCH
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
 }

@@ -6,7 +6,8 @@
 //   SpatialGrid::getCandidatesWithinRadius(cv::Point2d, r)       include/Dataset.h:92-113
 //   Temporal_Matches::Evaluate_Temporal_Edge_Pairs_on_Quads      src/Temporal_Matches.cpp:220-292 (per-row counts)
 //
-// tgt_project: one thread per keyframe mate.  tgt_veridical: sixteen lanes per keyframe mate walk the grid cells of the
+// tgt_project: one thread per keyframe mate (its second instantiation is the projection of a pose prior,
+// ebvo_temporal_set_prior: the same arithmetic plus a depth test).  tgt_veridical: sixteen lanes per keyframe mate walk the grid cells of the
 // current-frame mates that match_kernels.hip builds (the layout and the order of temporal_candidates_kernel: dy outer, dx
 // inner, ascending mate index within a cell; a ballot ranks the survivors of a step).  tgt_rows: eight lanes per row of a
 // CSR list of quads.  tgt_grid_rows: the grid stage of the chain (apply_spatial_grid_filtering_quads, :335-383), which
@@ -50,8 +51,53 @@ __device__ inline double mapped_orientation(const double *T2, const double *p, c
     return ebvo_atan2(t2d[1], t2d[0]);
 }
 
-// :82-105 per keyframe mate.  The orientations are computed before the margin test, as there.  A projection with a NaN
-// coordinate is not in the image (the reference would cast it to an int, which is undefined).
+// :82-105 for one keyframe mate: both projections (over their own z), both mapped orientations and the two camera-frame
+// points.  Shared by tgt_project_kernel and tprior_project_kernel, so that the prior stage searches at exactly the points
+// the ground truth evaluates.
+struct MateProjection
+{
+    double ql[3], qr[3], ol, orr, Gc[3], Gr[3];
+};
+
+__device__ inline void project_mate(const TgtPose &P, const ebvo_edge &kl, const ebvo_edge &kr, const double *gamma_i, MateProjection &m)
+{
+    double G[3], T1[3], g1[3], g2[3];
+    stereo_gamma_tangent(P.C, kl, kr, G, T1, g1, g2); // T_1 of :312; G: the triangulated Gamma
+    if (gamma_i)
+    {
+        G[0] = gamma_i[0];
+        G[1] = gamma_i[1];
+        G[2] = gamma_i[2];
+    }
+    double T2l[3], T2r[3];
+    mv3(P.R, G, m.Gc); // :83
+    m.Gc[0] += P.t[0];
+    m.Gc[1] += P.t[1];
+    m.Gc[2] += P.t[2];
+    project3(P.Kl, m.Gc, m.ql);
+    mv3(P.C.R21, m.Gc, m.Gr); // :87
+    m.Gr[0] += P.C.T21[0];
+    m.Gr[1] += P.C.T21[1];
+    m.Gr[2] += P.C.T21[2];
+    project3(P.Kr, m.Gr, m.qr);
+    mv3(P.R, T1, T2l);    // :317
+    mv3(P.R21R, T1, T2r); // :321
+    m.ol = mapped_orientation(T2l, m.ql, P.C.Kli);
+    m.orr = mapped_orientation(T2r, m.qr, P.C.Kri);
+}
+
+// :100-105, both cameras against ONE width and height.  A projection with a NaN coordinate is not in the image (the
+// reference would cast it to an int, which is undefined); neither is an infinite one.
+__device__ inline bool projections_inside(const MateProjection &m, double margin, double x_max, double y_max)
+{
+    return m.ql[0] > margin && m.ql[1] > margin && m.ql[0] < x_max && m.ql[1] < y_max && m.qr[0] > margin && m.qr[1] > margin &&
+           m.qr[0] < x_max && m.qr[1] < y_max;
+}
+
+// :82-105 per keyframe mate.  The orientations are computed before the margin test, as there.
+// DEPTH = false: the ground truth's in_image.  DEPTH = true (the pose prior of ebvo_temporal_set_prior): the byte is `live`,
+// which also asks for a positive depth in both cameras -- a point behind a camera projects into the image mirrored.
+template <bool DEPTH>
 __global__ __launch_bounds__(256) void tgt_project_kernel(const ebvo_edge *__restrict__ kfL, const ebvo_edge *__restrict__ kfR,
                                                           const double *__restrict__ gamma, int n, TgtPose P, double margin,
                                                           double x_max, double y_max, uint8_t *__restrict__ in_image,
@@ -60,36 +106,17 @@ __global__ __launch_bounds__(256) void tgt_project_kernel(const ebvo_edge *__res
 {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
     {
-        double G[3], T1[3], g1[3], g2[3];
-        stereo_gamma_tangent(P.C, kfL[i], kfR[i], G, T1, g1, g2); // T_1 of :312; G: the triangulated Gamma
-        if (gamma)
-        {
-            G[0] = gamma[(size_t)i * 3];
-            G[1] = gamma[(size_t)i * 3 + 1];
-            G[2] = gamma[(size_t)i * 3 + 2];
-        }
-        double Gc[3], Gr[3], ql[3], qr[3], T2l[3], T2r[3];
-        mv3(P.R, G, Gc); // :83
-        Gc[0] += P.t[0];
-        Gc[1] += P.t[1];
-        Gc[2] += P.t[2];
-        project3(P.Kl, Gc, ql);
-        mv3(P.C.R21, Gc, Gr); // :87
-        Gr[0] += P.C.T21[0];
-        Gr[1] += P.C.T21[1];
-        Gr[2] += P.C.T21[2];
-        project3(P.Kr, Gr, qr);
-        mv3(P.R, T1, T2l);    // :317
-        mv3(P.R21R, T1, T2r); // :321
-        ol[i] = mapped_orientation(T2l, ql, P.C.Kli);
-        orr[i] = mapped_orientation(T2r, qr, P.C.Kri);
-        pl[(size_t)i * 2] = ql[0];
-        pl[(size_t)i * 2 + 1] = ql[1];
-        pr[(size_t)i * 2] = qr[0];
-        pr[(size_t)i * 2 + 1] = qr[1];
-        // :100-105, both cameras against the LEFT width and height
-        const bool inside = ql[0] > margin && ql[1] > margin && ql[0] < x_max && ql[1] < y_max && qr[0] > margin && qr[1] > margin &&
-                            qr[0] < x_max && qr[1] < y_max;
+        MateProjection m;
+        project_mate(P, kfL[i], kfR[i], gamma ? gamma + (size_t)i * 3 : nullptr, m);
+        ol[i] = m.ol;
+        orr[i] = m.orr;
+        pl[(size_t)i * 2] = m.ql[0];
+        pl[(size_t)i * 2 + 1] = m.ql[1];
+        pr[(size_t)i * 2] = m.qr[0];
+        pr[(size_t)i * 2 + 1] = m.qr[1];
+        bool inside = projections_inside(m, margin, x_max, y_max);
+        if (DEPTH)
+            inside = inside && m.Gc[2] > 0.0 && m.Gr[2] > 0.0;
         in_image[i] = inside ? 1 : 0;
     }
 }
@@ -235,13 +262,17 @@ __global__ __launch_bounds__(256) void tgt_rows_kernel(const int32_t *__restrict
 // a current-frame mate counted when its right cell is in the right grid and within sr cells of the right query cell.
 // Every counted mate is a quad of the row; it is a true positive when both its edges lie < tp_dist from the row's
 // projections.  A row that is off walks nothing and writes (0, 0).
+// PRIOR = true: the match searched under a pose prior (ebvo_temporal_set_prior), so the query cells are those of the
+// prior's projections Q.pl / Q.pr and a mate that was not live walked nothing: its row is (0, 0).
+template <bool PRIOR>
 __global__ __launch_bounds__(256) void tgt_grid_rows_kernel(const ebvo_edge *__restrict__ kfL, const ebvo_edge *__restrict__ kfR,
                                                             int n_kf, const ebvo_edge *__restrict__ cfL,
                                                             const ebvo_edge *__restrict__ cfR, const MateCells *__restrict__ cells,
                                                             const int32_t *__restrict__ cell_start,
                                                             const int32_t *__restrict__ cell_list, int cell, int sr, int gw, int gh,
                                                             const uint8_t *__restrict__ on, const double *__restrict__ pl,
-                                                            const double *__restrict__ pr, double tp_dist, int32_t *__restrict__ out)
+                                                            const double *__restrict__ pr, double tp_dist, int32_t *__restrict__ out,
+                                                            TemporalPrior Q)
 {
     const int lane = threadIdx.x & 63, e = lane & 15, gshift = lane & 48;
     const int groups = (gridDim.x * blockDim.x) >> 4;
@@ -252,10 +283,20 @@ __global__ __launch_bounds__(256) void tgt_grid_rows_kernel(const ebvo_edge *__r
         const int i0 = w0 + (lane >> 4);
         const bool have = i0 < n_kf;
         const int i = have ? i0 : 0;
-        const bool live = have && on[i] != 0;
-        const ebvo_edge kl = kfL[i], kr = kfR[i];
+        const bool live = have && on[i] != 0 && (!PRIOR || Q.live[i] != 0);
         const double plx = pl[(size_t)i * 2], ply = pl[(size_t)i * 2 + 1], prx = pr[(size_t)i * 2], pry = pr[(size_t)i * 2 + 1];
-        const int qlx = (int)kl.x / cell, qly = (int)kl.y / cell, qrx = (int)kr.x / cell, qry = (int)kr.y / cell;
+        int qlx, qly, qrx, qry;
+        if (PRIOR)
+        {
+            // a live mate's projections lie inside the image: the casts are defined
+            qlx = live ? (int)Q.pl[(size_t)i * 2] / cell : 0, qly = live ? (int)Q.pl[(size_t)i * 2 + 1] / cell : 0;
+            qrx = live ? (int)Q.pr[(size_t)i * 2] / cell : 0, qry = live ? (int)Q.pr[(size_t)i * 2 + 1] / cell : 0;
+        }
+        else
+        {
+            const ebvo_edge kl = kfL[i], kr = kfR[i];
+            qlx = (int)kl.x / cell, qly = (int)kl.y / cell, qrx = (int)kr.x / cell, qry = (int)kr.y / cell;
+        }
         const int dy0 = max(-sr, -qly), dy1 = live ? min(sr, gh - 1 - qly) : dy0 - 1;
         const int dx0 = max(-sr, -qlx), dx1 = min(sr, gw - 1 - qlx);
         int n = 0, tp = 0;
@@ -303,12 +344,8 @@ int tgt_grid(const ebvo_ctx *ctx, int64_t items, int per_block)
 
 } // namespace
 
-int tgt_project_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, const double *d_gamma, int n_kf,
-                        const double *R, const double *t, const ebvo_stereo_calib *calib, double margin, int img_w, int img_h,
-                        uint8_t *d_in, double *d_pl, double *d_pr, double *d_ol, double *d_or)
+static TgtPose tgt_pose_host(const double *R, const double *t, const ebvo_stereo_calib *calib)
 {
-    if (n_kf <= 0)
-        return EBVO_OK;
     TgtPose P;
     P.C = final_calib_host(calib->K_left, calib->K_right, calib->R21, calib->T21);
     for (int k = 0; k < 9; ++k)
@@ -322,10 +359,36 @@ int tgt_project_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const eb
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j)
             P.R21R[i * 3 + j] = (calib->R21[i * 3] * R[j] + calib->R21[i * 3 + 1] * R[3 + j]) + calib->R21[i * 3 + 2] * R[6 + j];
+    return P;
+}
+
+int tgt_project_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, const double *d_gamma, int n_kf,
+                        const double *R, const double *t, const ebvo_stereo_calib *calib, double margin, int img_w, int img_h,
+                        uint8_t *d_in, double *d_pl, double *d_pr, double *d_ol, double *d_or)
+{
+    if (n_kf <= 0)
+        return EBVO_OK;
+    const TgtPose P = tgt_pose_host(R, t, calib);
     ProfScope ps(ctx, s, K_TGT_PROJECT);
     // get_left_width() - img_margin (:101): the same bound for both cameras
-    hipLaunchKernelGGL(tgt_project_kernel, dim3(tgt_grid(ctx, n_kf, 256)), dim3(256), 0, s.stream, d_kfL, d_kfR, d_gamma, n_kf, P, margin,
-                       (double)img_w - margin, (double)img_h - margin, d_in, d_pl, d_pr, d_ol, d_or);
+    hipLaunchKernelGGL(tgt_project_kernel<false>, dim3(tgt_grid(ctx, n_kf, 256)), dim3(256), 0, s.stream, d_kfL, d_kfR, d_gamma, n_kf, P,
+                       margin, (double)img_w - margin, (double)img_h - margin, d_in, d_pl, d_pr, d_ol, d_or);
+    EBVO_HIP(ctx, hipGetLastError());
+    return EBVO_OK;
+}
+
+int tprior_project_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, int n_kf, const double *R,
+                           const double *t, const ebvo_stereo_calib *calib, double margin, int img_w, int img_h, uint8_t *d_live,
+                           double *d_pl, double *d_pr, double *d_ol, double *d_or)
+{
+    if (n_kf <= 0)
+        return EBVO_OK;
+    const TgtPose P = tgt_pose_host(R, t, calib);
+    ProfScope ps(ctx, s, K_TGT_PROJECT);
+    // inside temporal_stage0_enqueue developer key 22 caps the grid as it caps every other launch of the chain
+    hipLaunchKernelGGL(tgt_project_kernel<true>, dim3(chain_grid_cap(s, (unsigned)tgt_grid(ctx, n_kf, 256))), dim3(256), 0, s.stream, d_kfL,
+                       d_kfR, (const double *)nullptr, n_kf, P, margin, (double)img_w - margin, (double)img_h - margin, d_live, d_pl, d_pr,
+                       d_ol, d_or);
     EBVO_HIP(ctx, hipGetLastError());
     return EBVO_OK;
 }
@@ -356,7 +419,8 @@ int tgt_veridical_enqueue(ebvo_ctx *ctx, Slot &s, int n_kf, const uint8_t *d_in,
 
 int tgt_grid_rows_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, int n_kf, const ebvo_edge *d_cfL,
                           const ebvo_edge *d_cfR, const void *d_grid, int n_cf, int cell, int sr, int gw, int gh, const uint8_t *d_on,
-                          const double *d_pl, const double *d_pr, double tp_dist, int32_t *d_rows, unsigned long long *d_tot)
+                          const double *d_pl, const double *d_pr, double tp_dist, int32_t *d_rows, unsigned long long *d_tot,
+                          const TemporalPrior *prior)
 {
     if (n_kf > 0)
     {
@@ -364,8 +428,13 @@ int tgt_grid_rows_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const 
         const int32_t *cell_start, *cell_list;
         match_temporal_grid_view(d_grid, n_cf, gw * gh, &cells, &cell_start, &cell_list);
         ProfScope ps(ctx, s, K_TGT_GRID);
-        hipLaunchKernelGGL(tgt_grid_rows_kernel, dim3(tgt_grid(ctx, n_kf, 16)), dim3(256), 0, s.stream, d_kfL, d_kfR, n_kf, d_cfL, d_cfR,
-                           cells, cell_start, cell_list, cell, sr, gw, gh, d_on, d_pl, d_pr, tp_dist, d_rows);
+        const dim3 grid(tgt_grid(ctx, n_kf, 16));
+        if (prior)
+            hipLaunchKernelGGL(tgt_grid_rows_kernel<true>, grid, dim3(256), 0, s.stream, d_kfL, d_kfR, n_kf, d_cfL, d_cfR, cells, cell_start,
+                               cell_list, cell, sr, gw, gh, d_on, d_pl, d_pr, tp_dist, d_rows, *prior);
+        else
+            hipLaunchKernelGGL(tgt_grid_rows_kernel<false>, grid, dim3(256), 0, s.stream, d_kfL, d_kfR, n_kf, d_cfL, d_cfR, cells, cell_start,
+                               cell_list, cell, sr, gw, gh, d_on, d_pl, d_pr, tp_dist, d_rows, TemporalPrior{});
         EBVO_HIP(ctx, hipGetLastError());
     }
     return gt_totals_enqueue(ctx, s, d_rows, d_on, n_kf, d_tot);

@@ -784,6 +784,20 @@ class TemporalMatcherHIP
         std::vector<double> ncc_left, sift_left, refine_score_left, refine_score_right;
         std::vector<uint8_t> refine_validity;
     };
+    // The pose the NEXT match of `slot` searches under (ebvo_temporal_set_prior): row-major R and t of the relative pose
+    // keyframe -> current frame, in the convention of MotionTrackerHIP's result (ebvo::predict_pose forms one from the last
+    // two).  One-shot: the next successful match consumes it, set_keyframe drops it.  This project's own: the reference
+    // always searches around the keyframe position.
+    bool set_prior(const double *R, const double *t, const ebvo_stereo_calib &calib, const ebvo_tprior_params *params = nullptr,
+                   int slot = 0)
+    {
+        return report(*ctx_, last_status = ebvo_temporal_set_prior(ctx_->get(), slot, R, t, &calib, params), "ebvo_temporal_set_prior");
+    }
+    bool clear_prior(int slot = 0)
+    {
+        return report(*ctx_, last_status = ebvo_temporal_clear_prior(ctx_->get(), slot), "ebvo_temporal_clear_prior");
+    }
+
     Quads match(int slot = 0, int stages = 1, const ebvo_temporal_params *params = nullptr)
     {
         Quads q;
@@ -1001,6 +1015,39 @@ inline PoseError pose_error(const double *R, const double *t, const double *R_gt
     e.trans_dir_deg = norm(t) == 0.0 || norm(t_gt) == 0.0 ? std::nan("")
                                                           : std::atan2(norm(x), t[0] * t_gt[0] + t[1] * t_gt[1] + t[2] * t_gt[2]) * deg;
     return e;
+}
+
+// Constant-velocity prediction of the next relative pose keyframe -> frame, for TemporalMatcherHIP::set_prior, on the host
+// (the twin of api.predict_pose): the step of the last two poses, T_k T_{k-1}^-1, applied once more to T_k.  Row-major R.
+// prev2_R == nullptr (one earlier pose only): the last pose itself.
+struct PredictedPose
+{
+    std::array<double, 9> R;
+    std::array<double, 3> t;
+};
+inline PredictedPose predict_pose(const double *prev_R, const double *prev_t, const double *prev2_R = nullptr,
+                                  const double *prev2_t = nullptr)
+{
+    PredictedPose out;
+    if (!prev2_R || !prev2_t)
+    {
+        std::copy(prev_R, prev_R + 9, out.R.begin());
+        std::copy(prev_t, prev_t + 3, out.t.begin());
+        return out;
+    }
+    double D[9], d[3]; // T_k T_{k-1}^-1 = (R_k R_{k-1}^T, t_k - D t_{k-1})
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j)
+            D[i * 3 + j] = prev_R[i * 3] * prev2_R[j * 3] + prev_R[i * 3 + 1] * prev2_R[j * 3 + 1] + prev_R[i * 3 + 2] * prev2_R[j * 3 + 2];
+    for (int i = 0; i < 3; ++i)
+        d[i] = prev_t[i] - (D[i * 3] * prev2_t[0] + D[i * 3 + 1] * prev2_t[1] + D[i * 3 + 2] * prev2_t[2]);
+    for (int i = 0; i < 3; ++i)
+    {
+        for (int j = 0; j < 3; ++j)
+            out.R[i * 3 + j] = D[i * 3] * prev_R[j] + D[i * 3 + 1] * prev_R[3 + j] + D[i * 3 + 2] * prev_R[6 + j];
+        out.t[i] = D[i * 3] * prev_t[0] + D[i * 3 + 1] * prev_t[1] + D[i * 3 + 2] * prev_t[2] + d[i];
+    }
+    return out;
 }
 
 // Frame_Evaluation_Metrics (include/Stereo_Matches.h): what get_Stereo_Edge_Pairs returns on a dataset with ground truth --

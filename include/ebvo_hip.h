@@ -971,6 +971,47 @@ int ebvo_tgt_grid_rows(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge 
                        const uint8_t *row_on, const double *proj_left, const double *proj_right, double tp_dist, int32_t *n_tp,
                        ebvo_gt_stage *stage_out);
 
+/* ---- temporal matching under a pose prior (this project's own; the reference searches around the keyframe position) ---
+ * A relative pose (R, t) keyframe -> current frame in the convention of the ground truth above and of the pose search
+ * (Gc = R * Gamma + t in the left camera) moves the search of every keyframe mate to where the pose predicts it: the mate
+ * is triangulated, projected into both cameras and its orientation mapped (the arithmetic of the ground truth's
+ * projection, bit for bit), and the grid walk and the orientation test of the candidate stage take the projections (and,
+ * with use_orientation, the mapped orientations) as their query in place of the mate's own edges.  A mate is LIVE iff its
+ * four projected coordinates lie strictly inside (img_margin, w - img_margin) x (img_margin, h - img_margin) of the
+ * CURRENT frame (both cameras against that one size; NaN and infinite coordinates are outside) and its depth is positive in
+ * both cameras; a mate that is not live has an empty row.  Rows keep the order of an unprimed match (dy outer, dx inner,
+ * ascending mate index within a cell), and every later stage is the unprimed chain on the candidate list.
+ *
+ * The setter is a per-slot, ONE-SHOT switch and does no device work: the next successful match / _submit call of the slot
+ * consumes the pose, a refused one leaves it pending; setting a keyframe drops the pending priors of every slot, the clear
+ * call drops the slot's (no error when there is none).  EBVO_ERR_STATE while a match of the slot is in flight;
+ * EBVO_ERR_ARG, with nothing changed, for a NaN or infinite entry of R or t, a calibration the ground truth would refuse,
+ * or an img_margin that is negative or not finite.  params NULL: the defaults.
+ * The fetch returns the arrays of the slot's match -- live [n_kf], proj_* [n_kf][2], orient_* [n_kf]; any pointer may be
+ * NULL -- which stay until the match is replaced; EBVO_ERR_STATE when the match was made without a prior.  On a match that
+ * kept its stage trail, the ground truth's EBVO_TGT_GRID row counts the cells the match searched: the prior's query
+ * points, nothing for a mate that is not live.
+ * The candidates call is the stage on host arrays, under the rules of the host-array calls above (slot 0's stream, buffers
+ * of its own, EBVO_ERR_STATE while slot 0 has work in flight): the arrays of the fetch plus row_ptr [n_kf + 1] and col_idx
+ * (cap entries; more candidates: EBVO_ERR_CAPACITY with *n_candidates set).  Any output pointer may be NULL. */
+typedef struct ebvo_tprior_params
+{
+    double img_margin;       /* 0 */
+    int32_t use_orientation; /* 1 */
+} ebvo_tprior_params;
+void ebvo_tprior_default_params(ebvo_tprior_params *p);
+int ebvo_temporal_set_prior(ebvo_ctx *ctx, int slot, const double R[9], const double t[3], const ebvo_stereo_calib *calib,
+                            const ebvo_tprior_params *params);
+int ebvo_temporal_clear_prior(ebvo_ctx *ctx, int slot);
+int ebvo_temporal_prior_fetch(ebvo_ctx *ctx, int slot, uint8_t *live, double *proj_left, double *proj_right, double *orient_left,
+                              double *orient_right);
+int ebvo_tprior_candidates(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *kf_right, int n_kf, const ebvo_edge *cf_left,
+                           const ebvo_edge *cf_right, int n_cf, int img_w, int img_h, int cell_size, double grid_radius,
+                           double orient_thr_deg, const double R[9], const double t[3], const ebvo_stereo_calib *calib,
+                           const ebvo_tprior_params *params, uint8_t *live, double *proj_left, double *proj_right,
+                           double *orient_left, double *orient_right, int32_t *row_ptr, int32_t *col_idx, int64_t cap,
+                           int64_t *n_candidates);
+
 /* ---------------------------------------------------------------------------------------- */
 /* Device-resident stereo pipeline: TOED(left) + TOED(right) + candidates + NCC of one pair,  */
 /* images and every intermediate in HBM.  This is what bench.py times.                        */
