@@ -59,6 +59,7 @@ ABI_SYMBOLS = (
     "ebvo_pose_from_quads_gt", "ebvo_temporal_estimate_pose_gt", "ebvo_pose_constraint_metrics",
     "ebvo_temporal_pose_constraint_metrics",
     "ebvo_pose_refine_default_params", "ebvo_pose_refine_from_quads", "ebvo_temporal_refine_pose",
+    "ebvo_align_default_params", "ebvo_pose_align_edges", "ebvo_temporal_align_pose", "ebvo_temporal_align_size",
 )
 
 
@@ -142,6 +143,22 @@ class PoseRefined(C.Structure):
 
 
 REFINE_OK, REFINE_NOTHING, REFINE_PIVOT = 0, 1, 2
+
+
+class AlignParams(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("iterations", C.c_int32), ("radius", C.c_double), ("cell_size", C.c_int32),
+                ("min_terms", C.c_int32), ("orient_thr_deg", C.c_double), ("huber_px", C.c_double), ("inlier_px", C.c_double),
+                ("step_eps", C.c_double), ("img_margin", C.c_double), ("cameras", C.c_int32), ("block_threads", C.c_int32)]
+
+
+class AlignedPose(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("status", C.c_int32), ("stop_reason", C.c_int32),
+                ("rounds_run", C.c_int32), ("steps_kept", C.c_int32), ("n_kf", C.c_int32), ("fit_terms", C.c_int32),
+                ("n_assoc", C.c_int32 * 2), ("inliers", C.c_int64), ("cost_first", C.c_double), ("cost_last", C.c_double),
+                ("rms_normal", C.c_double)]
+
+
+ALIGN_OK, ALIGN_NOTHING, ALIGN_PIVOT = 0, 1, 2   # the stop reasons are the refit's, 4 = fewer than min_terms associated terms
 (REFINE_STOP_EPS, REFINE_STOP_CAP, REFINE_STOP_COST, REFINE_STOP_PIVOT, REFINE_STOP_FEW) = range(5)
 
 # stage ids (ebvo_hip.h EBVO_PC_*) and the names of Solution_Constraints_Application (src/MotionTracker.cpp:299-378)
@@ -361,6 +378,16 @@ def load_library() -> C.CDLL:
     lib.ebvo_temporal_refine_pose.restype = i32
     lib.ebvo_temporal_refine_pose.argtypes = [vp, i32, C.POINTER(StereoCalib), C.POINTER(PoseParams), C.POINTER(PoseRefineParams),
                                               vp, vp, i32, C.POINTER(PoseRefined), vp]
+    lib.ebvo_align_default_params.restype = None
+    lib.ebvo_align_default_params.argtypes = [C.POINTER(AlignParams)]
+    lib.ebvo_pose_align_edges.restype = i32
+    lib.ebvo_pose_align_edges.argtypes = [vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, C.POINTER(StereoCalib), C.POINTER(AlignParams),
+                                          vp, vp, C.POINTER(AlignedPose), vp, vp]
+    lib.ebvo_temporal_align_pose.restype = i32
+    lib.ebvo_temporal_align_pose.argtypes = [vp, i32, C.POINTER(StereoCalib), C.POINTER(AlignParams), vp, vp, C.POINTER(AlignedPose),
+                                             vp, vp]
+    lib.ebvo_temporal_align_size.restype = i32
+    lib.ebvo_temporal_align_size.argtypes = [vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.ebvo_gt_default_params.restype = None
     lib.ebvo_gt_default_params.argtypes = [C.POINTER(GtParams)]
     lib.ebvo_stereo_set_gt.argtypes = [vp, i32, vp, i32, i32, ssz, C.POINTER(StereoCalib), C.POINTER(GtParams)]

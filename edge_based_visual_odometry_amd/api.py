@@ -907,6 +907,58 @@ class Context:
                                                        1 if gt_rows else 0, C.byref(r), ptr(inlier)), "ebvo_temporal_refine_pose")
         return self._refined_dict(r, inlier)
 
+    # -- alignment of the pose to the current frame's TOED edges by normal distance (the contract is in ebvo_hip.h) --------
+    def align_params(self, **kw) -> _lib.AlignParams:
+        """ebvo_align_params: the defaults of ebvo_align_default_params with `kw` applied."""
+        p = _lib.AlignParams()
+        self.lib.ebvo_align_default_params(C.byref(p))
+        fields = {name for name, _ in p._fields_}
+        for k, v in kw.items():
+            if k not in fields:
+                raise TypeError(f"align: unknown parameter {k!r}")
+            setattr(p, k, v)
+        return p
+
+    @staticmethod
+    def _aligned_dict(r, assoc_left, assoc_right) -> dict:
+        out = {k: getattr(r, k) for k in ("status", "stop_reason", "rounds_run", "steps_kept", "n_kf", "fit_terms", "inliers",
+                                          "cost_first", "cost_last", "rms_normal")}
+        out["n_assoc"] = (int(r.n_assoc[0]), int(r.n_assoc[1]))
+        out["R"] = np.array(r.R[:], dtype=np.float64).reshape(3, 3)
+        out["t"] = np.array(r.t[:], dtype=np.float64)
+        out["assoc_left"], out["assoc_right"] = assoc_left, assoc_right
+        return out
+
+    def pose_align_edges(self, kf_left, kf_right, cf_edges_left, cf_edges_right, img_w: int, img_h: int, calib, R, t, **params) -> dict:
+        """Alignment of the start pose (R, t) to the current frame's TOED edges on host arrays (ebvo_pose_align_edges):
+        cf_edges_right may be None with cameras=1.  params: the fields of ebvo_align_params.  Returns the fields of
+        ebvo_aligned_pose, R (3x3), t, and assoc_left / assoc_right (int32 per keyframe mate: edge index or -1)."""
+        kfL, kfR, E0 = _edges(kf_left), _edges(kf_right), _edges(cf_edges_left)
+        E1 = _edges(cf_edges_right) if cf_edges_right is not None else np.zeros(0, dtype=EDGE_DTYPE)
+        if len(kfL) != len(kfR):
+            raise ValueError("kf_left and kf_right differ in length")
+        p, cal, r = self.align_params(**params), self._calib(calib), _lib.AlignedPose()
+        R, t = self._start_pose(R, t)
+        aL, aR = np.full(len(kfL), -1, dtype=np.int32), np.full(len(kfL), -1, dtype=np.int32)
+        self._check(self.lib.ebvo_pose_align_edges(self._ctx, ptr(kfL), ptr(kfR), len(kfL), ptr(E0), len(E0),
+                                                   ptr(E1) if cf_edges_right is not None else None, len(E1), int(img_w), int(img_h),
+                                                   C.byref(cal), C.byref(p), ptr(R), ptr(t), C.byref(r), ptr(aL), ptr(aR)),
+                    "ebvo_pose_align_edges")
+        return self._aligned_dict(r, aL, aR)
+
+    def temporal_align_pose(self, calib, R, t, slot: int = 0, **params) -> dict:
+        """The same with the context's keyframe mates against the kept TOED edge lists the slot's pair left resident
+        (ebvo_temporal_align_pose): needs a keyframe and a waited pair, neither finalisation nor a temporal match."""
+        p, cal, r = self.align_params(**params), self._calib(calib), _lib.AlignedPose()
+        R, t = self._start_pose(R, t)
+        n_kf, n0, n1 = C.c_int32(), C.c_int32(), C.c_int32()
+        self._check(self.lib.ebvo_temporal_align_size(self._ctx, slot, C.byref(n_kf), C.byref(n0), C.byref(n1)),
+                    "ebvo_temporal_align_size")
+        aL, aR = np.full(n_kf.value, -1, dtype=np.int32), np.full(n_kf.value, -1, dtype=np.int32)
+        self._check(self.lib.ebvo_temporal_align_pose(self._ctx, slot, C.byref(cal), C.byref(p), ptr(R), ptr(t), C.byref(r), ptr(aL),
+                                                      ptr(aR)), "ebvo_temporal_align_pose")
+        return self._aligned_dict(r, aL, aR)
+
     # -- ground-truth evaluation from a disparity map (Find_Stereo_GT_Locations, get_Stereo_Edge_GT_Pairs,
     # -- Evaluate_Stereo_Edge_Correspondences) ---------------------------------------------------------------
     def gt_params(self, **kw) -> _lib.GtParams:

@@ -175,7 +175,7 @@ static void slot_destroy(Slot *s)
                        &s->keep,         &s->patches_raw,  &s->patches_norm,   &s->patches_flag,   &s->patches_norm_r,
                        &s->patches_flag_r, &s->pair_left,  &s->sincos,         &s->scratch_b,      &s->scratch_c,
                        &s->scratch_d,    &s->fetch_pack,   &s->pose_in,        &s->pose_geom,      &s->pose_order,
-                       &s->pose_draw,    &s->pose_hyp,       &s->pose_sel,       &s->pose_casc,       &s->pose_refit,     &s->gt_disp,        &s->gt_geom,        &s->gt_flags,
+                       &s->pose_draw,    &s->pose_hyp,       &s->pose_sel,       &s->pose_casc,       &s->pose_refit,     &s->align_up,       &s->align_ws,       &s->gt_disp,        &s->gt_geom,        &s->gt_flags,
                        &s->gt_boxes,     &s->gt_pool_i32,  &s->gt_pool_idx,    &s->gt_rows,        &s->gt_tot,
                        &s->gt_up,        &s->tgt_geom,     &s->tgt_i32,        &s->tgt_idx,        &s->tgt_u8,
                        &s->tgt_rows,     &s->tgt_flags,    &s->tgt_tot,        &s->tgt_up,
@@ -4325,6 +4325,197 @@ extern "C" int ebvo_temporal_refine_pose(ebvo_ctx *ctx, int slot, const ebvo_ste
     const Slot::TqFinal &F = s.tq_final;
     const uint8_t *on = gt_rows ? (const uint8_t *)s.tgt_u8.p + (size_t)s.tgt_n_kf : nullptr; // row_on[], as the GT search
     return pose_refit_run(ctx, s, ctx->kf_L, ctx->kf_R, F.rp, s.tq_n_kf, F.L, F.R, (int)F.n, on, cal, p, rp, R0, t0, out, inlier);
+}
+
+// ---- alignment of the pose to the current frame's TOED edges (align_kernels.hip) ---------------------------------------
+static int gt_grow(ebvo_ctx *ctx, Slot &s, GrowBuf &b, size_t bytes); // defined with the ground-truth calls below
+static int gt_host_slot(ebvo_ctx *ctx, Slot **out);
+extern "C" void ebvo_align_default_params(ebvo_align_params *p)
+{
+    if (!p)
+        return;
+    p->rounds = 4;
+    p->iterations = 10;
+    p->radius = 4.0;
+    p->cell_size = 4;
+    p->min_terms = 12;
+    p->orient_thr_deg = 10.0;
+    p->huber_px = 1.0;
+    p->inlier_px = 1.0;
+    p->step_eps = 1e-10;
+    p->img_margin = 10.0;
+    p->cameras = 2;
+    p->block_threads = 0;
+}
+
+static bool align_args_ok(const ebvo_stereo_calib *cal, const ebvo_align_params *ap, const double *R0, const double *t0,
+                          const ebvo_aligned_pose *out, int img_w, int img_h)
+{
+    if (!cal || !ap || !R0 || !t0 || !out || img_w < 1 || img_h < 1)
+        return false;
+    for (int i = 0; i < 9; ++i)
+        if (!std::isfinite(R0[i]))
+            return false;
+    for (int i = 0; i < 3; ++i)
+        if (!std::isfinite(t0[i]))
+            return false;
+    const int bt = ap->block_threads;
+    // every comparison is false for a NaN
+    if (!(ap->rounds >= 1 && ap->rounds <= 16 && ap->iterations >= 0 && ap->iterations <= 100 && std::isfinite(ap->radius) &&
+          ap->radius > 0 && ap->cell_size >= 1 && ap->orient_thr_deg >= 0 && ap->huber_px > 0 && ap->inlier_px >= 0 &&
+          ap->step_eps >= 0 && ap->min_terms >= 6 && ap->img_margin >= 0 && (ap->cameras == 1 || ap->cameras == 2) &&
+          (bt == 0 || bt == 256 || bt == 512 || bt == 1024)))
+        return false;
+    if (!(ceil(ap->radius / ap->cell_size) <= 8.0))
+        return false;
+    const int64_t gw = ((int64_t)img_w + ap->cell_size - 1) / ap->cell_size, gh = ((int64_t)img_h + ap->cell_size - 1) / ap->cell_size;
+    return gw * gh <= (1 << 26);
+}
+
+// nothing to launch: the start pose, status 1
+static void align_nothing(const double *R0, const double *t0, int n_kf, ebvo_aligned_pose *out, int32_t *assoc_left, int32_t *assoc_right)
+{
+    memset(out, 0, sizeof *out);
+    memcpy(out->R, R0, sizeof out->R);
+    memcpy(out->t, t0, sizeof out->t);
+    out->status = 1;
+    out->stop_reason = 4;
+    out->n_kf = n_kf;
+    for (int i = 0; i < n_kf; ++i)
+    {
+        if (assoc_left)
+            assoc_left[i] = -1;
+        if (assoc_right)
+            assoc_right[i] = -1;
+    }
+}
+
+static void align_publish(const AlignResult &r, int n_kf, ebvo_aligned_pose *out)
+{
+    memset(out, 0, sizeof *out);
+    memcpy(out->R, r.Rt, sizeof out->R);
+    memcpy(out->t, r.Rt + 9, sizeof out->t);
+    out->status = r.status;
+    out->stop_reason = r.stop;
+    out->rounds_run = r.rounds_run;
+    out->steps_kept = r.steps_kept;
+    out->n_kf = n_kf;
+    out->fit_terms = r.fit_terms;
+    out->n_assoc[0] = r.n_assoc[0];
+    out->n_assoc[1] = r.n_assoc[1];
+    out->inliers = r.inliers;
+    out->cost_first = r.cost_first;
+    out->cost_last = r.cost_last;
+    out->rms_normal = r.rms_normal;
+}
+
+extern "C" int ebvo_pose_align_edges(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *kf_right, int n_kf,
+                                     const ebvo_edge *cf_edges_left, int n0, const ebvo_edge *cf_edges_right, int n1, int img_w,
+                                     int img_h, const ebvo_stereo_calib *cal, const ebvo_align_params *params, const double R0[9],
+                                     const double t0[3], ebvo_aligned_pose *out, int32_t *assoc_left, int32_t *assoc_right)
+{
+    if (!ctx || !align_args_ok(cal, params, R0, t0, out, img_w, img_h) || n_kf < 0 || n0 < 0 || (n_kf > 0 && (!kf_left || !kf_right)) ||
+        (n0 > 0 && !cf_edges_left))
+        return EBVO_ERR_ARG;
+    if (params->cameras == 1)
+        n1 = 0;
+    else if (n1 < 0 || (n1 > 0 && !cf_edges_right))
+        return EBVO_ERR_ARG;
+    int rc;
+    Slot *sp;
+    if ((rc = gt_host_slot(ctx, &sp)))
+        return rc;
+    Slot &s = *sp;
+    if (n_kf == 0 || n0 + (int64_t)n1 == 0)
+    {
+        align_nothing(R0, t0, n_kf, out, assoc_left, assoc_right);
+        return EBVO_OK;
+    }
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nz = (size_t)n_kf, o_kfR = sizeof(ebvo_edge) * nz, o_E0 = 2 * o_kfR, o_E1 = o_E0 + sizeof(ebvo_edge) * (size_t)n0,
+                 total = o_E1 + sizeof(ebvo_edge) * (size_t)n1 + 64;
+    if ((rc = gt_grow(ctx, s, s.align_up, total)))
+        return rc;
+    char *base = (char *)s.align_up.p;
+    ebvo_edge *kfL = (ebvo_edge *)base, *kfR = (ebvo_edge *)(base + o_kfR), *E0 = (ebvo_edge *)(base + o_E0), *E1 = (ebvo_edge *)(base + o_E1);
+    hipStream_t st = s.stream;
+    EBVO_HIP(ctx, hipMemcpyAsync(kfL, kf_left, sizeof(ebvo_edge) * nz, hipMemcpyHostToDevice, st));
+    EBVO_HIP(ctx, hipMemcpyAsync(kfR, kf_right, sizeof(ebvo_edge) * nz, hipMemcpyHostToDevice, st));
+    if (n0)
+        EBVO_HIP(ctx, hipMemcpyAsync(E0, cf_edges_left, sizeof(ebvo_edge) * (size_t)n0, hipMemcpyHostToDevice, st));
+    if (n1)
+        EBVO_HIP(ctx, hipMemcpyAsync(E1, cf_edges_right, sizeof(ebvo_edge) * (size_t)n1, hipMemcpyHostToDevice, st));
+    AlignResult r;
+    {
+        const TemporalGridScope grid_scope(ctx, s);
+        rc = align_run(ctx, s, kfL, kfR, n_kf, E0, n0, E1, n1, img_w, img_h, cal, params, R0, t0, &r, assoc_left, assoc_right);
+    }
+    if (rc)
+    {
+        (void)hipStreamSynchronize(st); // the uploads read the caller's arrays: none of them outlives the call
+        return rc;
+    }
+    align_publish(r, n_kf, out);
+    return EBVO_OK;
+}
+
+// a keyframe, and a pair on the slot whose wait has returned, nothing of the slot in flight
+static int align_slot_state(ebvo_ctx *ctx, const Slot &s)
+{
+    if (ctx->kf_n < 0 || !s.have_run || s.in_flight || s.fin_in_flight || s.tq_in_flight)
+    {
+        ctx->last_error = s.in_flight || s.fin_in_flight || s.tq_in_flight ? "the slot has work in flight (wait for it first)"
+                          : ctx->kf_n < 0                                  ? "no keyframe (ebvo_temporal_set_keyframe first)"
+                                                                           : "the slot holds no pair (ebvo_stereo_submit and ebvo_stereo_wait first)";
+        return EBVO_ERR_STATE;
+    }
+    return EBVO_OK;
+}
+
+extern "C" int ebvo_temporal_align_size(ebvo_ctx *ctx, int slot, int32_t *n_kf, int32_t *n_left, int32_t *n_right)
+{
+    Slot *sp;
+    if (get_slot(ctx, slot, &sp) || !n_kf || !n_left || !n_right)
+        return EBVO_ERR_ARG;
+    if (int rc = align_slot_state(ctx, *sp))
+        return rc;
+    *n_kf = ctx->kf_n;
+    *n_left = sp->im[0].n_kept;
+    *n_right = sp->im[1].n_kept;
+    return EBVO_OK;
+}
+
+extern "C" int ebvo_temporal_align_pose(ebvo_ctx *ctx, int slot, const ebvo_stereo_calib *cal, const ebvo_align_params *params,
+                                        const double R0[9], const double t0[3], ebvo_aligned_pose *out, int32_t *assoc_left,
+                                        int32_t *assoc_right)
+{
+    Slot *sp;
+    if (get_slot(ctx, slot, &sp))
+        return EBVO_ERR_ARG;
+    Slot &s = *sp;
+    // the frame's size enters the accepted ranges through the grid; a slot without a pair has none yet
+    if (!align_args_ok(cal, params, R0, t0, out, s.have_run ? s.cur_w : 1, s.have_run ? s.cur_h : 1))
+        return EBVO_ERR_ARG;
+    if (int rc = align_slot_state(ctx, s))
+        return rc;
+    const int n_kf = ctx->kf_n, n0 = s.im[0].n_kept, n1 = params->cameras > 1 ? s.im[1].n_kept : 0;
+    if (n_kf == 0 || n0 + (int64_t)n1 == 0)
+    {
+        align_nothing(R0, t0, n_kf, out, assoc_left, assoc_right);
+        return EBVO_OK;
+    }
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    AlignResult r;
+    int rc;
+    {
+        const TemporalGridScope grid_scope(ctx, s);
+        rc = align_run(ctx, s, ctx->kf_L, ctx->kf_R, n_kf, s.im[0].edges, n0, s.im[1].edges, n1, s.cur_w, s.cur_h, cal, params, R0, t0, &r,
+                       assoc_left, assoc_right);
+    }
+    if (rc)
+        return rc;
+    align_publish(r, n_kf, out);
+    return EBVO_OK;
 }
 
 // the slot's page-locked result arena holds at least `bytes` (a re-allocation waits for copies still heading into the old one).

@@ -184,6 +184,8 @@ struct Slot
                                                                  // order, one batch of draws, its hypotheses
     GrowBuf pose_sel, pose_casc; // ground-truth rows: the compacted selection and what is scattered back; the cascade's draws,
                                  // counters and stage bytes
+    GrowBuf align_up, align_ws;  // edge alignment (align_kernels.hip): the uploaded lists of the host-array call; the state, tile sums,
+                                 // planes and both edge grids of either call
     GrowBuf pose_refit;          // inlier refit (pose_refit_kernels.hip): seven planes per quad, the fit set, the mask, the result
     // ground-truth evaluation (gt_kernels.hip, ebvo_stereo_set_gt): armed = the buffers below describe the resident pair
     GrowBuf gt_disp, gt_geom, gt_flags, gt_boxes, gt_pool_i32, gt_pool_idx, gt_rows, gt_tot;
@@ -715,6 +717,19 @@ int pose_refit_run(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_ed
                    const ebvo_edge *d_cfL, const ebvo_edge *d_cfR, int n, const uint8_t *d_on, const ebvo_stereo_calib *cal,
                    const ebvo_pose_params *p, const ebvo_pose_refine_params *rp, const double *R0, const double *t0,
                    ebvo_pose_refined *out, uint8_t *inlier);
+// align_kernels.hip: what align_metric_kernel leaves
+struct AlignResult
+{
+    double Rt[12];
+    double cost_first, cost_last, rms_normal;
+    int32_t status, stop, rounds_run, steps_kept, fit_terms, n_assoc[2], inliers;
+};
+// The alignment of n_kf >= 1 keyframe mates to the kept TOED edges d_E0 [n0] (and d_E1 [n1] with cameras = 2; n0 + n1 >= 1),
+// all device arrays; the workspace is s.align_ws.  Developer key 22 (Slot::tq_blocks) caps its grid-stride launches.
+// assoc_left / assoc_right (host, may be NULL): n_kf int32.  Waits for the result.
+int align_run(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, int n_kf, const ebvo_edge *d_E0, int n0,
+              const ebvo_edge *d_E1, int n1, int img_w, int img_h, const ebvo_stereo_calib *cal, const ebvo_align_params *ap,
+              const double *R0, const double *t0, AlignResult *res, int32_t *assoc_left, int32_t *assoc_right);
 int misc_fp64_peak(ebvo_ctx *ctx, Slot &s, int iters, double *tf_muladd, double *tf_fma);
 
 #endif

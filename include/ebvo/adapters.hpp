@@ -927,6 +927,64 @@ class MotionTrackerHIP
         return state.refined.status == 0;
     }
 
+    // The alignment of a pose to the current frame's TOED edges by normal distance (this project's own; the contract is in
+    // ebvo_hip.h): the keyframe mates' 3-D points are projected under the pose, associated with the nearest edge of compatible
+    // orientation in each image and the distances along the edges' normals minimised, re-associating every round.  It needs
+    // neither quads nor finalisation of the current frame.  NOTE: camera 1 uses the TRUE K_right of the calibration, unlike
+    // the search and the refit above (K_right := K_left).
+    struct Align_Options
+    {
+        ebvo_align_params p;
+        Align_Options() { ebvo_align_default_params(&p); }
+    };
+    struct Align_State
+    {
+        std::array<double, 9> R{{1, 0, 0, 0, 1, 0, 0, 0, 1}}; // in: the start pose; stays as given
+        std::array<double, 3> t{{0, 0, 0}};
+        ebvo_aligned_pose aligned{};                           // out: the aligned pose and every field of the stage
+        std::vector<int32_t> assoc_left, assoc_right;          // per keyframe mate: edge index or -1, when asked for
+    };
+
+    // the context's keyframe against the TOED edge lists the slot's waited pair left resident; true when aligned.status == 0
+    bool align_Relative_Pose(int slot, const Align_Options &opt, Align_State &state, bool want_assoc = false)
+    {
+        state.aligned = ebvo_aligned_pose{};
+        int32_t n_kf = 0, n0 = 0, n1 = 0;
+        last_status = ebvo_temporal_align_size(ctx_->get(), slot, &n_kf, &n0, &n1);
+        if (!report(*ctx_, last_status, "ebvo_temporal_align_size"))
+            return false;
+        size_assoc(state, want_assoc ? (size_t)n_kf : 0);
+        last_status = ebvo_temporal_align_pose(ctx_->get(), slot, &calib_, &opt.p, state.R.data(), state.t.data(), &state.aligned,
+                                               want_assoc ? state.assoc_left.data() : nullptr,
+                                               want_assoc ? state.assoc_right.data() : nullptr);
+        if (!report(*ctx_, last_status, "ebvo_temporal_align_pose"))
+            return false;
+        return state.aligned.status == 0;
+    }
+
+    // the same on host arrays: keyframe mates and the two edge lists of a frame of img_w x img_h (edges_right may be empty
+    // with opt.p.cameras = 1)
+    bool align_Relative_Pose(const std::vector<ebvo_edge> &kf_left, const std::vector<ebvo_edge> &kf_right,
+                             const std::vector<ebvo_edge> &edges_left, const std::vector<ebvo_edge> &edges_right, int img_w, int img_h,
+                             const Align_Options &opt, Align_State &state, bool want_assoc = false)
+    {
+        state.aligned = ebvo_aligned_pose{};
+        if (kf_left.size() != kf_right.size())
+        {
+            last_status = EBVO_ERR_ARG;
+            return false;
+        }
+        size_assoc(state, want_assoc ? kf_left.size() : 0);
+        last_status = ebvo_pose_align_edges(ctx_->get(), kf_left.data(), kf_right.data(), (int)kf_left.size(), edges_left.data(),
+                                            (int)edges_left.size(), edges_right.empty() ? nullptr : edges_right.data(),
+                                            (int)edges_right.size(), img_w, img_h, &calib_, &opt.p, state.R.data(), state.t.data(),
+                                            &state.aligned, want_assoc ? state.assoc_left.data() : nullptr,
+                                            want_assoc ? state.assoc_right.data() : nullptr);
+        if (!report(*ctx_, last_status, "ebvo_pose_align_edges"))
+            return false;
+        return state.aligned.status == 0;
+    }
+
     // n_runs calls of the reference's Solution_Constraints_Application (src/Pipeline.cpp:198-203 makes 20) in one device
     // call: one vector of five stages per run.  Empty on an error (last_status) and when the slot has too few quads.
     std::vector<std::vector<Quad_Pair_Evaluation_Metrics>> Solution_Constraints_Application(int slot, const Ransac_Options &opt,
@@ -987,6 +1045,11 @@ class MotionTrackerHIP
     }
 
   private:
+    static void size_assoc(Align_State &state, size_t n)
+    {
+        state.assoc_left.assign(n, -1);
+        state.assoc_right.assign(n, -1);
+    }
     Context::Ptr ctx_;
     ebvo_stereo_calib calib_;
 };

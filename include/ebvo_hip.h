@@ -41,7 +41,9 @@ extern "C" {
                               ebvo_pose_from_quads_gt, ebvo_temporal_estimate_pose_gt, ebvo_pose_constraint_metrics,
                               ebvo_temporal_pose_constraint_metrics; and with the additive inlier refit:
                               ebvo_pose_refine_params / _refined, ebvo_pose_refine_default_params,
-                              ebvo_pose_refine_from_quads, ebvo_temporal_refine_pose */
+                              ebvo_pose_refine_from_quads, ebvo_temporal_refine_pose; and with the additive edge
+                              alignment: ebvo_align_params, ebvo_aligned_pose, ebvo_align_default_params,
+                              ebvo_pose_align_edges, ebvo_temporal_align_pose, ebvo_temporal_align_size */
 
 typedef struct ebvo_ctx ebvo_ctx;
 
@@ -779,6 +781,97 @@ int ebvo_pose_refine_from_quads(ebvo_ctx *ctx, const ebvo_edge *kf_left, const e
 int ebvo_temporal_refine_pose(ebvo_ctx *ctx, int slot, const ebvo_stereo_calib *cal, const ebvo_pose_params *p,
                               const ebvo_pose_refine_params *rp, const double R0[9], const double t0[3], int gt_rows,
                               ebvo_pose_refined *out, uint8_t *inlier);
+
+/* ---- alignment of the pose to the current frame's TOED edges by normal distance (this project's own stage) ---------- */
+/* ICP on curves: the keyframe mates' 3-D points are projected under the pose, each projection is associated with the
+ * nearest current-frame TOED edge of compatible orientation, and the distance ALONG THAT EDGE'S NORMAL is minimised over the
+ * pose, re-associating as the pose moves.  It needs no quad: only the keyframe mates and the TOED edge lists of the current
+ * frame.  This comment is the arithmetic contract; tests/oracle_align.py restates it and the device matches it bit for bit.
+ * fp64, no FMA, IEEE division and sqrt; mv3 / cross3 of csrc/ebvo_geom.h; sines and cosines through ebvo_sincos, atan2
+ * through ebvo_atan2 (csrc/ebvo_math.h).
+ * Inputs: the keyframe mates kf_left[i], kf_right[i], i < n_kf; the calibration; the kept TOED edges of the current frame's
+ *   left image E0[j], j < n0, and (cameras = 2) of its right image E1[j], j < n1; the frame's size w x h; a start pose in the
+ *   convention of the pose search (Gc = R Gamma + t in the left camera).
+ * Cameras: camera 0 is K_left; camera 1 sits at (R21, T21) with the TRUE K_right of `cal`.  This is the projection of the
+ *   pose prior (ebvo_temporal_set_prior) and NOT the pose search's and the refit's K_right := K_left: the residuals are taken
+ *   against real right-image TOED edges, which lie where the true right camera saw them.
+ * Per mate: Gamma and the unit 3-D tangent T1 from stereo_gamma_tangent under (K_left^-1, K_right^-1, R21, T21), as the
+ *   prior's projection forms them.
+ * Association of a round under the pose (R, t), per mate i and camera c: Gc = mv3(R, Gamma) + t; camera 0: Y = Gc, M = R;
+ *   camera 1: Y = mv3(R21, Gc) + T21, M = R21 R (3 x 3 product in mv3 order).  p = mv3(K_c, Y), q = (p0 / p2, p1 / p2),
+ *   g = (q0, q1, p2 / p2) with q taken over its own third component as the prior does, ray = mv3(K_c^-1, g), T2 = mv3(M, T1),
+ *   t2 = T2 - T2_z ray normalised when its squared norm is > 0, o = ebvo_atan2(t2_y, t2_x).  The term is LIVE iff
+ *   img_margin < q_x < w - img_margin, img_margin < q_y < h - img_margin and Y_z > 0 (NaN, +-inf: not live) -- per camera,
+ *   not jointly.  Grid: gw = ceil(w / cell_size), gh = ceil(h / cell_size); edge e is in cell ((int)e.x / cell_size,
+ *   (int)e.y / cell_size) iff both lie in [0, gw) x [0, gh) (C division: e.x in (-cell_size, 0) is column 0; NaN and +-inf are
+ *   in no cell).  sr = ceil(radius / cell_size).  A live term's candidates are the edges e of E_c in the cells within sr of
+ *   q's cell (clipped to the grid) with orient_close(o, e.theta, orient_thr_deg) (|o - theta| in degrees folded at 180, within
+ *   the threshold of 0 or 180) and d2 = dx dx + dy dy <= radius radius, dx = e.x - q_x, dy = e.y - q_y.  It takes the
+ *   candidate with the smallest (d2, j) in lexicographic order -- no traversal order enters -- or is not associated.
+ * Residual of an associated term: (sn, cs) = ebvo_sincos(e.theta), n = (sn, -cs) (the reference's patch-shift normal,
+ *   src/utility.cpp:82-93); with pi, ip, jx, jy and Jx, Jy as the refit above forms them for that camera under K_c:
+ *   r = n0 (pi_x - e.x) + n1 (pi_y - e.y); rho = |r|; Huber with delta = huber_px by the refit's formulas; J_k = n0 Jx_k +
+ *   n1 Jy_k.  The 28 terms: w (J_i J_j), i <= j row-major (21), w (J_i r) (6), the cost.  A term that is not associated, or
+ *   whose rho is not < +inf, is +0.0 in all 28.  A mate's term is camera 0 + camera 1.
+ * Sums: mates are cut into tiles of 1024 consecutive indices; in a tile lane l holds +0.0 + the term of mate 1024 tile + l
+ *   (+0.0 past n_kf); each group of 64 lanes by the halving tree x[l] += x[l + s], s = 32 .. 1, the 16 group sums by the same
+ *   tree, s = 8 .. 1; the tile sums are added in ascending tile index from +0.0.  No launch geometry or arrival order enters.
+ * A round: associate under the current pose; A = the associated terms of both cameras.  A < min_terms: stop reason 4, pose
+ *   kept, the call ends.  Else, with the associations FIXED, the refit's loop: for it = 0 .. iterations the sums; it > 0 and
+ *   not cost <= cost_prev: previous pose restored, stop reason 2; it == iterations: stop reason 1; Cholesky as in the refit, a
+ *   pivot not > 0: stop reason 3, pose kept, the call ends; R <- Exp(d_0..2) R, t <- t + d_3..5; max |d| < step_eps: stop
+ *   reason 0.  `rounds` rounds are run, each re-associating; reasons 0, 1, 2 go on to the next round.
+ * After the last round one more association under the returned pose gives assoc_left / assoc_right (edge index or -1),
+ *   n_assoc, inliers (associated terms with |r| < inlier_px) and rms_normal = sqrt(S / (n_assoc[0] + n_assoc[1])), S the sum
+ *   of r r (camera 0 + camera 1 per mate, +0.0 for a term that is not associated or whose rho is not < +inf) through the same tile trees; 0 when nothing
+ *   is associated.
+ * block_threads is a developer switch as in the refit: 256 or 512 threads own lanes l, l + block_threads, ...; same bits. */
+typedef struct ebvo_align_params
+{
+    int32_t rounds, iterations;      /* 4, 10 */
+    double radius;                   /* 4.0 px: association radius */
+    int32_t cell_size, min_terms;    /* 4 px; 12 associated terms at least */
+    double orient_thr_deg;           /* 10 */
+    double huber_px, inlier_px;      /* 1.0 (+inf = least squares), 1.0 */
+    double step_eps;                 /* 1e-10 */
+    double img_margin;               /* 10: TOED keeps nothing nearer than 10 px to the border */
+    int32_t cameras, block_threads;  /* 2 (1 = left image only); 0 (= 1024), 256, 512 or 1024 */
+} ebvo_align_params;
+typedef struct ebvo_aligned_pose
+{
+    double R[9], t[3];
+    int32_t status;      /* 0 aligned / 1 nothing to fit (n_kf = 0, no edges: nothing launched; or A < min_terms under the
+                            start pose) / 2 the first solve hit a non-positive pivot; 1 and 2 return the start pose */
+    int32_t stop_reason; /* of the last round run: 0 eps, 1 step cap, 2 cost rose, 3 pivot, 4 A < min_terms */
+    int32_t rounds_run, steps_kept;
+    int32_t n_kf, fit_terms; /* fit_terms: A of the last round run */
+    int32_t n_assoc[2];      /* associated terms per camera under the returned pose */
+    int64_t inliers;
+    double cost_first, cost_last; /* of the last round that formed its sums */
+    double rms_normal;
+} ebvo_aligned_pose;
+void ebvo_align_default_params(ebvo_align_params *p);
+/* On host arrays.  cf_edges_right may be NULL with cameras = 1 (it and n1 are then ignored).  Accepted: 1 <= rounds <= 16,
+ * 0 <= iterations <= 100, radius finite and > 0, cell_size >= 1 with ceil(radius / cell_size) <= 8, orient_thr_deg >= 0,
+ * huber_px > 0 (+inf allowed), inlier_px >= 0, step_eps >= 0, min_terms >= 6, img_margin >= 0, cameras 1 or 2, block_threads
+ * in its set, no NaN, R0 and t0 finite, img_w, img_h >= 1 with a grid of at most 2^26 cells; anything else: EBVO_ERR_ARG,
+ * nothing touched.  assoc_left / assoc_right (may be NULL): n_kf int32 each (assoc_right all -1 with cameras = 1).  Runs on
+ * slot 0's stream without touching slot 0's results; EBVO_ERR_STATE while slot 0 has work in flight.  The inputs are copied
+ * before the call returns. */
+int ebvo_pose_align_edges(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *kf_right, int n_kf, const ebvo_edge *cf_edges_left,
+                          int n0, const ebvo_edge *cf_edges_right, int n1, int img_w, int img_h, const ebvo_stereo_calib *cal,
+                          const ebvo_align_params *params, const double R0[9], const double t0[3], ebvo_aligned_pose *out,
+                          int32_t *assoc_left, int32_t *assoc_right);
+/* The context's keyframe mates against the kept TOED edge lists the slot's pair left resident.  Needs a keyframe and a pair
+ * on the slot whose ebvo_stereo_wait has returned -- neither finalisation nor a temporal match; EBVO_ERR_STATE otherwise, or
+ * while anything of the slot is in flight.  The slot's pair, final mates, quads, ground-truth state, prior and the context's
+ * rand() stream are unchanged. */
+int ebvo_temporal_align_pose(ebvo_ctx *ctx, int slot, const ebvo_stereo_calib *cal, const ebvo_align_params *params,
+                             const double R0[9], const double t0[3], ebvo_aligned_pose *out, int32_t *assoc_left,
+                             int32_t *assoc_right);
+/* What that call would work on: the keyframe's mates (the length assoc_left / assoc_right need) and the slot's kept TOED
+ * edges per image.  The same state rules. */
+int ebvo_temporal_align_size(ebvo_ctx *ctx, int slot, int32_t *n_kf, int32_t *n_left, int32_t *n_right);
 
 /* ---- ground-truth evaluation from a disparity map (the reference's has_gt() == true branch, is_left = true) ------- */
 /* Find_Stereo_GT_Locations (src/Stereo_Matches.cpp:133-200), get_Stereo_Edge_GT_Pairs (:202-268) and
