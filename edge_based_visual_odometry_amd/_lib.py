@@ -60,6 +60,8 @@ ABI_SYMBOLS = (
     "ebvo_temporal_pose_constraint_metrics",
     "ebvo_pose_refine_default_params", "ebvo_pose_refine_from_quads", "ebvo_temporal_refine_pose",
     "ebvo_align_default_params", "ebvo_pose_align_edges", "ebvo_temporal_align_pose", "ebvo_temporal_align_size",
+    "ebvo_depth_default_params", "ebvo_depth_refine_edges", "ebvo_temporal_refine_depth", "ebvo_temporal_depth_fetch",
+    "ebvo_temporal_depth_reset", "ebvo_temporal_use_depth", "ebvo_pose_align_edges_depth",
 )
 
 
@@ -157,6 +159,19 @@ class AlignedPose(C.Structure):
                 ("n_assoc", C.c_int32 * 2), ("inliers", C.c_int64), ("cost_first", C.c_double), ("cost_last", C.c_double),
                 ("rms_normal", C.c_double)]
 
+
+class DepthParams(C.Structure):
+    _fields_ = [("sigma_disp_px", C.c_double), ("sigma_normal_px", C.c_double), ("huber_px", C.c_double), ("gate_px", C.c_double),
+                ("iterations", C.c_int32), ("cameras", C.c_int32), ("lambda_min", C.c_double), ("lambda_max", C.c_double),
+                ("info_max", C.c_double), ("img_margin", C.c_double), ("block_threads", C.c_int32), ("reserved", C.c_int32)]
+
+
+class DepthRefined(C.Structure):
+    _fields_ = [("n_kf", C.c_int32), ("n_dead", C.c_int32), ("n_updated", C.c_int32), ("n_restored", C.c_int32),
+                ("n_terms", C.c_int32 * 2), ("n_gated", C.c_int32 * 2), ("rms_before", C.c_double), ("rms_after", C.c_double)]
+
+
+DEPTH_DEAD, DEPTH_UPDATED, DEPTH_RESTORED, DEPTH_GATED_LEFT, DEPTH_GATED_RIGHT = 1, 2, 4, 8, 16   # flags of one update
 
 ALIGN_OK, ALIGN_NOTHING, ALIGN_PIVOT = 0, 1, 2   # the stop reasons are the refit's, 4 = fewer than min_terms associated terms
 (REFINE_STOP_EPS, REFINE_STOP_CAP, REFINE_STOP_COST, REFINE_STOP_PIVOT, REFINE_STOP_FEW) = range(5)
@@ -388,6 +403,23 @@ def load_library() -> C.CDLL:
                                              vp, vp]
     lib.ebvo_temporal_align_size.restype = i32
     lib.ebvo_temporal_align_size.argtypes = [vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.ebvo_depth_default_params.restype = None
+    lib.ebvo_depth_default_params.argtypes = [C.POINTER(DepthParams)]
+    lib.ebvo_depth_refine_edges.restype = i32
+    lib.ebvo_depth_refine_edges.argtypes = [vp, vp, vp, i32, vp, i32, vp, i32, vp, vp, i32, i32, C.POINTER(StereoCalib),
+                                            C.POINTER(DepthParams), vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(DepthRefined)]
+    lib.ebvo_temporal_refine_depth.restype = i32
+    lib.ebvo_temporal_refine_depth.argtypes = [vp, i32, C.POINTER(StereoCalib), C.POINTER(AlignParams), C.POINTER(DepthParams), vp, vp,
+                                               C.POINTER(DepthRefined)]
+    lib.ebvo_temporal_depth_fetch.restype = i32
+    lib.ebvo_temporal_depth_fetch.argtypes = [vp, vp, vp, vp, vp]
+    lib.ebvo_temporal_depth_reset.restype = i32
+    lib.ebvo_temporal_depth_reset.argtypes = [vp]
+    lib.ebvo_temporal_use_depth.restype = i32
+    lib.ebvo_temporal_use_depth.argtypes = [vp, i32]
+    lib.ebvo_pose_align_edges_depth.restype = i32
+    lib.ebvo_pose_align_edges_depth.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, C.POINTER(StereoCalib),
+                                                C.POINTER(AlignParams), vp, vp, C.POINTER(AlignedPose), vp, vp]
     lib.ebvo_gt_default_params.restype = None
     lib.ebvo_gt_default_params.argtypes = [C.POINTER(GtParams)]
     lib.ebvo_stereo_set_gt.argtypes = [vp, i32, vp, i32, i32, ssz, C.POINTER(StereoCalib), C.POINTER(GtParams)]

@@ -929,10 +929,12 @@ class Context:
         out["assoc_left"], out["assoc_right"] = assoc_left, assoc_right
         return out
 
-    def pose_align_edges(self, kf_left, kf_right, cf_edges_left, cf_edges_right, img_w: int, img_h: int, calib, R, t, **params) -> dict:
+    def pose_align_edges(self, kf_left, kf_right, cf_edges_left, cf_edges_right, img_w: int, img_h: int, calib, R, t, lambda_=None,
+                         **params) -> dict:
         """Alignment of the start pose (R, t) to the current frame's TOED edges on host arrays (ebvo_pose_align_edges):
-        cf_edges_right may be None with cameras=1.  params: the fields of ebvo_align_params.  Returns the fields of
-        ebvo_aligned_pose, R (3x3), t, and assoc_left / assoc_right (int32 per keyframe mate: edge index or -1)."""
+        cf_edges_right may be None with cameras=1.  params: the fields of ebvo_align_params.  lambda_ (one double per keyframe
+        mate): the alignment on Gamma / lambda (ebvo_pose_align_edges_depth).  Returns the fields of ebvo_aligned_pose, R (3x3),
+        t, and assoc_left / assoc_right (int32 per keyframe mate: edge index or -1)."""
         kfL, kfR, E0 = _edges(kf_left), _edges(kf_right), _edges(cf_edges_left)
         E1 = _edges(cf_edges_right) if cf_edges_right is not None else np.zeros(0, dtype=EDGE_DTYPE)
         if len(kfL) != len(kfR):
@@ -940,10 +942,16 @@ class Context:
         p, cal, r = self.align_params(**params), self._calib(calib), _lib.AlignedPose()
         R, t = self._start_pose(R, t)
         aL, aR = np.full(len(kfL), -1, dtype=np.int32), np.full(len(kfL), -1, dtype=np.int32)
-        self._check(self.lib.ebvo_pose_align_edges(self._ctx, ptr(kfL), ptr(kfR), len(kfL), ptr(E0), len(E0),
-                                                   ptr(E1) if cf_edges_right is not None else None, len(E1), int(img_w), int(img_h),
-                                                   C.byref(cal), C.byref(p), ptr(R), ptr(t), C.byref(r), ptr(aL), ptr(aR)),
-                    "ebvo_pose_align_edges")
+        tail = (ptr(E0), len(E0), ptr(E1) if cf_edges_right is not None else None, len(E1), int(img_w), int(img_h), C.byref(cal),
+                C.byref(p), ptr(R), ptr(t), C.byref(r), ptr(aL), ptr(aR))
+        if lambda_ is None:
+            self._check(self.lib.ebvo_pose_align_edges(self._ctx, ptr(kfL), ptr(kfR), len(kfL), *tail), "ebvo_pose_align_edges")
+        else:
+            lam = np.ascontiguousarray(lambda_, dtype=np.float64)
+            if lam.shape != (len(kfL),):
+                raise ValueError("lambda_ needs one value per keyframe mate")
+            self._check(self.lib.ebvo_pose_align_edges_depth(self._ctx, ptr(kfL), ptr(kfR), ptr(lam), len(kfL), *tail),
+                        "ebvo_pose_align_edges_depth")
         return self._aligned_dict(r, aL, aR)
 
     def temporal_align_pose(self, calib, R, t, slot: int = 0, **params) -> dict:
@@ -958,6 +966,86 @@ class Context:
         self._check(self.lib.ebvo_temporal_align_pose(self._ctx, slot, C.byref(cal), C.byref(p), ptr(R), ptr(t), C.byref(r), ptr(aL),
                                                       ptr(aR)), "ebvo_temporal_align_pose")
         return self._aligned_dict(r, aL, aR)
+
+    # -- inverse-depth filter of the keyframe mates, fed by aligned frames (the contract is in ebvo_hip.h) --------------------
+    def depth_params(self, **kw) -> _lib.DepthParams:
+        """ebvo_depth_params: the defaults of ebvo_depth_default_params with `kw` applied."""
+        p = _lib.DepthParams()
+        self.lib.ebvo_depth_default_params(C.byref(p))
+        fields = {name for name, _ in p._fields_}
+        for k, v in kw.items():
+            if k not in fields:
+                raise TypeError(f"depth: unknown parameter {k!r}")
+            setattr(p, k, v)
+        return p
+
+    @staticmethod
+    def _depth_dict(r) -> dict:
+        out = {k: getattr(r, k) for k in ("n_kf", "n_dead", "n_updated", "n_restored", "rms_before", "rms_after")}
+        out["n_terms"] = (int(r.n_terms[0]), int(r.n_terms[1]))
+        out["n_gated"] = (int(r.n_gated[0]), int(r.n_gated[1]))
+        return out
+
+    def depth_refine_edges(self, kf_left, kf_right, cf_edges_left, cf_edges_right, assoc_left, assoc_right, img_w: int, img_h: int,
+                           calib, R, t, state=None, **params) -> dict:
+        """One update of the mates' inverse-depth state on host arrays (ebvo_depth_refine_edges).  assoc_*: what
+        pose_align_edges returned (None: no term in that camera).  state: None (the prior) or (lambda, info, n_obs).  params:
+        the fields of ebvo_depth_params.  Returns the fields of ebvo_depth_refined and the new lambda, info, n_obs, flags."""
+        kfL, kfR, E0 = _edges(kf_left), _edges(kf_right), _edges(cf_edges_left)
+        E1 = _edges(cf_edges_right) if cf_edges_right is not None else np.zeros(0, dtype=EDGE_DTYPE)
+        n = len(kfL)
+        if len(kfR) != n:
+            raise ValueError("kf_left and kf_right differ in length")
+        assoc = []
+        for a in (assoc_left, assoc_right):
+            a = None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+            if a is not None and a.shape != (n,):
+                raise ValueError("an association array needs one value per keyframe mate")
+            assoc.append(a)
+        p, cal, r = self.depth_params(**params), self._calib(calib), _lib.DepthRefined()
+        R, t = self._start_pose(R, t)
+        lam, info, nobs, flags = np.ones(n), np.zeros(n), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.uint8)
+        if state is not None:
+            lam = np.array(state[0], dtype=np.float64)
+            info = np.array(state[1], dtype=np.float64)
+            nobs = np.array(state[2], dtype=np.int32)
+            if not (lam.shape == info.shape == nobs.shape == (n,)):
+                raise ValueError("the state needs one value per keyframe mate")
+        sin = (ptr(lam), ptr(info), ptr(nobs)) if state is not None else (None, None, None)
+        self._check(self.lib.ebvo_depth_refine_edges(self._ctx, ptr(kfL), ptr(kfR), n, ptr(E0), len(E0),
+                                                     ptr(E1) if cf_edges_right is not None else None, len(E1),
+                                                     None if assoc[0] is None else ptr(assoc[0]), None if assoc[1] is None else ptr(assoc[1]),
+                                                     int(img_w), int(img_h), C.byref(cal), C.byref(p), ptr(R), ptr(t), *sin, ptr(lam),
+                                                     ptr(info), ptr(nobs), ptr(flags), C.byref(r)), "ebvo_depth_refine_edges")
+        return dict(self._depth_dict(r), lambda_=lam, info=info, n_obs=nobs, flags=flags)
+
+    def temporal_refine_depth(self, calib, R, t, slot: int = 0, align=None, **params) -> dict:
+        """One update of the keyframe's resident state from the slot's resident pair under (R, t)
+        (ebvo_temporal_refine_depth).  align: a dict of ebvo_align_params fields (radius, cell_size, orient_thr_deg) for the
+        association; params: the fields of ebvo_depth_params."""
+        ap, dp, cal, r = self.align_params(**(align or {})), self.depth_params(**params), self._calib(calib), _lib.DepthRefined()
+        R, t = self._start_pose(R, t)
+        self._check(self.lib.ebvo_temporal_refine_depth(self._ctx, slot, C.byref(cal), C.byref(ap), C.byref(dp), ptr(R), ptr(t),
+                                                        C.byref(r)), "ebvo_temporal_refine_depth")
+        return self._depth_dict(r)
+
+    def temporal_depth_fetch(self, slot: int = 0) -> dict:
+        """lambda_, info, n_obs, flags of the keyframe's mates (ebvo_temporal_depth_fetch)."""
+        n_kf, n0, n1 = C.c_int32(), C.c_int32(), C.c_int32()
+        self._check(self.lib.ebvo_temporal_align_size(self._ctx, slot, C.byref(n_kf), C.byref(n0), C.byref(n1)),
+                    "ebvo_temporal_align_size")
+        n = n_kf.value
+        lam, info, nobs, flags = np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.uint8)
+        self._check(self.lib.ebvo_temporal_depth_fetch(self._ctx, ptr(lam), ptr(info), ptr(nobs), ptr(flags)), "ebvo_temporal_depth_fetch")
+        return dict(lambda_=lam, info=info, n_obs=nobs, flags=flags)
+
+    def temporal_depth_reset(self) -> None:
+        """The keyframe's state back to the prior (ebvo_temporal_depth_reset)."""
+        self._check(self.lib.ebvo_temporal_depth_reset(self._ctx), "ebvo_temporal_depth_reset")
+
+    def temporal_use_depth(self, on: bool) -> None:
+        """temporal_align_pose works on Gamma / lambda while on (ebvo_temporal_use_depth); default off."""
+        self._check(self.lib.ebvo_temporal_use_depth(self._ctx, 1 if on else 0), "ebvo_temporal_use_depth")
 
     # -- ground-truth evaluation from a disparity map (Find_Stereo_GT_Locations, get_Stereo_Edge_GT_Pairs,
     # -- Evaluate_Stereo_Edge_Correspondences) ---------------------------------------------------------------

@@ -663,13 +663,24 @@ AlignLayout align_layout(int n_kf, int tiles, int n_cells, const int ne[2])
     L.total = o;
     return L;
 }
-} // namespace
 
-// Every launch of the call is enqueued here, then the result record and the association arrays are copied back and waited
-// for.  d_E1 / n1 are not read with cameras = 1.
-int align_run(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, int n_kf, const ebvo_edge *d_E0, int n0,
-              const ebvo_edge *d_E1, int n1, int img_w, int img_h, const ebvo_stereo_calib *cal, const ebvo_align_params *ap,
-              const double *R0, const double *t0, AlignResult *res, int32_t *assoc_left, int32_t *assoc_right)
+// the workspace carved and the call's constants filled; nothing is enqueued
+struct AlignSetup
+{
+    AlignArgs A;
+    FinalCalib C;
+    AlignPose P0;
+    AlignState *d_state;
+    AlignResult *d_out;
+    double *d_tiles, *d_gt;
+    AssocPlanes P[2];
+    EdgeGrid g[2];
+    int ne[2], n_cells, tiles, bt;
+    unsigned anb;
+};
+
+int align_setup(ebvo_ctx *ctx, Slot &s, int n_kf, const ebvo_edge *d_E0, int n0, const ebvo_edge *d_E1, int n1, int img_w, int img_h,
+                const ebvo_stereo_calib *cal, const ebvo_align_params *ap, const double *R0, const double *t0, AlignSetup &S)
 {
     const int cams = ap->cameras, cell = ap->cell_size;
     const int gw = (int)(((int64_t)img_w + cell - 1) / cell), gh = (int)(((int64_t)img_h + cell - 1) / cell), n_cells = gw * gh;
@@ -679,15 +690,18 @@ int align_run(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d
     if (int rc = ebvo_grow(ctx, s, s.align_ws, L.total))
         return rc;
     char *base = (char *)s.align_ws.p;
-    hipStream_t st = s.stream;
-    AlignState *d_state = (AlignState *)(base + L.o_state);
-    AlignResult *d_out = (AlignResult *)(base + L.o_out);
-    double *d_tiles = (double *)(base + L.o_tiles), *d_gt = (double *)(base + L.o_gt);
+    S.d_state = (AlignState *)(base + L.o_state);
+    S.d_out = (AlignResult *)(base + L.o_out);
+    S.d_tiles = (double *)(base + L.o_tiles);
+    S.d_gt = (double *)(base + L.o_gt);
+    S.n_cells = n_cells;
+    S.tiles = tiles;
     const size_t n = (size_t)n_kf;
-    AssocPlanes P[2];
-    EdgeGrid g[2];
+    AssocPlanes *P = S.P;
+    EdgeGrid *g = S.g;
     for (int c = 0; c < 2; ++c)
     {
+        S.ne[c] = ne[c];
         char *a = base + L.o_assoc[c];
         P[c].idx = (int32_t *)a;
         P[c].ex = (double *)(a + al64(sizeof(int32_t) * n));
@@ -703,8 +717,8 @@ int align_run(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d
         g[c].start = g[c].fill + n_cells;
         g[c].list = g[c].start + n_cells + 1;
     }
-    AlignArgs A;
-    const FinalCalib C = final_calib_host(cal->K_left, cal->K_right, cal->R21, cal->T21); // the TRUE K_right, as the prior's projection
+    AlignArgs &A = S.A;
+    const FinalCalib C = S.C = final_calib_host(cal->K_left, cal->K_right, cal->R21, cal->T21); // the TRUE K_right, as the prior's projection
     memcpy(A.Kl, cal->K_left, sizeof A.Kl);
     memcpy(A.Kr, cal->K_right, sizeof A.Kr);
     memcpy(A.Kli, C.Kli, sizeof A.Kli);
@@ -728,30 +742,94 @@ int align_run(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d
     A.gw = gw;
     A.gh = gh;
     A.tiles = tiles;
-    AlignPose P0;
-    memcpy(P0.Rt, R0, sizeof(double) * 9);
-    memcpy(P0.Rt + 9, t0, sizeof(double) * 3);
-    const int bt = ap->block_threads ? ap->block_threads : AL_TILE;
+    memcpy(S.P0.Rt, R0, sizeof(double) * 9);
+    memcpy(S.P0.Rt + 9, t0, sizeof(double) * 3);
+    S.bt = ap->block_threads ? ap->block_threads : AL_TILE;
+    const int64_t ab = ((int64_t)n_kf * cams + 15) / 16; // 16 items per block of 256 threads
+    S.anb = chain_grid_cap(s, (unsigned)(ab > 8192 ? 8192 : ab));
+    return EBVO_OK;
+}
+
+// what precedes the first association: the state, Gamma and T1 (over d_lambda for the live mates when the keyframe's refined
+// depths are in use: one more launch, depth_kernels.hip), the two edge grids
+int align_enqueue_front(ebvo_ctx *ctx, Slot &s, const AlignSetup &S, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, const double *d_lambda)
+{
+    hipStream_t st = s.stream;
+    const int n_kf = S.A.n_kf, n_cells = S.n_cells;
+    hipLaunchKernelGGL(align_init_kernel, dim3(1), dim3(64), 0, st, S.d_state, S.P0);
+    const int64_t pb = ((int64_t)n_kf + 255) / 256;
+    hipLaunchKernelGGL(align_prepare_kernel, dim3(chain_grid_cap(s, (unsigned)(pb > 2048 ? 2048 : pb))), dim3(256), 0, st, S.C, d_kfL, d_kfR,
+                       n_kf, S.d_gt);
+    if (d_lambda)
+        depth_scale_enqueue(s, S.d_gt, n_kf, d_lambda);
+    for (int c = 0; c < S.A.cameras; ++c)
+    {
+        const EdgeGrid &g = S.g[c];
+        // cnt and fill, and start too: a camera without edges still has an (all-zero) start array
+        EBVO_HIP(ctx, hipMemsetAsync(g.cnt, 0, sizeof(int32_t) * (3 * (size_t)n_cells + 1), st));
+        if (S.ne[c] <= 0)
+            continue;
+        const int64_t eb = ((int64_t)S.ne[c] + 255) / 256;
+        const unsigned nb = chain_grid_cap(s, (unsigned)(eb > 2048 ? 2048 : eb));
+        hipLaunchKernelGGL(align_cells_kernel, dim3(nb), dim3(256), 0, st, g.E, S.ne[c], S.A.cell, S.A.gw, S.A.gh, g.cell_of, g.cnt);
+        hipLaunchKernelGGL(align_cell_scan_kernel, dim3(1), dim3(256), 0, st, g.cnt, n_cells, g.start);
+        hipLaunchKernelGGL(align_cell_scatter_kernel, dim3(nb), dim3(256), 0, st, g.cell_of, S.ne[c], g.start, g.fill, g.list);
+    }
+    return EBVO_OK;
+}
+} // namespace
+
+void align_prepare_enqueue(const Slot &s, const ebvo_stereo_calib *cal, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, int n_kf, double *d_gt)
+{
+    const FinalCalib C = final_calib_host(cal->K_left, cal->K_right, cal->R21, cal->T21);
+    const int64_t pb = ((int64_t)n_kf + 255) / 256;
+    hipLaunchKernelGGL(align_prepare_kernel, dim3(chain_grid_cap(s, (unsigned)(pb > 2048 ? 2048 : pb))), dim3(256), 0, s.stream, C, d_kfL, d_kfR,
+                       n_kf, d_gt);
+}
+
+// One association under (R, t), enqueued and not waited for: the edge index (or -1) per mate and camera stays in the workspace.
+int align_associate_once(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, int n_kf, const ebvo_edge *d_E0, int n0,
+                         const ebvo_edge *d_E1, int n1, int img_w, int img_h, const ebvo_stereo_calib *cal, const ebvo_align_params *ap,
+                         const double *R, const double *t, const double *d_lambda, const int32_t **idx0, const int32_t **idx1)
+{
+    AlignSetup S;
+    if (int rc = align_setup(ctx, s, n_kf, d_E0, n0, d_E1, n1, img_w, img_h, cal, ap, R, t, S))
+        return rc;
     {
         ProfScope ps(ctx, s, K_MISC);
-        hipLaunchKernelGGL(align_init_kernel, dim3(1), dim3(64), 0, st, d_state, P0);
-        const int64_t pb = ((int64_t)n_kf + 255) / 256;
-        hipLaunchKernelGGL(align_prepare_kernel, dim3(chain_grid_cap(s, (unsigned)(pb > 2048 ? 2048 : pb))), dim3(256), 0, st, C, d_kfL, d_kfR,
-                           n_kf, d_gt);
-        for (int c = 0; c < cams; ++c)
-        {
-            // cnt and fill, and start too: a camera without edges still has an (all-zero) start array
-            EBVO_HIP(ctx, hipMemsetAsync(g[c].cnt, 0, sizeof(int32_t) * (3 * (size_t)n_cells + 1), st));
-            if (ne[c] <= 0)
-                continue;
-            const int64_t eb = ((int64_t)ne[c] + 255) / 256;
-            const unsigned nb = chain_grid_cap(s, (unsigned)(eb > 2048 ? 2048 : eb));
-            hipLaunchKernelGGL(align_cells_kernel, dim3(nb), dim3(256), 0, st, g[c].E, ne[c], cell, gw, gh, g[c].cell_of, g[c].cnt);
-            hipLaunchKernelGGL(align_cell_scan_kernel, dim3(1), dim3(256), 0, st, g[c].cnt, n_cells, g[c].start);
-            hipLaunchKernelGGL(align_cell_scatter_kernel, dim3(nb), dim3(256), 0, st, g[c].cell_of, ne[c], g[c].start, g[c].fill, g[c].list);
-        }
-        const int64_t ab = ((int64_t)n_kf * cams + 15) / 16; // 16 items per block of 256 threads
-        const unsigned anb = chain_grid_cap(s, (unsigned)(ab > 8192 ? 8192 : ab));
+        if (int rc = align_enqueue_front(ctx, s, S, d_kfL, d_kfR, d_lambda))
+            return rc;
+        hipLaunchKernelGGL(align_associate_kernel, dim3(S.anb), dim3(256), 0, s.stream, S.A, S.d_state, -1, S.d_gt, S.g[0], S.g[1], S.P[0], S.P[1]);
+    }
+    EBVO_HIP(ctx, hipGetLastError());
+    *idx0 = S.P[0].idx;
+    *idx1 = ap->cameras > 1 ? S.P[1].idx : nullptr;
+    return EBVO_OK;
+}
+
+// Every launch of the call is enqueued here, then the result record and the association arrays are copied back and waited
+// for.  d_E1 / n1 are not read with cameras = 1.  d_lambda (may be NULL): the keyframe's inverse-depth ratios.
+int align_run(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, int n_kf, const ebvo_edge *d_E0, int n0,
+              const ebvo_edge *d_E1, int n1, int img_w, int img_h, const ebvo_stereo_calib *cal, const ebvo_align_params *ap,
+              const double *R0, const double *t0, const double *d_lambda, AlignResult *res, int32_t *assoc_left, int32_t *assoc_right)
+{
+    AlignSetup S;
+    if (int rc = align_setup(ctx, s, n_kf, d_E0, n0, d_E1, n1, img_w, img_h, cal, ap, R0, t0, S))
+        return rc;
+    const AlignArgs &A = S.A;
+    const AssocPlanes *P = S.P;
+    const EdgeGrid *g = S.g;
+    AlignState *d_state = S.d_state;
+    double *d_tiles = S.d_tiles, *d_gt = S.d_gt;
+    AlignResult *d_out = S.d_out;
+    const int cams = ap->cameras, tiles = S.tiles, bt = S.bt;
+    const unsigned anb = S.anb;
+    const size_t n = (size_t)n_kf;
+    hipStream_t st = s.stream;
+    {
+        ProfScope ps(ctx, s, K_MISC);
+        if (int rc = align_enqueue_front(ctx, s, S, d_kfL, d_kfR, d_lambda))
+            return rc;
         for (int rnd = 0; rnd < ap->rounds; ++rnd)
         {
             hipLaunchKernelGGL(align_associate_kernel, dim3(anb), dim3(256), 0, st, A, d_state, rnd, d_gt, g[0], g[1], P[0], P[1]);

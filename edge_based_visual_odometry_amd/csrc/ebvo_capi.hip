@@ -175,7 +175,7 @@ static void slot_destroy(Slot *s)
                        &s->keep,         &s->patches_raw,  &s->patches_norm,   &s->patches_flag,   &s->patches_norm_r,
                        &s->patches_flag_r, &s->pair_left,  &s->sincos,         &s->scratch_b,      &s->scratch_c,
                        &s->scratch_d,    &s->fetch_pack,   &s->pose_in,        &s->pose_geom,      &s->pose_order,
-                       &s->pose_draw,    &s->pose_hyp,       &s->pose_sel,       &s->pose_casc,       &s->pose_refit,     &s->align_up,       &s->align_ws,       &s->gt_disp,        &s->gt_geom,        &s->gt_flags,
+                       &s->pose_draw,    &s->pose_hyp,       &s->pose_sel,       &s->pose_casc,       &s->pose_refit,     &s->align_up,       &s->align_ws,       &s->depth_up,       &s->depth_ws,       &s->gt_disp,        &s->gt_geom,        &s->gt_flags,
                        &s->gt_boxes,     &s->gt_pool_i32,  &s->gt_pool_idx,    &s->gt_rows,        &s->gt_tot,
                        &s->gt_up,        &s->tgt_geom,     &s->tgt_i32,        &s->tgt_idx,        &s->tgt_u8,
                        &s->tgt_rows,     &s->tgt_flags,    &s->tgt_tot,        &s->tgt_up,
@@ -401,6 +401,10 @@ extern "C" void ebvo_ctx_destroy(ebvo_ctx *ctx)
     (void)hipFree(ctx->kf_imgL);
     (void)hipFree(ctx->kf_imgR);
     (void)hipFree(ctx->kf_Rf);
+    (void)hipFree(ctx->kf_lambda);
+    (void)hipFree(ctx->kf_info);
+    (void)hipFree(ctx->kf_nobs);
+    (void)hipFree(ctx->kf_dflags);
     for (PinnedBuf *b : {&ctx->sw_toed[0], &ctx->sw_toed[1], &ctx->sw_cand, &ctx->sw_ncc, &ctx->sw_up})
         if (b->p)
             (void)hipHostFree(b->p);
@@ -3282,6 +3286,7 @@ extern "C" int ebvo_temporal_set_keyframe(ebvo_ctx *ctx, int slot)
         ctx->kf_cap = cap;
     }
     ctx->kf_n = (int)n;
+    ctx->kf_depth_fresh = true; // the new keyframe's mates are at the prior
     ++ctx->kf_gen; // quads matched against the previous keyframe no longer belong to ctx->kf_L / kf_R
     {
         // the keyframe's undistorted images stay with it: the photometric refinement of the quads samples them
@@ -4409,10 +4414,11 @@ static void align_publish(const AlignResult &r, int n_kf, ebvo_aligned_pose *out
     out->rms_normal = r.rms_normal;
 }
 
-extern "C" int ebvo_pose_align_edges(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *kf_right, int n_kf,
-                                     const ebvo_edge *cf_edges_left, int n0, const ebvo_edge *cf_edges_right, int n1, int img_w,
-                                     int img_h, const ebvo_stereo_calib *cal, const ebvo_align_params *params, const double R0[9],
-                                     const double t0[3], ebvo_aligned_pose *out, int32_t *assoc_left, int32_t *assoc_right)
+// lambda (host, may be NULL): the inverse-depth ratio per mate (ebvo_pose_align_edges_depth)
+static int align_edges_host(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *kf_right, const double *lambda, int n_kf,
+                            const ebvo_edge *cf_edges_left, int n0, const ebvo_edge *cf_edges_right, int n1, int img_w, int img_h,
+                            const ebvo_stereo_calib *cal, const ebvo_align_params *params, const double *R0, const double *t0,
+                            ebvo_aligned_pose *out, int32_t *assoc_left, int32_t *assoc_right)
 {
     if (!ctx || !align_args_ok(cal, params, R0, t0, out, img_w, img_h) || n_kf < 0 || n0 < 0 || (n_kf > 0 && (!kf_left || !kf_right)) ||
         (n0 > 0 && !cf_edges_left))
@@ -4433,7 +4439,7 @@ extern "C" int ebvo_pose_align_edges(ebvo_ctx *ctx, const ebvo_edge *kf_left, co
     }
     EBVO_HIP(ctx, hipSetDevice(ctx->device));
     const size_t nz = (size_t)n_kf, o_kfR = sizeof(ebvo_edge) * nz, o_E0 = 2 * o_kfR, o_E1 = o_E0 + sizeof(ebvo_edge) * (size_t)n0,
-                 total = o_E1 + sizeof(ebvo_edge) * (size_t)n1 + 64;
+                 o_lam = (o_E1 + sizeof(ebvo_edge) * (size_t)n1 + 63) & ~(size_t)63, total = o_lam + (lambda ? sizeof(double) * nz : 0) + 64;
     if ((rc = gt_grow(ctx, s, s.align_up, total)))
         return rc;
     char *base = (char *)s.align_up.p;
@@ -4445,10 +4451,13 @@ extern "C" int ebvo_pose_align_edges(ebvo_ctx *ctx, const ebvo_edge *kf_left, co
         EBVO_HIP(ctx, hipMemcpyAsync(E0, cf_edges_left, sizeof(ebvo_edge) * (size_t)n0, hipMemcpyHostToDevice, st));
     if (n1)
         EBVO_HIP(ctx, hipMemcpyAsync(E1, cf_edges_right, sizeof(ebvo_edge) * (size_t)n1, hipMemcpyHostToDevice, st));
+    double *d_lam = lambda ? (double *)(base + o_lam) : nullptr;
+    if (lambda)
+        EBVO_HIP(ctx, hipMemcpyAsync(d_lam, lambda, sizeof(double) * nz, hipMemcpyHostToDevice, st));
     AlignResult r;
     {
         const TemporalGridScope grid_scope(ctx, s);
-        rc = align_run(ctx, s, kfL, kfR, n_kf, E0, n0, E1, n1, img_w, img_h, cal, params, R0, t0, &r, assoc_left, assoc_right);
+        rc = align_run(ctx, s, kfL, kfR, n_kf, E0, n0, E1, n1, img_w, img_h, cal, params, R0, t0, d_lam, &r, assoc_left, assoc_right);
     }
     if (rc)
     {
@@ -4457,6 +4466,25 @@ extern "C" int ebvo_pose_align_edges(ebvo_ctx *ctx, const ebvo_edge *kf_left, co
     }
     align_publish(r, n_kf, out);
     return EBVO_OK;
+}
+
+extern "C" int ebvo_pose_align_edges(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *kf_right, int n_kf,
+                                     const ebvo_edge *cf_edges_left, int n0, const ebvo_edge *cf_edges_right, int n1, int img_w,
+                                     int img_h, const ebvo_stereo_calib *cal, const ebvo_align_params *params, const double R0[9],
+                                     const double t0[3], ebvo_aligned_pose *out, int32_t *assoc_left, int32_t *assoc_right)
+{
+    return align_edges_host(ctx, kf_left, kf_right, nullptr, n_kf, cf_edges_left, n0, cf_edges_right, n1, img_w, img_h, cal, params, R0, t0,
+                            out, assoc_left, assoc_right);
+}
+
+extern "C" int ebvo_pose_align_edges_depth(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *kf_right, const double *lambda,
+                                           int n_kf, const ebvo_edge *cf_edges_left, int n0, const ebvo_edge *cf_edges_right, int n1,
+                                           int img_w, int img_h, const ebvo_stereo_calib *cal, const ebvo_align_params *params,
+                                           const double R0[9], const double t0[3], ebvo_aligned_pose *out, int32_t *assoc_left,
+                                           int32_t *assoc_right)
+{
+    return align_edges_host(ctx, kf_left, kf_right, lambda, n_kf, cf_edges_left, n0, cf_edges_right, n1, img_w, img_h, cal, params, R0, t0,
+                            out, assoc_left, assoc_right);
 }
 
 // a keyframe, and a pair on the slot whose wait has returned, nothing of the slot in flight
@@ -4509,12 +4537,283 @@ extern "C" int ebvo_temporal_align_pose(ebvo_ctx *ctx, int slot, const ebvo_ster
     int rc;
     {
         const TemporalGridScope grid_scope(ctx, s);
-        rc = align_run(ctx, s, ctx->kf_L, ctx->kf_R, n_kf, s.im[0].edges, n0, s.im[1].edges, n1, s.cur_w, s.cur_h, cal, params, R0, t0, &r,
-                       assoc_left, assoc_right);
+        // the keyframe's refined depths, when they are in use and a frame has been fused (at the prior lambda is 1)
+        const double *d_lam = ctx->use_depth && !ctx->kf_depth_fresh ? ctx->kf_lambda : nullptr;
+        rc = align_run(ctx, s, ctx->kf_L, ctx->kf_R, n_kf, s.im[0].edges, n0, s.im[1].edges, n1, s.cur_w, s.cur_h, cal, params, R0, t0, d_lam,
+                       &r, assoc_left, assoc_right);
     }
     if (rc)
         return rc;
     align_publish(r, n_kf, out);
+    return EBVO_OK;
+}
+
+// ---- inverse-depth filter of the keyframe mates (depth_kernels.hip) -----------------------------------------------------
+extern "C" void ebvo_depth_default_params(ebvo_depth_params *p)
+{
+    if (!p)
+        return;
+    p->sigma_disp_px = 0.25;
+    p->sigma_normal_px = 0.5;
+    p->huber_px = 1.0;
+    p->gate_px = 3.0;
+    p->iterations = 3;
+    p->cameras = 2;
+    p->lambda_min = 0.25;
+    p->lambda_max = 4.0;
+    p->info_max = 1e6;
+    p->img_margin = 10.0;
+    p->block_threads = 0;
+    p->reserved = 0;
+}
+
+static bool depth_args_ok(const ebvo_stereo_calib *cal, const ebvo_depth_params *dp, const double *R, const double *t,
+                          const ebvo_depth_refined *out, int img_w, int img_h)
+{
+    if (!cal || !dp || !R || !t || !out || img_w < 1 || img_h < 1)
+        return false;
+    for (int i = 0; i < 9; ++i)
+        if (!std::isfinite(R[i]))
+            return false;
+    for (int i = 0; i < 3; ++i)
+        if (!std::isfinite(t[i]))
+            return false;
+    const int bt = dp->block_threads;
+    // every comparison is false for a NaN
+    return std::isfinite(dp->sigma_disp_px) && dp->sigma_disp_px > 0 && std::isfinite(dp->sigma_normal_px) && dp->sigma_normal_px > 0 &&
+           dp->huber_px > 0 && dp->gate_px > 0 && dp->iterations >= 0 && dp->iterations <= 16 && std::isfinite(dp->lambda_max) &&
+           dp->lambda_min > 0 && dp->lambda_min <= dp->lambda_max && dp->info_max > 0 && dp->img_margin >= 0 &&
+           (dp->cameras == 1 || dp->cameras == 2) && (bt == 0 || bt == 256 || bt == 512 || bt == 1024) && dp->reserved == 0;
+}
+
+static void depth_publish(const DepthRecord &r, int n_kf, ebvo_depth_refined *out)
+{
+    memset(out, 0, sizeof *out);
+    out->n_kf = n_kf;
+    out->n_dead = r.n_dead;
+    out->n_updated = r.n_updated;
+    out->n_restored = r.n_restored;
+    for (int c = 0; c < 2; ++c)
+    {
+        out->n_terms[c] = r.n_terms[c];
+        out->n_gated[c] = r.n_gated[c];
+    }
+    out->rms_before = r.rms_before;
+    out->rms_after = r.rms_after;
+}
+
+extern "C" int ebvo_depth_refine_edges(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *kf_right, int n_kf,
+                                       const ebvo_edge *cf_edges_left, int n0, const ebvo_edge *cf_edges_right, int n1,
+                                       const int32_t *assoc_left, const int32_t *assoc_right, int img_w, int img_h,
+                                       const ebvo_stereo_calib *cal, const ebvo_depth_params *params, const double R[9], const double t[3],
+                                       const double *lambda_in, const double *info_in, const int32_t *n_obs_in, double *lambda,
+                                       double *info, int32_t *n_obs, uint8_t *flags, ebvo_depth_refined *out)
+{
+    if (!ctx || !depth_args_ok(cal, params, R, t, out, img_w, img_h) || n_kf < 0 || n0 < 0 ||
+        (n_kf > 0 && (!kf_left || !kf_right || !lambda || !info || !n_obs || !flags)) || (n0 > 0 && !cf_edges_left))
+        return EBVO_ERR_ARG;
+    const int have_in = (lambda_in ? 1 : 0) + (info_in ? 1 : 0) + (n_obs_in ? 1 : 0);
+    if (have_in != 0 && have_in != 3)
+        return EBVO_ERR_ARG;
+    if (params->cameras == 1)
+        n1 = 0;
+    else if (n1 < 0 || (n1 > 0 && !cf_edges_right))
+        return EBVO_ERR_ARG;
+    int rc;
+    Slot *sp;
+    if ((rc = gt_host_slot(ctx, &sp)))
+        return rc;
+    Slot &s = *sp;
+    if (n_kf == 0)
+    {
+        memset(out, 0, sizeof *out);
+        return EBVO_OK;
+    }
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nz = (size_t)n_kf, eb = sizeof(ebvo_edge);
+    auto up64 = [](size_t v) { return (v + 63) & ~(size_t)63; };
+    // kf_left, kf_right, E0, E1, assoc x 2, lambda, info, n_obs, flags
+    const size_t o_kfR = up64(eb * nz), o_E0 = o_kfR + up64(eb * nz), o_E1 = o_E0 + up64(eb * (size_t)n0), o_a0 = o_E1 + up64(eb * (size_t)n1),
+                 o_a1 = o_a0 + up64(4 * nz), o_lam = o_a1 + up64(4 * nz), o_info = o_lam + up64(8 * nz), o_nobs = o_info + up64(8 * nz),
+                 o_fl = o_nobs + up64(4 * nz), total = o_fl + up64(nz);
+    if ((rc = gt_grow(ctx, s, s.depth_up, total)))
+        return rc;
+    char *base = (char *)s.depth_up.p;
+    ebvo_edge *kfL = (ebvo_edge *)base, *kfR = (ebvo_edge *)(base + o_kfR), *E0 = (ebvo_edge *)(base + o_E0), *E1 = (ebvo_edge *)(base + o_E1);
+    int32_t *a0 = (int32_t *)(base + o_a0), *a1 = (int32_t *)(base + o_a1), *d_nobs = (int32_t *)(base + o_nobs);
+    double *d_lam = (double *)(base + o_lam), *d_info = (double *)(base + o_info);
+    uint8_t *d_fl = (uint8_t *)(base + o_fl);
+    hipStream_t st = s.stream;
+    const bool right = params->cameras > 1 && assoc_right;
+    DepthRecord r;
+    auto enqueue = [&]() -> int {
+        EBVO_HIP(ctx, hipMemcpyAsync(kfL, kf_left, eb * nz, hipMemcpyHostToDevice, st));
+        EBVO_HIP(ctx, hipMemcpyAsync(kfR, kf_right, eb * nz, hipMemcpyHostToDevice, st));
+        if (n0)
+            EBVO_HIP(ctx, hipMemcpyAsync(E0, cf_edges_left, eb * (size_t)n0, hipMemcpyHostToDevice, st));
+        if (n1)
+            EBVO_HIP(ctx, hipMemcpyAsync(E1, cf_edges_right, eb * (size_t)n1, hipMemcpyHostToDevice, st));
+        if (assoc_left)
+            EBVO_HIP(ctx, hipMemcpyAsync(a0, assoc_left, 4 * nz, hipMemcpyHostToDevice, st));
+        if (right)
+            EBVO_HIP(ctx, hipMemcpyAsync(a1, assoc_right, 4 * nz, hipMemcpyHostToDevice, st));
+        if (have_in)
+        {
+            EBVO_HIP(ctx, hipMemcpyAsync(d_lam, lambda_in, 8 * nz, hipMemcpyHostToDevice, st));
+            EBVO_HIP(ctx, hipMemcpyAsync(d_info, info_in, 8 * nz, hipMemcpyHostToDevice, st));
+            EBVO_HIP(ctx, hipMemcpyAsync(d_nobs, n_obs_in, 4 * nz, hipMemcpyHostToDevice, st));
+        }
+        const TemporalGridScope grid_scope(ctx, s);
+        if (int rc2 = depth_run(ctx, s, kfL, kfR, n_kf, E0, n0, E1, n1, assoc_left ? a0 : nullptr, right ? a1 : nullptr, img_w, img_h, cal, params,
+                                R, t, have_in ? d_lam : nullptr, have_in ? d_info : nullptr, have_in ? d_nobs : nullptr, d_lam, d_info,
+                                d_nobs, d_fl, &r))
+            return rc2;
+        EBVO_HIP(ctx, hipMemcpyAsync(lambda, d_lam, 8 * nz, hipMemcpyDeviceToHost, st));
+        EBVO_HIP(ctx, hipMemcpyAsync(info, d_info, 8 * nz, hipMemcpyDeviceToHost, st));
+        EBVO_HIP(ctx, hipMemcpyAsync(n_obs, d_nobs, 4 * nz, hipMemcpyDeviceToHost, st));
+        EBVO_HIP(ctx, hipMemcpyAsync(flags, d_fl, nz, hipMemcpyDeviceToHost, st));
+        return EBVO_OK;
+    };
+    rc = enqueue();
+    const hipError_t e = hipStreamSynchronize(st); // the copies read and write the caller's arrays: none of them outlives the call
+    if (rc)
+        return rc;
+    EBVO_HIP(ctx, e);
+    depth_publish(r, n_kf, out);
+    return EBVO_OK;
+}
+
+// the keyframe's state arrays hold kf_n values
+static int depth_state_ensure(ebvo_ctx *ctx)
+{
+    const size_t n = (size_t)ctx->kf_n;
+    if (n <= ctx->kf_depth_cap && ctx->kf_lambda)
+        return EBVO_OK;
+    EBVO_HIP(ctx, hipDeviceSynchronize());
+    for (void *p : {(void *)ctx->kf_lambda, (void *)ctx->kf_info, (void *)ctx->kf_nobs, (void *)ctx->kf_dflags})
+        (void)hipFree(p);
+    ctx->kf_lambda = ctx->kf_info = nullptr;
+    ctx->kf_nobs = nullptr;
+    ctx->kf_dflags = nullptr;
+    ctx->kf_depth_cap = 0;
+    ctx->kf_depth_fresh = true;
+    const size_t cap = n + n / 4 + 64;
+    if (hipMalloc(&ctx->kf_lambda, 8 * cap) != hipSuccess || hipMalloc(&ctx->kf_info, 8 * cap) != hipSuccess ||
+        hipMalloc(&ctx->kf_nobs, 4 * cap) != hipSuccess || hipMalloc(&ctx->kf_dflags, cap) != hipSuccess)
+    {
+        (void)hipGetLastError();
+        ctx->last_error = "hipMalloc failed (keyframe depth state)";
+        return EBVO_ERR_NOMEM;
+    }
+    ctx->kf_depth_cap = cap;
+    return EBVO_OK;
+}
+
+extern "C" int ebvo_temporal_refine_depth(ebvo_ctx *ctx, int slot, const ebvo_stereo_calib *cal, const ebvo_align_params *align_params,
+                                          const ebvo_depth_params *depth_params, const double R[9], const double t[3],
+                                          ebvo_depth_refined *out)
+{
+    Slot *sp;
+    if (get_slot(ctx, slot, &sp))
+        return EBVO_ERR_ARG;
+    Slot &s = *sp;
+    const int w = s.have_run ? s.cur_w : 1, h = s.have_run ? s.cur_h : 1;
+    ebvo_aligned_pose unused;
+    if (!depth_args_ok(cal, depth_params, R, t, out, w, h) || !align_args_ok(cal, align_params, R, t, &unused, w, h))
+        return EBVO_ERR_ARG;
+    if (int rc = align_slot_state(ctx, s))
+        return rc;
+    const int n_kf = ctx->kf_n, n0 = s.im[0].n_kept, n1 = depth_params->cameras > 1 ? s.im[1].n_kept : 0;
+    if (n_kf == 0)
+    {
+        memset(out, 0, sizeof *out);
+        return EBVO_OK;
+    }
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = depth_state_ensure(ctx))
+        return rc;
+    ebvo_align_params ap = *align_params;
+    ap.cameras = depth_params->cameras;
+    const bool fresh = ctx->kf_depth_fresh;
+    DepthRecord r;
+    int rc;
+    {
+        const TemporalGridScope grid_scope(ctx, s);
+        const int32_t *idx0 = nullptr, *idx1 = nullptr;
+        rc = EBVO_OK;
+        if (n0 + (int64_t)n1 > 0) // without an edge nothing can be associated: every live mate is restored
+            rc = align_associate_once(ctx, s, ctx->kf_L, ctx->kf_R, n_kf, s.im[0].edges, n0, s.im[1].edges, n1, s.cur_w, s.cur_h, cal, &ap, R, t,
+                                      fresh ? nullptr : ctx->kf_lambda, &idx0, &idx1);
+        if (!rc)
+            rc = depth_run(ctx, s, ctx->kf_L, ctx->kf_R, n_kf, s.im[0].edges, n0, s.im[1].edges, n1, idx0, idx1, s.cur_w, s.cur_h, cal,
+                           depth_params, R, t, fresh ? nullptr : ctx->kf_lambda, fresh ? nullptr : ctx->kf_info,
+                           fresh ? nullptr : ctx->kf_nobs, ctx->kf_lambda, ctx->kf_info, ctx->kf_nobs, ctx->kf_dflags, &r);
+    }
+    const hipError_t e = hipStreamSynchronize(s.stream);
+    if (rc)
+        return rc;
+    EBVO_HIP(ctx, e);
+    ctx->kf_depth_fresh = false;
+    depth_publish(r, n_kf, out);
+    return EBVO_OK;
+}
+
+extern "C" int ebvo_temporal_depth_fetch(ebvo_ctx *ctx, double *lambda, double *info, int32_t *n_obs, uint8_t *flags)
+{
+    if (!ctx)
+        return EBVO_ERR_ARG;
+    if (ctx->kf_n < 0)
+    {
+        ctx->last_error = "no keyframe (ebvo_temporal_set_keyframe first)";
+        return EBVO_ERR_STATE;
+    }
+    const size_t n = (size_t)ctx->kf_n;
+    if (ctx->kf_depth_fresh || n == 0)
+    {
+        for (size_t i = 0; i < n; ++i)
+        {
+            if (lambda)
+                lambda[i] = 1.0;
+            if (info)
+                info[i] = 0.0;
+            if (n_obs)
+                n_obs[i] = 0;
+            if (flags)
+                flags[i] = 0;
+        }
+        return EBVO_OK;
+    }
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    // every call that writes the state waits for its stream before it returns
+    if (lambda)
+        EBVO_HIP(ctx, hipMemcpy(lambda, ctx->kf_lambda, 8 * n, hipMemcpyDeviceToHost));
+    if (info)
+        EBVO_HIP(ctx, hipMemcpy(info, ctx->kf_info, 8 * n, hipMemcpyDeviceToHost));
+    if (n_obs)
+        EBVO_HIP(ctx, hipMemcpy(n_obs, ctx->kf_nobs, 4 * n, hipMemcpyDeviceToHost));
+    if (flags)
+        EBVO_HIP(ctx, hipMemcpy(flags, ctx->kf_dflags, n, hipMemcpyDeviceToHost));
+    return EBVO_OK;
+}
+
+extern "C" int ebvo_temporal_depth_reset(ebvo_ctx *ctx)
+{
+    if (!ctx)
+        return EBVO_ERR_ARG;
+    if (ctx->kf_n < 0)
+    {
+        ctx->last_error = "no keyframe (ebvo_temporal_set_keyframe first)";
+        return EBVO_ERR_STATE;
+    }
+    ctx->kf_depth_fresh = true;
+    return EBVO_OK;
+}
+
+extern "C" int ebvo_temporal_use_depth(ebvo_ctx *ctx, int on)
+{
+    if (!ctx)
+        return EBVO_ERR_ARG;
+    ctx->use_depth = on != 0;
     return EBVO_OK;
 }
 

@@ -186,6 +186,8 @@ struct Slot
                                  // counters and stage bytes
     GrowBuf align_up, align_ws;  // edge alignment (align_kernels.hip): the uploaded lists of the host-array call; the state, tile sums,
                                  // planes and both edge grids of either call
+    GrowBuf depth_up, depth_ws;  // inverse-depth filter (depth_kernels.hip): the uploaded arrays of the host-array call; Gamma and T1,
+                                 // the tile sums and the record of either call
     GrowBuf pose_refit;          // inlier refit (pose_refit_kernels.hip): seven planes per quad, the fit set, the mask, the result
     // ground-truth evaluation (gt_kernels.hip, ebvo_stereo_set_gt): armed = the buffers below describe the resident pair
     GrowBuf gt_disp, gt_geom, gt_flags, gt_boxes, gt_pool_i32, gt_pool_idx, gt_rows, gt_tot;
@@ -342,6 +344,13 @@ struct ebvo_ctx
     size_t kf_img_bytes = 0;
     int kf_h = 0, kf_w = 0;    // shape of kf_imgL / kf_imgR: the refinement of the quads takes one shape for both frames
     size_t kf_cap = 0;
+    // the keyframe's inverse-depth state (ebvo_temporal_refine_depth): allocated by the first fusion; fresh = at the prior
+    double *kf_lambda = nullptr, *kf_info = nullptr;
+    int32_t *kf_nobs = nullptr;
+    uint8_t *kf_dflags = nullptr;
+    size_t kf_depth_cap = 0;
+    bool kf_depth_fresh = true;
+    bool use_depth = false;    // ebvo_temporal_use_depth
     bool undist_on = false;    // ebvo_stereo_set_undistort
     ebvo_undistort_params undist{};
     int lanes = 4;             // streams the kernels of submitted pairs are dealt to from four slots on (ebvo_stereo_submit)
@@ -726,10 +735,34 @@ struct AlignResult
 };
 // The alignment of n_kf >= 1 keyframe mates to the kept TOED edges d_E0 [n0] (and d_E1 [n1] with cameras = 2; n0 + n1 >= 1),
 // all device arrays; the workspace is s.align_ws.  Developer key 22 (Slot::tq_blocks) caps its grid-stride launches.
-// assoc_left / assoc_right (host, may be NULL): n_kf int32.  Waits for the result.
+// assoc_left / assoc_right (host, may be NULL): n_kf int32.  Waits for the result.  d_lambda (device, may be NULL): the
+// inverse-depth ratio per mate; the prepared Gamma of every live mate is divided by it (one more launch, depth_scale_enqueue).
 int align_run(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, int n_kf, const ebvo_edge *d_E0, int n0,
               const ebvo_edge *d_E1, int n1, int img_w, int img_h, const ebvo_stereo_calib *cal, const ebvo_align_params *ap,
-              const double *R0, const double *t0, AlignResult *res, int32_t *assoc_left, int32_t *assoc_right);
+              const double *R0, const double *t0, const double *d_lambda, AlignResult *res, int32_t *assoc_left, int32_t *assoc_right);
+// align_prepare_kernel alone: Gamma and T1 of every mate into d_gt [6][n_kf]
+void align_prepare_enqueue(const Slot &s, const ebvo_stereo_calib *cal, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, int n_kf, double *d_gt);
+// The alignment's grids and ONE association under (R, t), enqueued and not waited for; the same preconditions as align_run.
+// idx0 / idx1: the device arrays (in s.align_ws) that will hold the edge index or -1 per mate (idx1 NULL with cameras = 1).
+int align_associate_once(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, int n_kf, const ebvo_edge *d_E0, int n0,
+                         const ebvo_edge *d_E1, int n1, int img_w, int img_h, const ebvo_stereo_calib *cal, const ebvo_align_params *ap,
+                         const double *R, const double *t, const double *d_lambda, const int32_t **idx0, const int32_t **idx1);
+// depth_kernels.hip: Gamma of every live mate (finite, Gamma_z > 0) over its lambda, in place on the prepared planes
+void depth_scale_enqueue(const Slot &s, double *d_gt, int n_kf, const double *d_lambda);
+// what depth_finish_kernel leaves
+struct DepthRecord
+{
+    double rms_before, rms_after;
+    int32_t n_dead, n_updated, n_restored, n_terms[2], n_gated[2], pad;
+};
+// One update of n_kf >= 1 mates, enqueued and NOT waited for (the record's copy to `rec` included): d_idx0 / d_idx1 (device, may
+// be NULL = no association) index d_E0 [n0] / d_E1 [n1]; the in-state is NULL (the prior) or three device arrays, which may
+// be the out-state's.  The workspace is s.depth_ws.
+int depth_run(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, int n_kf, const ebvo_edge *d_E0, int n0,
+              const ebvo_edge *d_E1, int n1, const int32_t *d_idx0, const int32_t *d_idx1, int img_w, int img_h,
+              const ebvo_stereo_calib *cal, const ebvo_depth_params *dp, const double *R, const double *t, const double *d_lam_in,
+              const double *d_info_in, const int32_t *d_nobs_in, double *d_lam, double *d_info, int32_t *d_nobs, uint8_t *d_flags,
+              DepthRecord *rec);
 int misc_fp64_peak(ebvo_ctx *ctx, Slot &s, int iters, double *tf_muladd, double *tf_fma);
 
 #endif

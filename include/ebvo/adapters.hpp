@@ -985,6 +985,89 @@ class MotionTrackerHIP
         return state.aligned.status == 0;
     }
 
+    // The inverse-depth filter of the keyframe mates (this project's own; the contract is in ebvo_hip.h): every aligned frame
+    // refines lambda_i, the ratio of mate i's triangulated depth to the refined one, from the normal distances of its
+    // projections to the edges they were associated with.
+    struct Depth_Options
+    {
+        ebvo_depth_params p;
+        Depth_Options() { ebvo_depth_default_params(&p); }
+    };
+    struct Mate_Depths
+    {
+        std::vector<double> lambda, info;   // per keyframe mate; empty lambda on the way in: the prior
+        std::vector<int32_t> n_obs;
+        std::vector<uint8_t> flags;         // EBVO_DEPTH_* of the last update
+        ebvo_depth_refined refined{};       // the last update's record
+    };
+
+    // one update of the context's keyframe from the slot's waited pair under the pose (state.R, state.t); the association
+    // takes its radius, cell size and orientation threshold from align_opt
+    bool refine_Mate_Depths(int slot, const Align_Options &align_opt, const Depth_Options &opt, const Align_State &state,
+                            ebvo_depth_refined &refined)
+    {
+        refined = ebvo_depth_refined{};
+        last_status = ebvo_temporal_refine_depth(ctx_->get(), slot, &calib_, &align_opt.p, &opt.p, state.R.data(), state.t.data(), &refined);
+        return report(*ctx_, last_status, "ebvo_temporal_refine_depth");
+    }
+
+    // the same on host arrays, with the associations an alignment returned (state.assoc_left / assoc_right); depths is the
+    // incoming state (empty lambda: the prior) and the outgoing one
+    bool refine_Mate_Depths(const std::vector<ebvo_edge> &kf_left, const std::vector<ebvo_edge> &kf_right,
+                            const std::vector<ebvo_edge> &edges_left, const std::vector<ebvo_edge> &edges_right, int img_w, int img_h,
+                            const Depth_Options &opt, const Align_State &state, Mate_Depths &depths)
+    {
+        const size_t n = kf_left.size();
+        depths.refined = ebvo_depth_refined{};
+        const bool prior = depths.lambda.empty() && n > 0;
+        if (kf_right.size() != n || (!state.assoc_left.empty() && state.assoc_left.size() != n) ||
+            (!state.assoc_right.empty() && state.assoc_right.size() != n) ||
+            (!prior && (depths.lambda.size() != n || depths.info.size() != n || depths.n_obs.size() != n)))
+        {
+            last_status = EBVO_ERR_ARG;
+            return false;
+        }
+        depths.lambda.resize(n);
+        depths.info.resize(n);
+        depths.n_obs.resize(n);
+        depths.flags.assign(n, 0);
+        last_status = ebvo_depth_refine_edges(
+            ctx_->get(), kf_left.data(), kf_right.data(), (int)n, edges_left.data(), (int)edges_left.size(),
+            edges_right.empty() ? nullptr : edges_right.data(), (int)edges_right.size(), state.assoc_left.empty() ? nullptr : state.assoc_left.data(),
+            state.assoc_right.empty() ? nullptr : state.assoc_right.data(), img_w, img_h, &calib_, &opt.p, state.R.data(), state.t.data(),
+            prior ? nullptr : depths.lambda.data(), prior ? nullptr : depths.info.data(), prior ? nullptr : depths.n_obs.data(),
+            depths.lambda.data(), depths.info.data(), depths.n_obs.data(), depths.flags.data(), &depths.refined);
+        return report(*ctx_, last_status, "ebvo_depth_refine_edges");
+    }
+
+    // the keyframe's resident state (n_kf of the slot's ebvo_temporal_align_size)
+    bool mate_depths(int slot, Mate_Depths &depths)
+    {
+        int32_t n_kf = 0, n0 = 0, n1 = 0;
+        last_status = ebvo_temporal_align_size(ctx_->get(), slot, &n_kf, &n0, &n1);
+        if (!report(*ctx_, last_status, "ebvo_temporal_align_size"))
+            return false;
+        depths.lambda.assign((size_t)n_kf, 1.0);
+        depths.info.assign((size_t)n_kf, 0.0);
+        depths.n_obs.assign((size_t)n_kf, 0);
+        depths.flags.assign((size_t)n_kf, 0);
+        last_status = ebvo_temporal_depth_fetch(ctx_->get(), depths.lambda.data(), depths.info.data(), depths.n_obs.data(), depths.flags.data());
+        return report(*ctx_, last_status, "ebvo_temporal_depth_fetch");
+    }
+
+    bool reset_Mate_Depths()
+    {
+        last_status = ebvo_temporal_depth_reset(ctx_->get());
+        return report(*ctx_, last_status, "ebvo_temporal_depth_reset");
+    }
+
+    // while on, align_Relative_Pose(slot, ...) works on the refined points Gamma / lambda; default off
+    bool use_Mate_Depths(bool on)
+    {
+        last_status = ebvo_temporal_use_depth(ctx_->get(), on ? 1 : 0);
+        return report(*ctx_, last_status, "ebvo_temporal_use_depth");
+    }
+
     // n_runs calls of the reference's Solution_Constraints_Application (src/Pipeline.cpp:198-203 makes 20) in one device
     // call: one vector of five stages per run.  Empty on an error (last_status) and when the slot has too few quads.
     std::vector<std::vector<Quad_Pair_Evaluation_Metrics>> Solution_Constraints_Application(int slot, const Ransac_Options &opt,

@@ -43,7 +43,10 @@ extern "C" {
                               ebvo_pose_refine_params / _refined, ebvo_pose_refine_default_params,
                               ebvo_pose_refine_from_quads, ebvo_temporal_refine_pose; and with the additive edge
                               alignment: ebvo_align_params, ebvo_aligned_pose, ebvo_align_default_params,
-                              ebvo_pose_align_edges, ebvo_temporal_align_pose, ebvo_temporal_align_size */
+                              ebvo_pose_align_edges, ebvo_temporal_align_pose, ebvo_temporal_align_size; and with the
+                              additive inverse-depth filter: ebvo_depth_params / _refined, ebvo_depth_default_params,
+                              ebvo_depth_refine_edges, ebvo_temporal_refine_depth, ebvo_temporal_depth_fetch / _reset,
+                              ebvo_temporal_use_depth, ebvo_pose_align_edges_depth */
 
 typedef struct ebvo_ctx ebvo_ctx;
 
@@ -872,6 +875,106 @@ int ebvo_temporal_align_pose(ebvo_ctx *ctx, int slot, const ebvo_stereo_calib *c
 /* What that call would work on: the keyframe's mates (the length assoc_left / assoc_right need) and the slot's kept TOED
  * edges per image.  The same state rules. */
 int ebvo_temporal_align_size(ebvo_ctx *ctx, int slot, int32_t *n_kf, int32_t *n_left, int32_t *n_right);
+
+/* ---- refinement of the keyframe mates' depths from aligned frames: inverse-depth filter (this project's own stage) --- */
+/* Every frame aligned to the keyframe sees the keyframe's curve points again: its left camera at a temporal baseline, its
+ * right camera at the rig's.  Per keyframe mate one scalar is filtered: lambda, the ratio of the triangulated depth to the
+ * refined one, so that the refined point is Gamma / lambda.  This comment is the arithmetic contract; tests/oracle_depth.py
+ * restates it and the device matches it bit for bit.  fp64, no FMA, IEEE division and sqrt; mv3 / mtv3 / dot3 of
+ * csrc/ebvo_geom.h; sines and cosines through ebvo_sincos.  Additive: the ABI version stays 6.
+ * State per mate i: lambda_i (1.0 at the prior), info_i (1 / variance of lambda_i), n_obs_i (int32: frames fused),
+ *   flags_i (uint8, written by every update: EBVO_DEPTH_* of that update alone).
+ * Per mate: Gamma and T1 exactly as the alignment's align_prepare_kernel forms them (stereo_gamma_tangent under K_left^-1,
+ *   K_right^-1, R21, T21).  A mate is DEAD iff a component of Gamma is not finite or Gamma_z is not > 0: flag DEAD, counted in
+ *   n_dead and in nothing else; its state passes through unchanged (from the prior: lambda 1.0, info +0.0, n_obs 0).
+ * Prior of a live mate (used when no in-state is given): b = sqrt(dot3(T21, T21)), s = (sigma_disp_px Gamma_z) / (K_left[0] b),
+ *   info0 = 1.0 / (s s); lambda 1.0, n_obs 0.
+ * Refined point: Gs = (Gamma_x / lambda, Gamma_y / lambda, Gamma_z / lambda), three divisions.
+ * One camera's term at lambda under the pose (R, t), for the edge e = E_c[a] the association a names (0 <= a < n_c; any
+ *   other value, a NULL association array, or camera 1 with cameras = 1: no term): RG = mv3(R, Gs), X = RG + t; camera 0:
+ *   Y = X, K = K_left; camera 1: Y = mv3(R21, X) + T21, K = the TRUE K_right (as the alignment).  p = mv3(K, Y), pi = (p0 / p2,
+ *   p1 / p2), ip = 1.0 / p2, jx_k = ip (K[k] - pi_x K[6 + k]), jy_k = ip (K[3 + k] - pi_y K[6 + k]), k < 3; camera 1:
+ *   jx <- mtv3(R21, jx), jy <- mtv3(R21, jy).  (sn, cs) = ebvo_sincos(e.theta), n = (sn, -cs).
+ *   r = n0 (pi_x - e.x) + n1 (pi_y - e.y); m_k = n0 jx_k + n1 jy_k; j = -(dot3(m, RG) / lambda): d r / d lambda, because
+ *   d Gs / d lambda = -Gs / lambda.
+ * One update of a live mate with the incoming (lambda_in, info_in, n_obs_in):
+ *   1. both terms at lambda_in.  A term is LIVE iff it exists and img_margin < pi_x < w - img_margin, img_margin < pi_y <
+ *      h - img_margin and Y_z > 0 (per camera; NaN: not live).  A term that is not live is no term.
+ *   2. gate: a live term SURVIVES iff |r| <= gate_px and |r| < +inf; otherwise it is dropped for the whole update, counted in
+ *      n_gated[c], flag GATED_LEFT / GATED_RIGHT.  The set of surviving terms is fixed here.  n_terms[c] counts them.
+ *   3. lambda = lambda_in; iv = 1.0 / (sigma_normal_px sigma_normal_px).  For it = 0 .. iterations: the surviving terms at
+ *      lambda; rho = |r|, w = 1.0 if rho <= huber_px else huber_px / rho (the refit's Huber weight); Sh = +0.0, Sg = +0.0; camera 0
+ *      then camera 1, surviving only: Sh = Sh + w (j j), Sg = Sg + w (j r); h = info_in + Sh iv; if it == iterations: stop;
+ *      g = info_in (lambda - lambda_in) + Sg iv; lambda = lambda - g / h.  (iterations + 1 evaluations; the last forms h and
+ *      the outgoing residuals only.  iterations = 0 updates info alone.)
+ *   4. accept iff lambda is finite, lambda_min <= lambda <= lambda_max, at least one term survived and h is finite:
+ *      lambda_i = lambda, info_i = min(h, info_max) (h if it is the smaller, else info_max), n_obs_i = n_obs_in + 1, flag
+ *      UPDATED, n_updated.  Otherwise the incoming state is written back, flag RESTORED, n_restored.
+ * rms_before = sqrt(Sb / (n_terms[0] + n_terms[1])), Sb the sum over the mates of +0.0 + ((r0 r0 or +0.0) + (r1 r1 or +0.0)),
+ *   the surviving terms' residuals at lambda_in (+0.0 for a dead mate), through the alignment's tile trees: tiles of 1024
+ *   mates, a 64-lane halving tree, the 16 group sums by the same tree, tiles added in ascending order from +0.0.  rms_after:
+ *   the same with the residuals at the outgoing lambda (an accepted mate: the last evaluation; a restored one: those at
+ *   lambda_in).  Both 0.0 when no term survived.  No launch geometry enters; the counts are integers.
+ * block_threads is the alignment's developer switch. */
+#define EBVO_DEPTH_DEAD 1u
+#define EBVO_DEPTH_UPDATED 2u
+#define EBVO_DEPTH_RESTORED 4u
+#define EBVO_DEPTH_GATED_LEFT 8u
+#define EBVO_DEPTH_GATED_RIGHT 16u
+typedef struct ebvo_depth_params
+{
+    double sigma_disp_px;            /* 0.25 px: the disparity noise the prior stands for */
+    double sigma_normal_px;          /* 0.5 px: noise of one normal residual */
+    double huber_px, gate_px;        /* 1.0 (+inf = least squares), 3.0 (+inf = only non-finite residuals are dropped) */
+    int32_t iterations, cameras;     /* 3; 2 (1 = left image only) */
+    double lambda_min, lambda_max;   /* 0.25, 4.0 */
+    double info_max;                 /* 1e6: sigma(lambda) never below 1e-3 (+inf = no clip) */
+    double img_margin;               /* 10, as the alignment */
+    int32_t block_threads, reserved; /* 0 (= 1024), 256, 512 or 1024; 0 */
+} ebvo_depth_params;
+typedef struct ebvo_depth_refined
+{
+    int32_t n_kf, n_dead, n_updated, n_restored;
+    int32_t n_terms[2], n_gated[2];
+    double rms_before, rms_after;
+} ebvo_depth_refined;
+void ebvo_depth_default_params(ebvo_depth_params *p);
+/* One update on host arrays.  assoc_left / assoc_right: n_kf int32 each as ebvo_pose_align_edges returns them (assoc_right
+ * and cf_edges_right may be NULL with cameras = 1, either association array may be NULL: no term in that camera).
+ * lambda_in / info_in / n_obs_in: the incoming state, all three or none (none: the prior).  lambda / info / n_obs / flags: the
+ * outgoing state, all four required when n_kf > 0; they may be the incoming arrays.  Accepted: sigma_disp_px, sigma_normal_px
+ * finite and > 0, huber_px > 0 and gate_px > 0 (+inf allowed), 0 <= iterations <= 16, 0 < lambda_min <= lambda_max finite,
+ * info_max > 0 (+inf allowed), img_margin >= 0, cameras 1 or 2, block_threads in its set, reserved 0, no NaN, R and t finite,
+ * img_w, img_h >= 1; anything else: EBVO_ERR_ARG, nothing touched.  n_kf = 0: nothing launched, a zero record.  Runs on slot
+ * 0's stream under the state rules of ebvo_pose_align_edges; the inputs are copied before the call returns. */
+int ebvo_depth_refine_edges(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *kf_right, int n_kf, const ebvo_edge *cf_edges_left,
+                            int n0, const ebvo_edge *cf_edges_right, int n1, const int32_t *assoc_left, const int32_t *assoc_right,
+                            int img_w, int img_h, const ebvo_stereo_calib *cal, const ebvo_depth_params *params, const double R[9],
+                            const double t[3], const double *lambda_in, const double *info_in, const int32_t *n_obs_in, double *lambda,
+                            double *info, int32_t *n_obs, uint8_t *flags, ebvo_depth_refined *out);
+/* Resident: the keyframe's mates are associated under (R, t) with the slot's kept TOED edge lists by the alignment's own grid
+ * and association (radius, cell_size, orient_thr_deg, img_margin of align_params; its other fields are checked and not used;
+ * cameras is depth_params'), on Gamma / lambda with the keyframe's CURRENT lambda whether ebvo_temporal_use_depth is on or
+ * not (the update linearises there); then one update of the keyframe's resident state.  Everything is enqueued up front.  The
+ * state rules of ebvo_temporal_align_pose; the slot's pair, quads, prior, ground-truth state and the rand() stream are
+ * unchanged. */
+int ebvo_temporal_refine_depth(ebvo_ctx *ctx, int slot, const ebvo_stereo_calib *cal, const ebvo_align_params *align_params,
+                               const ebvo_depth_params *depth_params, const double R[9], const double t[3], ebvo_depth_refined *out);
+/* The keyframe's state: n_kf values each (any pointer may be NULL).  A keyframe that has fused no frame is AT THE PRIOR and
+ * reads lambda 1.0, info +0.0 (info0 is formed by the first update, from its parameters), n_obs 0, flags 0.
+ * EBVO_ERR_STATE without a keyframe. */
+int ebvo_temporal_depth_fetch(ebvo_ctx *ctx, double *lambda, double *info, int32_t *n_obs, uint8_t *flags);
+/* Back to the prior.  ebvo_temporal_set_keyframe does the same, and no other call does. */
+int ebvo_temporal_depth_reset(ebvo_ctx *ctx);
+/* on != 0: ebvo_temporal_align_pose works on Gamma / lambda of the live mates (one small launch over the prepared planes; a
+ * keyframe at the prior is lambda = 1 and the launch is left out).  Default off: the existing calls enqueue exactly what they
+ * enqueue without this stage.  The pose search, the refit and the prior's projection never read lambda. */
+int ebvo_temporal_use_depth(ebvo_ctx *ctx, int on);
+/* ebvo_pose_align_edges on Gamma / lambda: lambda [n_kf] (NULL: the bits of ebvo_pose_align_edges). */
+int ebvo_pose_align_edges_depth(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *kf_right, const double *lambda, int n_kf,
+                                const ebvo_edge *cf_edges_left, int n0, const ebvo_edge *cf_edges_right, int n1, int img_w, int img_h,
+                                const ebvo_stereo_calib *cal, const ebvo_align_params *params, const double R0[9], const double t0[3],
+                                ebvo_aligned_pose *out, int32_t *assoc_left, int32_t *assoc_right);
 
 /* ---- ground-truth evaluation from a disparity map (the reference's has_gt() == true branch, is_left = true) ------- */
 /* Find_Stereo_GT_Locations (src/Stereo_Matches.cpp:133-200), get_Stereo_Edge_GT_Pairs (:202-268) and
