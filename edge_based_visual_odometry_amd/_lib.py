@@ -62,6 +62,7 @@ ABI_SYMBOLS = (
     "ebvo_align_default_params", "ebvo_pose_align_edges", "ebvo_temporal_align_pose", "ebvo_temporal_align_size",
     "ebvo_depth_default_params", "ebvo_depth_refine_edges", "ebvo_temporal_refine_depth", "ebvo_temporal_depth_fetch",
     "ebvo_temporal_depth_reset", "ebvo_temporal_use_depth", "ebvo_pose_align_edges_depth",
+    "ebvo_depth_carry_default_params", "ebvo_depth_carry", "ebvo_temporal_promote_keyframe", "ebvo_temporal_depth_source",
 )
 
 
@@ -164,6 +165,17 @@ class DepthParams(C.Structure):
     _fields_ = [("sigma_disp_px", C.c_double), ("sigma_normal_px", C.c_double), ("huber_px", C.c_double), ("gate_px", C.c_double),
                 ("iterations", C.c_int32), ("cameras", C.c_int32), ("lambda_min", C.c_double), ("lambda_max", C.c_double),
                 ("info_max", C.c_double), ("img_margin", C.c_double), ("block_threads", C.c_int32), ("reserved", C.c_int32)]
+
+
+class DepthCarryParams(C.Structure):
+    _fields_ = [("sigma_disp_px", C.c_double), ("radius", C.c_double), ("cell_size", C.c_int32), ("min_obs", C.c_int32),
+                ("orient_thr_deg", C.c_double), ("carry", C.c_double), ("gate_sigmas", C.c_double), ("lambda_min", C.c_double),
+                ("lambda_max", C.c_double), ("info_max", C.c_double), ("img_margin", C.c_double), ("reserved", C.c_int32),
+                ("pad", C.c_int32)]
+
+
+class DepthCarried(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("n_old", "n_sources", "n_live", "n_new", "n_dead", "n_assoc", "n_carried", "n_gated")]
 
 
 class DepthRefined(C.Structure):
@@ -420,6 +432,16 @@ def load_library() -> C.CDLL:
     lib.ebvo_pose_align_edges_depth.restype = i32
     lib.ebvo_pose_align_edges_depth.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, C.POINTER(StereoCalib),
                                                 C.POINTER(AlignParams), vp, vp, C.POINTER(AlignedPose), vp, vp]
+    lib.ebvo_depth_carry_default_params.restype = None
+    lib.ebvo_depth_carry_default_params.argtypes = [C.POINTER(DepthCarryParams)]
+    lib.ebvo_depth_carry.restype = i32
+    lib.ebvo_depth_carry.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(StereoCalib),
+                                     C.POINTER(DepthCarryParams), vp, vp, vp, vp, vp, vp, vp, C.POINTER(DepthCarried)]
+    lib.ebvo_temporal_promote_keyframe.restype = i32
+    lib.ebvo_temporal_promote_keyframe.argtypes = [vp, i32, C.POINTER(StereoCalib), C.POINTER(DepthCarryParams), vp, vp,
+                                                   C.POINTER(DepthCarried)]
+    lib.ebvo_temporal_depth_source.restype = i32
+    lib.ebvo_temporal_depth_source.argtypes = [vp, vp]
     lib.ebvo_gt_default_params.restype = None
     lib.ebvo_gt_default_params.argtypes = [C.POINTER(GtParams)]
     lib.ebvo_stereo_set_gt.argtypes = [vp, i32, vp, i32, i32, ssz, C.POINTER(StereoCalib), C.POINTER(GtParams)]

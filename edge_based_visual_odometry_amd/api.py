@@ -1047,6 +1047,67 @@ class Context:
         """temporal_align_pose works on Gamma / lambda while on (ebvo_temporal_use_depth); default off."""
         self._check(self.lib.ebvo_temporal_use_depth(self._ctx, 1 if on else 0), "ebvo_temporal_use_depth")
 
+    # -- handover of the refined depths to the next keyframe on promotion (the contract is in ebvo_hip.h) ---------------------
+    def depth_carry_params(self, **kw) -> _lib.DepthCarryParams:
+        """ebvo_depth_carry_params: the defaults of ebvo_depth_carry_default_params with `kw` applied."""
+        p = _lib.DepthCarryParams()
+        self.lib.ebvo_depth_carry_default_params(C.byref(p))
+        fields = {name for name, _ in p._fields_}
+        for k, v in kw.items():
+            if k not in fields:
+                raise TypeError(f"depth carry: unknown parameter {k!r}")
+            setattr(p, k, v)
+        return p
+
+    @staticmethod
+    def _carried_dict(r) -> dict:
+        return {k: int(getattr(r, k)) for k, _ in r._fields_}
+
+    def depth_carry(self, kf_left, kf_right, new_left, new_right, img_w: int, img_h: int, calib, R, t, state=None, **params) -> dict:
+        """The old keyframe's depths carried to the new mates on host arrays (ebvo_depth_carry).  state: None (nothing to carry:
+        every live new mate at its prior) or the old mates' (lambda, info, n_obs).  (R, t): old keyframe -> new frame.  params:
+        the fields of ebvo_depth_carry_params.  Returns the fields of ebvo_depth_carried and lambda_, info, n_obs, flags,
+        src_index of the new mates."""
+        oL, oR, nL, nR = _edges(kf_left), _edges(kf_right), _edges(new_left), _edges(new_right)
+        no, nn = len(oL), len(nL)
+        if len(oR) != no or len(nR) != nn:
+            raise ValueError("left and right mates differ in length")
+        p, cal, r = self.depth_carry_params(**params), self._calib(calib), _lib.DepthCarried()
+        R, t = self._start_pose(R, t)
+        sin = (None, None, None)
+        if state is not None:
+            lam_in = np.ascontiguousarray(state[0], dtype=np.float64)
+            info_in = np.ascontiguousarray(state[1], dtype=np.float64)
+            nobs_in = np.ascontiguousarray(state[2], dtype=np.int32)
+            if not (lam_in.shape == info_in.shape == nobs_in.shape == (no,)):
+                raise ValueError("the state needs one value per old keyframe mate")
+            sin = (ptr(lam_in), ptr(info_in), ptr(nobs_in))
+        lam, info, nobs = np.ones(nn), np.zeros(nn), np.zeros(nn, dtype=np.int32)
+        flags, src = np.zeros(nn, dtype=np.uint8), np.full(nn, -1, dtype=np.int32)
+        self._check(self.lib.ebvo_depth_carry(self._ctx, ptr(oL), ptr(oR), no, *sin, ptr(nL), ptr(nR), nn, int(img_w), int(img_h),
+                                              C.byref(cal), C.byref(p), ptr(R), ptr(t), ptr(lam), ptr(info), ptr(nobs), ptr(flags), ptr(src),
+                                              C.byref(r)), "ebvo_depth_carry")
+        return dict(self._carried_dict(r), lambda_=lam, info=info, n_obs=nobs, flags=flags, src_index=src)
+
+    def temporal_promote_keyframe(self, calib, R, t, slot: int = 0, **params) -> dict:
+        """The slot's finalised pair becomes the keyframe and inherits the old keyframe's refined depths through (R, t), old
+        keyframe -> this frame (ebvo_temporal_promote_keyframe).  Returns the fields of ebvo_depth_carried."""
+        p, cal, r = self.depth_carry_params(**params), self._calib(calib), _lib.DepthCarried()
+        R, t = self._start_pose(R, t)
+        self._check(self.lib.ebvo_temporal_promote_keyframe(self._ctx, slot, C.byref(cal), C.byref(p), ptr(R), ptr(t), C.byref(r)),
+                    "ebvo_temporal_promote_keyframe")
+        return self._carried_dict(r)
+
+    def temporal_depth_source(self, slot: int = 0) -> np.ndarray:
+        """src_index of the last promotion: per keyframe mate the old keyframe's mate it took its depth from, or -1
+        (ebvo_temporal_depth_source)."""
+        n_kf, n0, n1 = C.c_int32(), C.c_int32(), C.c_int32()
+        self._check(self.lib.ebvo_temporal_align_size(self._ctx, slot, C.byref(n_kf), C.byref(n0), C.byref(n1)),
+                    "ebvo_temporal_align_size")
+        src = np.full(n_kf.value, -1, dtype=np.int32)
+        self._check(self.lib.ebvo_temporal_depth_source(self._ctx, ptr(src)), "ebvo_temporal_depth_source")
+        return src
+
     # -- ground-truth evaluation from a disparity map (Find_Stereo_GT_Locations, get_Stereo_Edge_GT_Pairs,
     # -- Evaluate_Stereo_Edge_Correspondences) ---------------------------------------------------------------
     def gt_params(self, **kw) -> _lib.GtParams:

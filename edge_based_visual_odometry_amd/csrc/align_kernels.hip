@@ -765,15 +765,15 @@ int align_enqueue_front(ebvo_ctx *ctx, Slot &s, const AlignSetup &S, const ebvo_
     for (int c = 0; c < S.A.cameras; ++c)
     {
         const EdgeGrid &g = S.g[c];
-        // cnt and fill, and start too: a camera without edges still has an (all-zero) start array
-        EBVO_HIP(ctx, hipMemsetAsync(g.cnt, 0, sizeof(int32_t) * (3 * (size_t)n_cells + 1), st));
         if (S.ne[c] <= 0)
+        {
+            // a camera without edges still has an (all-zero) start array
+            EBVO_HIP(ctx, hipMemsetAsync(g.cnt, 0, sizeof(int32_t) * (3 * (size_t)n_cells + 1), st));
             continue;
-        const int64_t eb = ((int64_t)S.ne[c] + 255) / 256;
-        const unsigned nb = chain_grid_cap(s, (unsigned)(eb > 2048 ? 2048 : eb));
-        hipLaunchKernelGGL(align_cells_kernel, dim3(nb), dim3(256), 0, st, g.E, S.ne[c], S.A.cell, S.A.gw, S.A.gh, g.cell_of, g.cnt);
-        hipLaunchKernelGGL(align_cell_scan_kernel, dim3(1), dim3(256), 0, st, g.cnt, n_cells, g.start);
-        hipLaunchKernelGGL(align_cell_scatter_kernel, dim3(nb), dim3(256), 0, st, g.cell_of, S.ne[c], g.start, g.fill, g.list);
+        }
+        const int32_t *start, *list; // = g.start, g.list: the grid's arrays are carved in align_grid_enqueue's order
+        if (int rc = align_grid_enqueue(ctx, s, g.E, S.ne[c], S.A.cell, S.A.gw, S.A.gh, g.cell_of, &start, &list))
+            return rc;
     }
     return EBVO_OK;
 }
@@ -785,6 +785,24 @@ void align_prepare_enqueue(const Slot &s, const ebvo_stereo_calib *cal, const eb
     const int64_t pb = ((int64_t)n_kf + 255) / 256;
     hipLaunchKernelGGL(align_prepare_kernel, dim3(chain_grid_cap(s, (unsigned)(pb > 2048 ? 2048 : pb))), dim3(256), 0, s.stream, C, d_kfL, d_kfR,
                        n_kf, d_gt);
+}
+
+// The three grid kernels over any edge list: the alignment's own two, and carry_kernels.hip's list of projected old mates.
+// cnt and fill are zeroed, and start too.
+int align_grid_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_E, int n, int cell, int gw, int gh, int32_t *ws, const int32_t **start,
+                       const int32_t **list)
+{
+    const int n_cells = gw * gh;
+    int32_t *cell_of = ws, *cnt = cell_of + n, *fill = cnt + n_cells, *st_ = fill + n_cells, *lst = st_ + n_cells + 1;
+    EBVO_HIP(ctx, hipMemsetAsync(cnt, 0, sizeof(int32_t) * (3 * (size_t)n_cells + 1), s.stream));
+    const int64_t eb = ((int64_t)n + 255) / 256;
+    const unsigned nb = chain_grid_cap(s, (unsigned)(eb > 2048 ? 2048 : eb));
+    hipLaunchKernelGGL(align_cells_kernel, dim3(nb), dim3(256), 0, s.stream, d_E, n, cell, gw, gh, cell_of, cnt);
+    hipLaunchKernelGGL(align_cell_scan_kernel, dim3(1), dim3(256), 0, s.stream, cnt, n_cells, st_);
+    hipLaunchKernelGGL(align_cell_scatter_kernel, dim3(nb), dim3(256), 0, s.stream, cell_of, n, st_, fill, lst);
+    *start = st_;
+    *list = lst;
+    return EBVO_OK;
 }
 
 // One association under (R, t), enqueued and not waited for: the edge index (or -1) per mate and camera stays in the workspace.

@@ -175,7 +175,7 @@ static void slot_destroy(Slot *s)
                        &s->keep,         &s->patches_raw,  &s->patches_norm,   &s->patches_flag,   &s->patches_norm_r,
                        &s->patches_flag_r, &s->pair_left,  &s->sincos,         &s->scratch_b,      &s->scratch_c,
                        &s->scratch_d,    &s->fetch_pack,   &s->pose_in,        &s->pose_geom,      &s->pose_order,
-                       &s->pose_draw,    &s->pose_hyp,       &s->pose_sel,       &s->pose_casc,       &s->pose_refit,     &s->align_up,       &s->align_ws,       &s->depth_up,       &s->depth_ws,       &s->gt_disp,        &s->gt_geom,        &s->gt_flags,
+                       &s->pose_draw,    &s->pose_hyp,       &s->pose_sel,       &s->pose_casc,       &s->pose_refit,     &s->align_up,       &s->align_ws,       &s->depth_up,       &s->depth_ws,       &s->carry_up,       &s->carry_ws,       &s->gt_disp,        &s->gt_geom,        &s->gt_flags,
                        &s->gt_boxes,     &s->gt_pool_i32,  &s->gt_pool_idx,    &s->gt_rows,        &s->gt_tot,
                        &s->gt_up,        &s->tgt_geom,     &s->tgt_i32,        &s->tgt_idx,        &s->tgt_u8,
                        &s->tgt_rows,     &s->tgt_flags,    &s->tgt_tot,        &s->tgt_up,
@@ -401,6 +401,9 @@ extern "C" void ebvo_ctx_destroy(ebvo_ctx *ctx)
     (void)hipFree(ctx->kf_imgL);
     (void)hipFree(ctx->kf_imgR);
     (void)hipFree(ctx->kf_Rf);
+    for (void *p : {(void *)ctx->kf_lambda_alt, (void *)ctx->kf_info_alt, (void *)ctx->kf_nobs_alt, (void *)ctx->kf_dflags_alt,
+                    (void *)ctx->kf_src, (void *)ctx->kf_src_alt})
+        (void)hipFree(p);
     (void)hipFree(ctx->kf_lambda);
     (void)hipFree(ctx->kf_info);
     (void)hipFree(ctx->kf_nobs);
@@ -3240,12 +3243,9 @@ static int mate_descriptors(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_L, const 
     return EBVO_OK;
 }
 
-extern "C" int ebvo_temporal_set_keyframe(ebvo_ctx *ctx, int slot)
+// what a slot needs to become the keyframe (ebvo_temporal_set_keyframe, ebvo_temporal_promote_keyframe)
+static int keyframe_slot_state(ebvo_ctx *ctx, const Slot &s)
 {
-    Slot *sp;
-    if (get_slot(ctx, slot, &sp))
-        return EBVO_ERR_ARG;
-    Slot &s = *sp;
     if (!s.have_final || s.in_flight || s.tq_in_flight)
         return EBVO_ERR_STATE;
     // a match in flight in ANY slot reads the stored keyframe (ctx->kf_*) on its own stream, and its wait runs the chain
@@ -3256,6 +3256,12 @@ extern "C" int ebvo_temporal_set_keyframe(ebvo_ctx *ctx, int slot)
             ctx->last_error = "a temporal match is in flight in another slot (ebvo_temporal_match_wait first): the keyframe stays";
             return EBVO_ERR_STATE;
         }
+    return EBVO_OK;
+}
+
+// the slot's final mates, patches, descriptors and images into the keyframe store; the depth state back to the prior.  Waits.
+static int keyframe_install(ebvo_ctx *ctx, Slot &s)
+{
     EBVO_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc_f = drain_fetch(ctx, s))
         return rc_f;
@@ -3287,6 +3293,7 @@ extern "C" int ebvo_temporal_set_keyframe(ebvo_ctx *ctx, int slot)
     }
     ctx->kf_n = (int)n;
     ctx->kf_depth_fresh = true; // the new keyframe's mates are at the prior
+    ctx->kf_promoted = false;
     ++ctx->kf_gen; // quads matched against the previous keyframe no longer belong to ctx->kf_L / kf_R
     {
         // the keyframe's undistorted images stay with it: the photometric refinement of the quads samples them
@@ -3334,6 +3341,16 @@ extern "C" int ebvo_temporal_set_keyframe(ebvo_ctx *ctx, int slot)
         return rc;
     EBVO_HIP(ctx, hipStreamSynchronize(s.stream));
     return EBVO_OK;
+}
+
+extern "C" int ebvo_temporal_set_keyframe(ebvo_ctx *ctx, int slot)
+{
+    Slot *sp;
+    if (get_slot(ctx, slot, &sp))
+        return EBVO_ERR_ARG;
+    if (int rc = keyframe_slot_state(ctx, *sp))
+        return rc;
+    return keyframe_install(ctx, *sp);
 }
 
 // developer key 22 holds for the launches of temporal_stage0_enqueue and temporal_chain only: the helpers they share with
@@ -4814,6 +4831,243 @@ extern "C" int ebvo_temporal_use_depth(ebvo_ctx *ctx, int on)
     if (!ctx)
         return EBVO_ERR_ARG;
     ctx->use_depth = on != 0;
+    return EBVO_OK;
+}
+
+// ---- handover of the refined depths to the next keyframe on promotion (carry_kernels.hip) --------------------------------
+extern "C" void ebvo_depth_carry_default_params(ebvo_depth_carry_params *p)
+{
+    if (!p)
+        return;
+    p->sigma_disp_px = 0.25;
+    p->radius = 1.5;
+    p->cell_size = 4;
+    p->min_obs = 1;
+    p->orient_thr_deg = 10.0;
+    p->carry = 0.5;
+    p->gate_sigmas = 3.0;
+    p->lambda_min = 0.25;
+    p->lambda_max = 4.0;
+    p->info_max = 1e6;
+    p->img_margin = 10.0;
+    p->reserved = 0;
+    p->pad = 0;
+}
+
+static bool carry_args_ok(const ebvo_stereo_calib *cal, const ebvo_depth_carry_params *cp, const double *R, const double *t,
+                          const ebvo_depth_carried *out, int img_w, int img_h)
+{
+    if (!cal || !cp || !R || !t || !out || img_w < 1 || img_h < 1)
+        return false;
+    for (int i = 0; i < 9; ++i)
+        if (!std::isfinite(R[i]))
+            return false;
+    for (int i = 0; i < 3; ++i)
+        if (!std::isfinite(t[i]))
+            return false;
+    // every comparison is false for a NaN
+    if (!(std::isfinite(cp->sigma_disp_px) && cp->sigma_disp_px > 0 && std::isfinite(cp->radius) && cp->radius > 0 && cp->cell_size >= 1 &&
+          cp->min_obs >= 0 && cp->orient_thr_deg >= 0 && cp->carry > 0 && cp->carry <= 1 && cp->gate_sigmas > 0 &&
+          std::isfinite(cp->lambda_max) && cp->lambda_min > 0 && cp->lambda_min <= cp->lambda_max && cp->info_max > 0 &&
+          cp->img_margin >= 0 && cp->reserved == 0 && cp->pad == 0))
+        return false;
+    if (!(ceil(cp->radius / cp->cell_size) <= 8.0))
+        return false;
+    const int64_t gw = ((int64_t)img_w + cp->cell_size - 1) / cp->cell_size, gh = ((int64_t)img_h + cp->cell_size - 1) / cp->cell_size;
+    return gw * gh <= (1 << 26);
+}
+
+static void carry_publish(const int32_t *counts, int n_old, int n_new, ebvo_depth_carried *out)
+{
+    out->n_old = n_old;
+    out->n_sources = counts[0];
+    out->n_live = counts[1];
+    out->n_new = n_new;
+    out->n_dead = counts[2];
+    out->n_assoc = counts[3];
+    out->n_carried = counts[4];
+    out->n_gated = counts[5];
+}
+
+extern "C" int ebvo_depth_carry(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *kf_right, int n_old, const double *lambda_in,
+                                const double *info_in, const int32_t *n_obs_in, const ebvo_edge *new_left, const ebvo_edge *new_right,
+                                int n_new, int img_w, int img_h, const ebvo_stereo_calib *cal, const ebvo_depth_carry_params *params,
+                                const double R[9], const double t[3], double *lambda, double *info, int32_t *n_obs, uint8_t *flags,
+                                int32_t *src_index, ebvo_depth_carried *out)
+{
+    if (!ctx || !carry_args_ok(cal, params, R, t, out, img_w, img_h) || n_old < 0 || n_new < 0 || (n_old > 0 && (!kf_left || !kf_right)) ||
+        (n_new > 0 && (!new_left || !new_right || !lambda || !info || !n_obs || !flags || !src_index)))
+        return EBVO_ERR_ARG;
+    const int have_in = (lambda_in ? 1 : 0) + (info_in ? 1 : 0) + (n_obs_in ? 1 : 0);
+    if (have_in != 0 && have_in != 3)
+        return EBVO_ERR_ARG;
+    int rc;
+    Slot *sp;
+    if ((rc = gt_host_slot(ctx, &sp)))
+        return rc;
+    Slot &s = *sp;
+    int32_t counts[CARRY_COUNTS] = {0, 0, 0, 0, 0, 0};
+    if (n_new == 0)
+    {
+        carry_publish(counts, n_old, n_new, out);
+        return EBVO_OK;
+    }
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    const bool assoc = have_in && n_old > 0;
+    const size_t no = assoc ? (size_t)n_old : 0, nn = (size_t)n_new, eb = sizeof(ebvo_edge);
+    auto up64 = [](size_t v) { return (v + 63) & ~(size_t)63; };
+    // old mates and their state, new mates, the outgoing state
+    const size_t o_oR = up64(eb * no), o_li = o_oR + up64(eb * no), o_ii = o_li + up64(8 * no), o_ni = o_ii + up64(8 * no),
+                 o_nL = o_ni + up64(4 * no), o_nR = o_nL + up64(eb * nn), o_lam = o_nR + up64(eb * nn), o_info = o_lam + up64(8 * nn),
+                 o_nobs = o_info + up64(8 * nn), o_src = o_nobs + up64(4 * nn), o_fl = o_src + up64(4 * nn), total = o_fl + up64(nn);
+    if ((rc = gt_grow(ctx, s, s.carry_up, total)))
+        return rc;
+    char *base = (char *)s.carry_up.p;
+    ebvo_edge *oL = (ebvo_edge *)base, *oR = (ebvo_edge *)(base + o_oR), *nL = (ebvo_edge *)(base + o_nL), *nR = (ebvo_edge *)(base + o_nR);
+    double *d_li = (double *)(base + o_li), *d_ii = (double *)(base + o_ii), *d_lam = (double *)(base + o_lam), *d_info = (double *)(base + o_info);
+    int32_t *d_ni = (int32_t *)(base + o_ni), *d_nobs = (int32_t *)(base + o_nobs), *d_src = (int32_t *)(base + o_src);
+    uint8_t *d_fl = (uint8_t *)(base + o_fl);
+    hipStream_t st = s.stream;
+    auto enqueue = [&]() -> int {
+        if (assoc)
+        {
+            EBVO_HIP(ctx, hipMemcpyAsync(oL, kf_left, eb * no, hipMemcpyHostToDevice, st));
+            EBVO_HIP(ctx, hipMemcpyAsync(oR, kf_right, eb * no, hipMemcpyHostToDevice, st));
+            EBVO_HIP(ctx, hipMemcpyAsync(d_li, lambda_in, 8 * no, hipMemcpyHostToDevice, st));
+            EBVO_HIP(ctx, hipMemcpyAsync(d_ii, info_in, 8 * no, hipMemcpyHostToDevice, st));
+            EBVO_HIP(ctx, hipMemcpyAsync(d_ni, n_obs_in, 4 * no, hipMemcpyHostToDevice, st));
+        }
+        EBVO_HIP(ctx, hipMemcpyAsync(nL, new_left, eb * nn, hipMemcpyHostToDevice, st));
+        EBVO_HIP(ctx, hipMemcpyAsync(nR, new_right, eb * nn, hipMemcpyHostToDevice, st));
+        const TemporalGridScope grid_scope(ctx, s);
+        if (int rc2 = carry_run(ctx, s, oL, oR, n_old, assoc ? d_li : nullptr, assoc ? d_ii : nullptr, assoc ? d_ni : nullptr, nL, nR, n_new, img_w,
+                                img_h, cal, params, R, t, d_lam, d_info, d_nobs, d_fl, d_src, counts))
+            return rc2;
+        EBVO_HIP(ctx, hipMemcpyAsync(lambda, d_lam, 8 * nn, hipMemcpyDeviceToHost, st));
+        EBVO_HIP(ctx, hipMemcpyAsync(info, d_info, 8 * nn, hipMemcpyDeviceToHost, st));
+        EBVO_HIP(ctx, hipMemcpyAsync(n_obs, d_nobs, 4 * nn, hipMemcpyDeviceToHost, st));
+        EBVO_HIP(ctx, hipMemcpyAsync(flags, d_fl, nn, hipMemcpyDeviceToHost, st));
+        EBVO_HIP(ctx, hipMemcpyAsync(src_index, d_src, 4 * nn, hipMemcpyDeviceToHost, st));
+        return EBVO_OK;
+    };
+    rc = enqueue();
+    const hipError_t e = hipStreamSynchronize(st); // the copies read and write the caller's arrays: none of them outlives the call
+    if (rc)
+        return rc;
+    EBVO_HIP(ctx, e);
+    carry_publish(counts, n_old, n_new, out);
+    return EBVO_OK;
+}
+
+// the second set of state arrays holds n values (the set the next promotion writes)
+static int carry_alt_ensure(ebvo_ctx *ctx, size_t n)
+{
+    if (n <= ctx->kf_depth_alt_cap && n <= ctx->kf_src_alt_cap && ctx->kf_lambda_alt && ctx->kf_src_alt)
+        return EBVO_OK;
+    EBVO_HIP(ctx, hipDeviceSynchronize());
+    for (void *p : {(void *)ctx->kf_lambda_alt, (void *)ctx->kf_info_alt, (void *)ctx->kf_nobs_alt, (void *)ctx->kf_dflags_alt,
+                    (void *)ctx->kf_src_alt})
+        (void)hipFree(p);
+    ctx->kf_lambda_alt = ctx->kf_info_alt = nullptr;
+    ctx->kf_nobs_alt = ctx->kf_src_alt = nullptr;
+    ctx->kf_dflags_alt = nullptr;
+    ctx->kf_depth_alt_cap = ctx->kf_src_alt_cap = 0;
+    const size_t cap = n + n / 4 + 64;
+    if (hipMalloc(&ctx->kf_lambda_alt, 8 * cap) != hipSuccess || hipMalloc(&ctx->kf_info_alt, 8 * cap) != hipSuccess ||
+        hipMalloc(&ctx->kf_nobs_alt, 4 * cap) != hipSuccess || hipMalloc(&ctx->kf_dflags_alt, cap) != hipSuccess ||
+        hipMalloc(&ctx->kf_src_alt, 4 * cap) != hipSuccess)
+    {
+        (void)hipGetLastError();
+        ctx->last_error = "hipMalloc failed (carried depth state)";
+        return EBVO_ERR_NOMEM;
+    }
+    ctx->kf_depth_alt_cap = ctx->kf_src_alt_cap = cap;
+    return EBVO_OK;
+}
+
+extern "C" int ebvo_temporal_promote_keyframe(ebvo_ctx *ctx, int slot, const ebvo_stereo_calib *cal, const ebvo_depth_carry_params *params,
+                                              const double R[9], const double t[3], ebvo_depth_carried *out)
+{
+    Slot *sp;
+    if (get_slot(ctx, slot, &sp))
+        return EBVO_ERR_ARG;
+    Slot &s = *sp;
+    // the frame's size enters the accepted ranges through the grid; a slot without a pair has none yet
+    if (!carry_args_ok(cal, params, R, t, out, s.have_run ? s.cur_w : 1, s.have_run ? s.cur_h : 1))
+        return EBVO_ERR_ARG;
+    if (ctx->kf_n < 0)
+    {
+        ctx->last_error = "no keyframe to promote from (ebvo_temporal_set_keyframe first)";
+        return EBVO_ERR_STATE;
+    }
+    if (int rc = keyframe_slot_state(ctx, s))
+        return rc;
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = drain_fetch(ctx, s))
+        return rc;
+    const int n_old = ctx->kf_n, n_new = s.n_final;
+    // an old keyframe at the prior has nothing to carry
+    const bool carry = !ctx->kf_depth_fresh && n_old > 0 && n_new > 0;
+    int32_t counts[CARRY_COUNTS] = {0, 0, 0, 0, 0, 0};
+    if (carry)
+    {
+        if (int rc = carry_alt_ensure(ctx, (size_t)n_new))
+            return rc;
+        const ebvo_edge *fl, *fr;
+        final_mates(s, &fl, &fr);
+        // behind these launches, on the same stream, the installation overwrites the store they read
+        const TemporalGridScope grid_scope(ctx, s);
+        const int rc = carry_run(ctx, s, ctx->kf_L, ctx->kf_R, n_old, ctx->kf_lambda, ctx->kf_info, ctx->kf_nobs, fl, fr, n_new, s.cur_w, s.cur_h,
+                                 cal, params, R, t, ctx->kf_lambda_alt, ctx->kf_info_alt, ctx->kf_nobs_alt, ctx->kf_dflags_alt, ctx->kf_src_alt,
+                                 counts);
+        if (rc)
+        {
+            (void)hipStreamSynchronize(s.stream);
+            return rc;
+        }
+    }
+    if (int rc = keyframe_install(ctx, s))
+    {
+        (void)hipStreamSynchronize(s.stream); // the counters' copy writes this frame's stack
+        return rc;
+    }
+    if (carry)
+    {
+        std::swap(ctx->kf_lambda, ctx->kf_lambda_alt);
+        std::swap(ctx->kf_info, ctx->kf_info_alt);
+        std::swap(ctx->kf_nobs, ctx->kf_nobs_alt);
+        std::swap(ctx->kf_dflags, ctx->kf_dflags_alt);
+        std::swap(ctx->kf_depth_cap, ctx->kf_depth_alt_cap);
+        std::swap(ctx->kf_src, ctx->kf_src_alt);
+        std::swap(ctx->kf_src_cap, ctx->kf_src_alt_cap);
+        ctx->kf_depth_fresh = false;
+    }
+    ctx->kf_promoted = true;
+    ctx->kf_src_none = !carry;
+    carry_publish(counts, n_old, n_new, out);
+    return EBVO_OK;
+}
+
+extern "C" int ebvo_temporal_depth_source(ebvo_ctx *ctx, int32_t *src_index)
+{
+    if (!ctx)
+        return EBVO_ERR_ARG;
+    if (ctx->kf_n < 0 || !ctx->kf_promoted)
+    {
+        ctx->last_error = "the keyframe was not installed by ebvo_temporal_promote_keyframe";
+        return EBVO_ERR_STATE;
+    }
+    const size_t n = (size_t)ctx->kf_n;
+    if (!src_index || n == 0)
+        return EBVO_OK;
+    if (ctx->kf_src_none)
+    {
+        for (size_t i = 0; i < n; ++i)
+            src_index[i] = -1;
+        return EBVO_OK;
+    }
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    EBVO_HIP(ctx, hipMemcpy(src_index, ctx->kf_src, 4 * n, hipMemcpyDeviceToHost));
     return EBVO_OK;
 }
 

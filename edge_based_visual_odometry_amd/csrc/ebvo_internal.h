@@ -188,6 +188,8 @@ struct Slot
                                  // planes and both edge grids of either call
     GrowBuf depth_up, depth_ws;  // inverse-depth filter (depth_kernels.hip): the uploaded arrays of the host-array call; Gamma and T1,
                                  // the tile sums and the record of either call
+    GrowBuf carry_up, carry_ws;  // handover of the depths on promotion (carry_kernels.hip): the uploaded arrays and the outgoing state
+                                 // of the host-array call; the counters, the old mates' projections, their planes and grid of either call
     GrowBuf pose_refit;          // inlier refit (pose_refit_kernels.hip): seven planes per quad, the fit set, the mask, the result
     // ground-truth evaluation (gt_kernels.hip, ebvo_stereo_set_gt): armed = the buffers below describe the resident pair
     GrowBuf gt_disp, gt_geom, gt_flags, gt_boxes, gt_pool_i32, gt_pool_idx, gt_rows, gt_tot;
@@ -350,6 +352,15 @@ struct ebvo_ctx
     uint8_t *kf_dflags = nullptr;
     size_t kf_depth_cap = 0;
     bool kf_depth_fresh = true;
+    // ebvo_temporal_promote_keyframe: the carried state is computed into this second set and the two sets change places once the
+    // slot is installed, so that a refused or failed promotion leaves the old keyframe's state as it was.  kf_src: src_index of
+    // the last promotion (kf_src_alt: where the next one writes it)
+    double *kf_lambda_alt = nullptr, *kf_info_alt = nullptr;
+    int32_t *kf_nobs_alt = nullptr, *kf_src = nullptr, *kf_src_alt = nullptr;
+    uint8_t *kf_dflags_alt = nullptr;
+    size_t kf_depth_alt_cap = 0, kf_src_cap = 0, kf_src_alt_cap = 0;
+    bool kf_promoted = false;  // the keyframe was installed by a promotion (ebvo_temporal_depth_source)
+    bool kf_src_none = true;   // ... whose old keyframe had nothing to carry: every src_index is -1
     bool use_depth = false;    // ebvo_temporal_use_depth
     bool undist_on = false;    // ebvo_stereo_set_undistort
     ebvo_undistort_params undist{};
@@ -763,6 +774,21 @@ int depth_run(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d
               const ebvo_stereo_calib *cal, const ebvo_depth_params *dp, const double *R, const double *t, const double *d_lam_in,
               const double *d_info_in, const int32_t *d_nobs_in, double *d_lam, double *d_info, int32_t *d_nobs, uint8_t *d_flags,
               DepthRecord *rec);
+// align_kernels.hip: the alignment's CSR cell grid (align_cells / align_cell_scan / align_cell_scatter, unchanged) over ANY edge
+// list of n >= 1 device edges, enqueued and not waited for.  ws: align_grid_ints(n, n_cells) int32 of the caller's (cell_of [n],
+// cnt, fill [n_cells each], start [n_cells + 1], list [n]); *start / *list: where the association's two arrays lie in it.
+inline size_t align_grid_ints(int n, int n_cells) { return 2 * (size_t)n + 3 * (size_t)n_cells + 1; }
+int align_grid_enqueue(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_E, int n, int cell, int gw, int gh, int32_t *ws, const int32_t **start,
+                       const int32_t **list);
+// carry_kernels.hip: the handover of the old keyframe's depths to n_new >= 1 new mates, enqueued and NOT waited for (the copy of
+// the six counters to `counts` included: n_sources, n_live, n_dead, n_assoc, n_carried, n_gated).  The in-state is NULL (no
+// association is launched: every live new mate at its prior) or three device arrays of n_old values.  The workspace is
+// s.carry_ws; developer key 22 (Slot::tq_blocks) caps its grid-stride launches.
+constexpr int CARRY_COUNTS = 6;
+int carry_run(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_oldL, const ebvo_edge *d_oldR, int n_old, const double *d_lam_in,
+              const double *d_info_in, const int32_t *d_nobs_in, const ebvo_edge *d_newL, const ebvo_edge *d_newR, int n_new, int img_w,
+              int img_h, const ebvo_stereo_calib *cal, const ebvo_depth_carry_params *cp, const double *R, const double *t, double *d_lam,
+              double *d_info, int32_t *d_nobs, uint8_t *d_flags, int32_t *d_src, int32_t *counts);
 int misc_fp64_peak(ebvo_ctx *ctx, Slot &s, int iters, double *tf_muladd, double *tf_fma);
 
 #endif

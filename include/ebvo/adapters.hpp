@@ -1068,6 +1068,69 @@ class MotionTrackerHIP
         return report(*ctx_, last_status, "ebvo_temporal_use_depth");
     }
 
+    // The handover of the refined depths when the current frame becomes the keyframe (this project's own; the contract is in
+    // ebvo_hip.h): each new mate takes the depth the nearest old projection of compatible orientation predicts for it and
+    // fuses it with its own triangulation prior.  When to switch stays the caller's decision.
+    struct Carry_Options
+    {
+        ebvo_depth_carry_params p;
+        Carry_Options() { ebvo_depth_carry_default_params(&p); }
+    };
+    struct Carried_Depths
+    {
+        Mate_Depths depths;             // the NEW keyframe's mates (depths.refined is not used)
+        std::vector<int32_t> src_index; // per new mate: the old mate it took its depth from, or -1
+        ebvo_depth_carried carried{};
+    };
+
+    // the slot's finalised pair becomes the keyframe and inherits the old keyframe's depths through the pose (state.R, state.t),
+    // old keyframe -> this frame
+    bool promote_Keyframe(int slot, const Carry_Options &opt, const Align_State &state, ebvo_depth_carried &carried)
+    {
+        carried = ebvo_depth_carried{};
+        last_status = ebvo_temporal_promote_keyframe(ctx_->get(), slot, &calib_, &opt.p, state.R.data(), state.t.data(), &carried);
+        return report(*ctx_, last_status, "ebvo_temporal_promote_keyframe");
+    }
+
+    // the same on host arrays: `old_depths` is the old mates' state (empty lambda: nothing to carry, the priors alone)
+    bool carry_Mate_Depths(const std::vector<ebvo_edge> &kf_left, const std::vector<ebvo_edge> &kf_right, const Mate_Depths &old_depths,
+                           const std::vector<ebvo_edge> &new_left, const std::vector<ebvo_edge> &new_right, int img_w, int img_h,
+                           const Carry_Options &opt, const Align_State &state, Carried_Depths &out)
+    {
+        const size_t no = kf_left.size(), nn = new_left.size();
+        out.carried = ebvo_depth_carried{};
+        const bool none = old_depths.lambda.empty();
+        if (kf_right.size() != no || new_right.size() != nn ||
+            (!none && (old_depths.lambda.size() != no || old_depths.info.size() != no || old_depths.n_obs.size() != no)))
+        {
+            last_status = EBVO_ERR_ARG;
+            return false;
+        }
+        out.depths.lambda.assign(nn, 1.0);
+        out.depths.info.assign(nn, 0.0);
+        out.depths.n_obs.assign(nn, 0);
+        out.depths.flags.assign(nn, 0);
+        out.src_index.assign(nn, -1);
+        last_status = ebvo_depth_carry(ctx_->get(), kf_left.data(), kf_right.data(), (int)no, none ? nullptr : old_depths.lambda.data(),
+                                       none ? nullptr : old_depths.info.data(), none ? nullptr : old_depths.n_obs.data(), new_left.data(),
+                                       new_right.data(), (int)nn, img_w, img_h, &calib_, &opt.p, state.R.data(), state.t.data(),
+                                       out.depths.lambda.data(), out.depths.info.data(), out.depths.n_obs.data(), out.depths.flags.data(),
+                                       out.src_index.data(), &out.carried);
+        return report(*ctx_, last_status, "ebvo_depth_carry");
+    }
+
+    // src_index of the last promote_Keyframe (n_kf of the slot's ebvo_temporal_align_size)
+    bool mate_depth_sources(int slot, std::vector<int32_t> &src_index)
+    {
+        int32_t n_kf = 0, n0 = 0, n1 = 0;
+        last_status = ebvo_temporal_align_size(ctx_->get(), slot, &n_kf, &n0, &n1);
+        if (!report(*ctx_, last_status, "ebvo_temporal_align_size"))
+            return false;
+        src_index.assign((size_t)n_kf, -1);
+        last_status = ebvo_temporal_depth_source(ctx_->get(), src_index.data());
+        return report(*ctx_, last_status, "ebvo_temporal_depth_source");
+    }
+
     // n_runs calls of the reference's Solution_Constraints_Application (src/Pipeline.cpp:198-203 makes 20) in one device
     // call: one vector of five stages per run.  Empty on an error (last_status) and when the slot has too few quads.
     std::vector<std::vector<Quad_Pair_Evaluation_Metrics>> Solution_Constraints_Application(int slot, const Ransac_Options &opt,

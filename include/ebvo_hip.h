@@ -46,7 +46,10 @@ extern "C" {
                               ebvo_pose_align_edges, ebvo_temporal_align_pose, ebvo_temporal_align_size; and with the
                               additive inverse-depth filter: ebvo_depth_params / _refined, ebvo_depth_default_params,
                               ebvo_depth_refine_edges, ebvo_temporal_refine_depth, ebvo_temporal_depth_fetch / _reset,
-                              ebvo_temporal_use_depth, ebvo_pose_align_edges_depth */
+                              ebvo_temporal_use_depth, ebvo_pose_align_edges_depth; and with the additive handover of
+                              the depths on promotion: ebvo_depth_carry_params, ebvo_depth_carried,
+                              ebvo_depth_carry_default_params, ebvo_depth_carry, ebvo_temporal_promote_keyframe,
+                              ebvo_temporal_depth_source */
 
 typedef struct ebvo_ctx ebvo_ctx;
 
@@ -975,6 +978,90 @@ int ebvo_pose_align_edges_depth(ebvo_ctx *ctx, const ebvo_edge *kf_left, const e
                                 const ebvo_edge *cf_edges_left, int n0, const ebvo_edge *cf_edges_right, int n1, int img_w, int img_h,
                                 const ebvo_stereo_calib *cal, const ebvo_align_params *params, const double R0[9], const double t0[3],
                                 ebvo_aligned_pose *out, int32_t *assoc_left, int32_t *assoc_right);
+
+/* ---- handover of the refined depths to the next keyframe on promotion (this project's own stage) -------------------- */
+/* When the current frame becomes the keyframe, the old keyframe's refined depths are carried to the new keyframe's mates
+ * through the known relative pose: each old mate is projected into the new frame, each new mate GATHERS the nearest old
+ * projection of compatible orientation, and the depth it predicts is fused, as a second independent measurement, with the
+ * new mate's own triangulation prior.  This comment is the arithmetic contract; tests/oracle_carry.py restates it and the
+ * device matches it bit for bit.  fp64, no FMA, IEEE division and sqrt; mv3 / dot3 of csrc/ebvo_geom.h; ebvo_sincos and
+ * ebvo_atan2 of csrc/ebvo_math.h.  Additive: the ABI version stays 6.
+ * Inputs: the old keyframe's mates kf_left[i], kf_right[i], i < n_old, with their state (lambda_i, info_i, n_obs_i); the new
+ *   keyframe's mates new_left[m], new_right[m], m < n_new (the final mates of the frame being promoted); that frame's size
+ *   w x h; the calibration; the pose (R, t) from the old keyframe to the new frame in the convention of the pose search
+ *   (Gc = R Gamma + t in the left camera).
+ * Old mate i: Gamma and T1 exactly as the alignment's align_prepare_kernel forms them.  It is a SOURCE iff every component of
+ *   Gamma is finite and Gamma_z > 0, lambda_i is finite and > 0, info_i > 0 and n_obs_i >= min_obs.  Of a source, in this
+ *   order: Gs = Gamma / lambda_i (three divisions); RG = mv3(R, Gs); X = RG + t; q and o: the projection and the mapped
+ *   orientation by the alignment's camera-0 formulas (p = mv3(K_left, X), q = p / p2, ray = mv3(K_left^-1, (q0 / q2, q1 / q2,
+ *   q2 / q2)), T2 = mv3(R, T1), t2 = T2 - T2_z ray normalised when its squared norm is > 0, o = ebvo_atan2(t2_y, t2_x));
+ *   zp = X_z; a = RG_z / (zp lambda_i).  A source is LIVE by the alignment's camera-0 test against the new frame's size:
+ *   img_margin < q_x < w - img_margin, img_margin < q_y < h - img_margin and zp > 0 (NaN, +-inf: not live).
+ * New mate m: Gamma' by the same geometry.  It is DEAD by the filter's rule (a component of Gamma' not finite, or Gamma'_z not
+ *   > 0): lambda 1.0, info +0.0, n_obs 0, flag EBVO_DEPTH_DEAD, src_index -1.  A live mate's prior is the filter's:
+ *   b = sqrt(dot3(T21, T21)), s' = (sigma_disp_px Gamma'_z) / (K_left[0] b), info0' = 1.0 / (s' s').
+ * Association (a gather: the new mate looks for old projections, so no two sources ever write the same state).  The grid is
+ *   the alignment's (cell_size; a projection is in cell ((int)q_x / cell_size, (int)q_y / cell_size) by align_cell's rule),
+ *   built over the live sources' projections.  With e = new_left[m]: the candidates of a live mate m are the live sources i
+ *   in the cells within ceil(radius / cell_size) of e's cell (by the same rule; a mate whose e.x or e.y is in no cell has no
+ *   candidate), clipped to the grid, with
+ *   orient_close(o_i, e.theta, orient_thr_deg) and d2 = dx dx + dy dy <= radius radius, dx = q_x - e.x, dy = q_y - e.y.
+ *   The mate takes the smallest (d2, i) in lexicographic order -- no traversal order enters -- or none.  src_index[m] = i,
+ *   or -1.
+ * Fusion of an associated live mate: lm = Gamma'_z / zp_i (the ratio of the new triangulated depth to the one the old
+ *   keyframe predicts: the new mate's lambda as the old keyframe measures it); c = lm a_i (d lm / d lambda_i up to sign);
+ *   im = (carry info_i) / (c c).  If im is not finite or not > 0 the mate is treated as gated.  Gate: d = lm - 1.0,
+ *   v = 1.0 / info0' + 1.0 / im; accepted iff lambda_min <= lm <= lambda_max and d d <= (gate_sigmas gate_sigmas) v.
+ *   Accepted: h = info0' + im; lambda' = (info0' + im lm) / h; info' = min(h, info_max) (h if it is the smaller, else
+ *   info_max); n_obs' = n_obs_i; flag EBVO_DEPTH_CARRIED.  Gated: the prior (1.0, info0', 0), flag EBVO_DEPTH_CARRY_GATED.
+ *   Not associated: the prior, flags 0.
+ * The record counts: n_sources, n_live (of the old mates; both 0 when no association is launched), n_dead (new mates),
+ *   n_assoc = n_carried + n_gated.  Integers only; no launch geometry enters anything. */
+#define EBVO_DEPTH_CARRIED 32u
+#define EBVO_DEPTH_CARRY_GATED 64u
+typedef struct ebvo_depth_carry_params
+{
+    double sigma_disp_px;          /* 0.25 px: the disparity noise the new mate's prior stands for (the filter's) */
+    double radius;                 /* 1.5 px: an old projection further from the new mate's left edge is another curve point */
+    int32_t cell_size, min_obs;    /* 4 px; 1: an old mate that fused fewer frames has nothing to hand over (>= 0) */
+    double orient_thr_deg;         /* 10 */
+    double carry;                  /* 0.5, in (0, 1]: discount of the carried information for pose and association error */
+    double gate_sigmas;            /* 3 (> 0, +inf = no chi gate) */
+    double lambda_min, lambda_max; /* 0.25, 4.0 */
+    double info_max;               /* 1e6 (+inf = no clip) */
+    double img_margin;             /* 10, as the alignment */
+    int32_t reserved, pad;         /* 0, 0 */
+} ebvo_depth_carry_params;
+typedef struct ebvo_depth_carried
+{
+    int32_t n_old, n_sources, n_live, n_new, n_dead, n_assoc, n_carried, n_gated;
+} ebvo_depth_carried;
+void ebvo_depth_carry_default_params(ebvo_depth_carry_params *p);
+/* On host arrays.  lambda_in / info_in / n_obs_in: the old mates' state, all three or none.  lambda / info / n_obs / flags /
+ * src_index: n_new values each, all five required when n_new > 0.  A NULL in-state, n_old = 0 or n_new = 0 launches no
+ * association: every live new mate is at its prior.  Accepted: sigma_disp_px and radius finite and > 0, cell_size >= 1 with
+ * ceil(radius / cell_size) <= 8, orient_thr_deg >= 0, 0 < carry <= 1, gate_sigmas > 0 (+inf allowed), min_obs >= 0,
+ * 0 < lambda_min <= lambda_max finite, info_max > 0 (+inf allowed), img_margin >= 0, reserved 0, no NaN, R and t finite,
+ * img_w, img_h >= 1 with a grid of at most 2^26 cells; anything else: EBVO_ERR_ARG, nothing touched.  Runs on slot 0's stream
+ * under the state rules of ebvo_pose_align_edges; the inputs are copied before the call returns. */
+int ebvo_depth_carry(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *kf_right, int n_old, const double *lambda_in,
+                     const double *info_in, const int32_t *n_obs_in, const ebvo_edge *new_left, const ebvo_edge *new_right, int n_new,
+                     int img_w, int img_h, const ebvo_stereo_calib *cal, const ebvo_depth_carry_params *params, const double R[9],
+                     const double t[3], double *lambda, double *info, int32_t *n_obs, uint8_t *flags, int32_t *src_index,
+                     ebvo_depth_carried *out);
+/* The slot's finalised pair becomes the keyframe and inherits the old keyframe's refined depths: the carried state is
+ * computed first, into buffers of the call's own, from the old keyframe's mates, its resident state and the slot's final
+ * mates; then the slot is installed as ebvo_temporal_set_keyframe installs it (the same store, the same bits); then the
+ * carried state is installed, so that the new keyframe is NOT at the prior.  Needs a keyframe besides what
+ * ebvo_temporal_set_keyframe needs; its refusals otherwise (nothing in flight in any slot).  An old keyframe still at the prior
+ * has nothing to carry: the call then is ebvo_temporal_set_keyframe, the record holds n_old and n_new and zeros, and the new
+ * keyframe is at the prior.  On any refusal the old keyframe and its state stay as they were.  Pending priors are dropped and
+ * the keyframe generation is bumped, as by ebvo_temporal_set_keyframe.  The decision to switch stays the caller's. */
+int ebvo_temporal_promote_keyframe(ebvo_ctx *ctx, int slot, const ebvo_stereo_calib *cal, const ebvo_depth_carry_params *params,
+                                   const double R[9], const double t[3], ebvo_depth_carried *out);
+/* src_index of the last promotion: n_kf int32 (all -1 when the old keyframe had nothing to carry).  EBVO_ERR_STATE when the
+ * keyframe was not installed by a promotion. */
+int ebvo_temporal_depth_source(ebvo_ctx *ctx, int32_t *src_index);
 
 /* ---- ground-truth evaluation from a disparity map (the reference's has_gt() == true branch, is_left = true) ------- */
 /* Find_Stereo_GT_Locations (src/Stereo_Matches.cpp:133-200), get_Stereo_Edge_GT_Pairs (:202-268) and
