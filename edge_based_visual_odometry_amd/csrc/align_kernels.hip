@@ -109,21 +109,12 @@ __global__ __launch_bounds__(256) void align_prepare_kernel(FinalCalib C, const 
     }
 }
 
-// (int)v / cell inside [0, n_cells), or -1.  The comparison is made on the double, so that NaN and +-inf are in no cell and
-// the cast is defined: (int)v / cell >= 0 iff v > -cell, < n_cells iff v < n_cells * cell
-__device__ inline int align_cell(double v, int cell, int n_cells)
-{
-    if (!(v > -(double)cell && v < (double)n_cells * (double)cell))
-        return -1;
-    return (int)v / cell;
-}
-
 __global__ __launch_bounds__(256) void align_cells_kernel(const ebvo_edge *__restrict__ E, int n, int cell, int gw, int gh,
                                                           int32_t *__restrict__ cell_of, int32_t *__restrict__ cnt)
 {
     for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x)
     {
-        const int cx = align_cell(E[j].x, cell, gw), cy = align_cell(E[j].y, cell, gh);
+        const int cx = grid_cell(E[j].x, cell, gw), cy = grid_cell(E[j].y, cell, gh);
         const int c = (cx >= 0 && cy >= 0) ? cy * gw + cx : -1;
         cell_of[j] = c;
         if (c >= 0)
@@ -175,26 +166,6 @@ __global__ __launch_bounds__(256) void align_cell_scatter_kernel(const int32_t *
     }
 }
 
-// K * G, then the three components over the z the product gave (tgt_kernels.hip: project3)
-__device__ inline void align_project3(const double *K, const double *G, double *p)
-{
-    mv3(K, G, p);
-    const double z = p[2];
-    p[0] /= z;
-    p[1] /= z;
-    p[2] /= z;
-}
-
-// orientation_mapping as tgt_kernels.hip's mapped_orientation forms it
-__device__ inline double align_orientation(const double *T2, const double *p, const double *Kinv)
-{
-    const double g[3] = {p[0] / p[2], p[1] / p[2], p[2] / p[2]};
-    double ray[3], t2d[3];
-    mv3(Kinv, g, ray);
-    project_tangent3(T2, ray, t2d);
-    return ebvo_atan2(t2d[1], t2d[0]);
-}
-
 // Sixteen lanes per item; item = camera * n_kf + mate.  The pose is read from the state.  A launch of a round (round >= 0)
 // returns at once when the call has ended; the last association (round < 0) always runs.  cnt: st->n_assoc, zeroed by the
 // consumer of the association before this launch (align_init / the last workgroup of the launch that read it).
@@ -225,24 +196,17 @@ __global__ __launch_bounds__(256) void align_associate_kernel(AlignArgs A, Align
         {
             const double G[3] = {GT[i], GT[(size_t)n + i], GT[2 * (size_t)n + i]};
             const double T1[3] = {GT[3 * (size_t)n + i], GT[4 * (size_t)n + i], GT[5 * (size_t)n + i]};
-            double Y[3], q[3], T2[3];
-            mv3(Rt, G, Y);
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-                Y[k] += Rt[9 + k];
+            double RG[3], Y[3], q[3], T2[3];
+            pose_point(Rt, Rt + 9, G, RG, Y);
             if (cam)
             {
-                double Yr[3];
-                mv3(A.R21, Y, Yr);
-#pragma unroll
-                for (int k = 0; k < 3; ++k)
-                    Y[k] = Yr[k] + A.T21[k];
+                const double X[3] = {Y[0], Y[1], Y[2]};
+                stereo_point(A.R21, A.T21, X, Y);
             }
-            align_project3(cam ? A.Kr : A.Kl, Y, q);
+            project3(cam ? A.Kr : A.Kl, Y, q);
             mv3(cam ? M : Rt, T1, T2);
-            const double o = align_orientation(T2, q, cam ? A.Kri : A.Kli);
-            const bool live = q[0] > A.margin && q[1] > A.margin && q[0] < A.x_max && q[1] < A.y_max && Y[2] > 0.0;
-            if (live)
+            const double o = mapped_orientation(T2, q, cam ? A.Kri : A.Kli);
+            if (live_projection(q[0], q[1], Y[2], A.margin, A.x_max, A.y_max))
             {
                 // inside the margin the casts are defined and the cell is inside the grid
                 const int qx = min((int)q[0] / A.cell, A.gw - 1), qy = min((int)q[1] / A.cell, A.gh - 1);
@@ -310,35 +274,14 @@ struct AlignCam
 __device__ static inline void align_camera(const double *K, const double *Y, const double *RG, const double *Rs, bool assoc, double ex,
                                            double ey, double n0, double n1, double delta, AlignCam &o)
 {
-    double p[3];
-    mv3(K, Y, p);
-    const double pix = p[0] / p[2], piy = p[1] / p[2];
+    double pix, piy, jx[3], jy[3];
+    const double pz = camera_pixel(K, Y, pix, piy);
     o.r = n0 * (pix - ex) + n1 * (piy - ey);
     const double rho = fabs(o.r);
     o.valid = assoc && rho < INFINITY;
-    const bool small = rho <= delta;
-    o.w = small ? 1.0 : delta / rho;
-    o.cost = small ? (rho * rho) * 0.5 : delta * (rho - delta * 0.5);
-    const double ip = 1.0 / p[2];
-    double jx[3], jy[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-    {
-        jx[j] = ip * (K[j] - pix * K[6 + j]);
-        jy[j] = ip * (K[3 + j] - piy * K[6 + j]);
-    }
-    if (Rs)
-    {
-        double a[3], b[3];
-        mtv3(Rs, jx, a); // row . R21
-        mtv3(Rs, jy, b);
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-        {
-            jx[j] = a[j];
-            jy[j] = b[j];
-        }
-    }
+    o.w = huber_weight(rho, delta);
+    o.cost = huber_cost(rho, delta);
+    camera_rows(K, Rs, pz, pix, piy, jx, jy);
     double Jx[3], Jy[3];
     cross3(RG, jx, Jx); // m . -[R Gamma]x = R Gamma x m
     cross3(RG, jy, Jy);
@@ -357,14 +300,8 @@ __device__ static inline void align_mate(const AlignArgs &A, const double *Rt, c
     const size_t n = (size_t)A.n_kf;
     const double G[3] = {GT[i], GT[n + i], GT[2 * n + i]};
     double RG[3], X[3], Y[3];
-    mv3(Rt, G, RG);
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-        X[k] = RG[k] + Rt[9 + k];
-    mv3(A.R21, X, Y);
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-        Y[k] = Y[k] + A.T21[k];
+    pose_point(Rt, Rt + 9, G, RG, X);
+    stereo_point(A.R21, A.T21, X, Y);
     align_camera(A.Kl, X, RG, nullptr, P0.idx[i] >= 0, P0.ex[i], P0.ey[i], P0.n0[i], P0.n1[i], A.huber, L);
     if (A.cameras > 1)
         align_camera(A.Kr, Y, RG, A.R21, P1.idx[i] >= 0, P1.ex[i], P1.ey[i], P1.n0[i], P1.n1[i], A.huber, R);
@@ -376,31 +313,6 @@ __device__ static inline void align_mate(const AlignArgs &A, const double *Rt, c
         for (int k = 0; k < 6; ++k)
             R.J[k] = 0.0;
     }
-}
-
-// x of every lane of a wave -> part[group] by the halving tree x[l] += x[l + s], s = 32 .. 1 (lane 0 ends with it)
-__device__ static inline void align_wave_sum(double x, int lane, double *slot)
-{
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1)
-        x = x + __shfl_down(x, s);
-    if (lane == 0)
-        *slot = x;
-}
-
-// the 16 group sums of value v by the same tree, s = 8 .. 1
-__device__ static inline double align_group_sum(const double *part, int stride, int v)
-{
-    double g[AL_GROUPS];
-#pragma unroll
-    for (int j = 0; j < AL_GROUPS; ++j)
-        g[j] = part[j * stride + v];
-#pragma unroll
-    for (int s = AL_GROUPS / 2; s >= 1; s >>= 1)
-#pragma unroll
-        for (int l = 0; l < s; ++l)
-            g[l] = g[l] + g[l + s];
-    return g[0];
 }
 
 // The tile is stored; true in every thread of the workgroup that arrived last (which re-arms the counter).  The classic
@@ -423,10 +335,10 @@ __device__ static inline bool align_last_workgroup(AlignState *st, int tiles, in
     return last;
 }
 
-// what follows the 28 sums of step `it` of round `rnd` (the refit's decisions; reasons 3 and 4 end the call)
+// what follows the 28 sums of step `it` of round `rnd`: the round's first step consumes the association's counts, then the
+// shared decision (ebvo_gn6.h); stop reasons 3 and 4 end the call
 __device__ static inline void align_decide(const AlignArgs &A, int rnd, int it, const double *sums, AlignState &st)
 {
-    st.go = 0;
     if (it == 0)
     {
         ++st.rounds_run;
@@ -434,6 +346,7 @@ __device__ static inline void align_decide(const AlignArgs &A, int rnd, int it, 
         st.n_assoc[0] = st.n_assoc[1] = 0; // consumed: the next association counts from zero
         if (st.fit_terms < A.min_terms)
         {
+            st.go = 0;
             st.stop = 4;
             st.done = 1;
             if (rnd == 0)
@@ -441,60 +354,8 @@ __device__ static inline void align_decide(const AlignArgs &A, int rnd, int it, 
             return;
         }
     }
-    const double cost = sums[27];
-    if (it == 0)
-        st.c_first = cost;
-    if (it > 0 && !(cost <= st.c_prev)) // the cost rose (a NaN counts as larger): back to the pose before
-    {
-#pragma unroll
-        for (int i = 0; i < 12; ++i)
-            st.Rt[i] = st.Pv[i];
-        --st.steps;
-        st.stop = 2;
-        return;
-    }
-    st.c_last = cost;
-    if (it == A.iterations)
-    {
-        st.stop = 1;
-        return;
-    }
-    double d[6];
-    if (!refit_solve(sums, d))
-    {
-        st.stop = 3;
+    if (gn6_decide(rnd, it, A.iterations, A.eps, sums, st) == 3)
         st.done = 1;
-        if (rnd == 0 && it == 0)
-            st.status = 2;
-        return;
-    }
-    double Rt[12];
-#pragma unroll
-    for (int i = 0; i < 12; ++i)
-        st.Pv[i] = Rt[i] = st.Rt[i];
-    st.c_prev = cost;
-    refit_rotate(d, Rt);
-    double m = 0.0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        Rt[9 + i] = Rt[9 + i] + d[3 + i];
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-    {
-        const double a = fabs(d[i]);
-        if (a > m)
-            m = a;
-    }
-#pragma unroll
-    for (int i = 0; i < 12; ++i)
-        st.Rt[i] = Rt[i];
-    ++st.steps;
-    if (m < A.eps)
-    {
-        st.stop = 0;
-        return;
-    }
-    st.go = 1;
 }
 
 // Step `it` of round `rnd`: workgroup t forms the 28 sums of tile t.  A block of 256 or 512 threads owns lanes v, v + blockDim,
@@ -545,11 +406,11 @@ __global__ __launch_bounds__(AL_TILE) void align_sums_kernel(AlignArgs A, AlignS
         }
 #pragma unroll
         for (int s = 0; s < AL_SUMS; ++s)
-            align_wave_sum(term[s], lane, &part[(v >> 6) * AL_SUMS + s]);
+            wave_sum(term[s], lane, &part[(v >> 6) * AL_SUMS + s]);
     }
     __syncthreads();
     if (tid < AL_SUMS)
-        tile_sums[(size_t)tile * AL_SUMS + tid] = align_group_sum(part, AL_SUMS, tid);
+        tile_sums[(size_t)tile * AL_SUMS + tid] = group_sum<AL_GROUPS>(part, AL_SUMS, tid);
     if (!align_last_workgroup(st, A.tiles, &flag))
         return;
     if (tid < AL_SUMS)
@@ -593,15 +454,12 @@ __global__ __launch_bounds__(AL_TILE) void align_metric_kernel(AlignArgs A, Alig
             term = 0.0 + ((L.valid ? L.r * L.r : 0.0) + (R.valid ? R.r * R.r : 0.0));
             inl = (L.valid && fabs(L.r) < A.inlier ? 1 : 0) + (R.valid && fabs(R.r) < A.inlier ? 1 : 0);
         }
-        for (int s = 32; s >= 1; s >>= 1)
-            inl += __shfl_down(inl, s);
-        if (lane == 0 && inl)
-            atomicAdd(&st->inliers, inl);
-        align_wave_sum(term, lane, &part[v >> 6]);
+        wave_count(inl, lane, &st->inliers);
+        wave_sum(term, lane, &part[v >> 6]);
     }
     __syncthreads();
     if (tid == 0)
-        tile_sums[tile] = align_group_sum(part, 1, 0);
+        tile_sums[tile] = group_sum<AL_GROUPS>(part, 1, 0);
     if (!align_last_workgroup(st, A.tiles, &flag))
         return;
     if (tid == 0)
@@ -629,8 +487,6 @@ __global__ __launch_bounds__(AL_TILE) void align_metric_kernel(AlignArgs A, Alig
     }
 }
 
-inline size_t al64(size_t v) { return (v + 63) & ~(size_t)63; }
-
 struct AlignLayout
 {
     size_t o_state, o_out, o_tiles, o_gt, o_assoc[2], o_grid[2], total;
@@ -643,22 +499,22 @@ AlignLayout align_layout(int n_kf, int tiles, int n_cells, const int ne[2])
     const size_t n = (size_t)n_kf;
     size_t o = 0;
     L.o_state = o;
-    o += al64(sizeof(AlignState));
+    o += round_up64(sizeof(AlignState));
     L.o_out = o;
-    o += al64(sizeof(AlignResult));
+    o += round_up64(sizeof(AlignResult));
     L.o_tiles = o;
-    o += al64(sizeof(double) * AL_SUMS * (size_t)tiles);
+    o += round_up64(sizeof(double) * AL_SUMS * (size_t)tiles);
     L.o_gt = o;
-    o += al64(sizeof(double) * 6 * n);
+    o += round_up64(sizeof(double) * 6 * n);
     for (int c = 0; c < 2; ++c)
     {
         L.o_assoc[c] = o;
-        o += al64(sizeof(int32_t) * n) + al64(sizeof(double) * 4 * n);
+        o += round_up64(sizeof(int32_t) * n) + round_up64(sizeof(double) * 4 * n);
     }
     for (int c = 0; c < 2; ++c)
     {
         L.o_grid[c] = o;
-        o += al64(sizeof(int32_t) * (2 * (size_t)ne[c] + 3 * (size_t)n_cells + 1));
+        o += round_up64(sizeof(int32_t) * (2 * (size_t)ne[c] + 3 * (size_t)n_cells + 1));
     }
     L.total = o;
     return L;
@@ -704,7 +560,7 @@ int align_setup(ebvo_ctx *ctx, Slot &s, int n_kf, const ebvo_edge *d_E0, int n0,
         S.ne[c] = ne[c];
         char *a = base + L.o_assoc[c];
         P[c].idx = (int32_t *)a;
-        P[c].ex = (double *)(a + al64(sizeof(int32_t) * n));
+        P[c].ex = (double *)(a + round_up64(sizeof(int32_t) * n));
         P[c].ey = P[c].ex + n;
         P[c].n0 = P[c].ey + n;
         P[c].n1 = P[c].n0 + n;

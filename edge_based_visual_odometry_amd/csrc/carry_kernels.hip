@@ -2,9 +2,9 @@
 // arithmetic contract is written once in include/ebvo_hip.h; tests/oracle_carry.py restates it on the CPU and the device
 // matches it bit for bit.
 //   carry_project_kernel   one thread per OLD mate: Gamma and T1 (stereo_gamma_tangent), the source test, Gamma / lambda under
-//                          the pose, the projection and the mapped orientation by the alignment's camera-0 formulas.  It
+//                          the pose, the projection and the mapped orientation as the alignment's camera 0 forms them.  It
 //                          writes the projection as an ebvo_edge (x, y, theta = o, index = i; NaN x and y for a mate that is
-//                          not a live source, which align_cell puts in no cell) and a plane each for zp, a, info, n_obs
+//                          not a live source, which grid_cell puts in no cell) and a plane each for zp, a, info, n_obs
 //   (the alignment's align_cells / align_cell_scan / align_cell_scatter kernels then build the CSR grid over that list,
 //   unchanged: align_grid_enqueue)
 //   carry_gather_kernel    ONE lane per NEW mate: Gamma' and the prior, the cell window around the mate's left edge, the
@@ -24,6 +24,7 @@
 #include "ebvo_internal.h"
 #include "ebvo_math.h"
 #include "ebvo_geom.h"
+#include "ebvo_gn6.h"
 
 namespace
 {
@@ -41,27 +42,6 @@ struct CarrySources
     double *zp, *a, *info;
     int32_t *nobs;
 };
-
-__device__ static inline bool carry_finite(double v) { return fabs(v) < INFINITY; }
-__device__ static inline bool carry_live_mate(const double *G) { return carry_finite(G[0]) && carry_finite(G[1]) && carry_finite(G[2]) && G[2] > 0.0; }
-
-// align_kernels.hip's align_cell: (int)v / cell inside [0, n_cells), or -1 (NaN and +-inf are in no cell)
-__device__ static inline int carry_cell(double v, int cell, int n_cells)
-{
-    if (!(v > -(double)cell && v < (double)n_cells * (double)cell))
-        return -1;
-    return (int)v / cell;
-}
-
-// the sum of c over the wave, then one atomic (every lane of the wave calls this)
-__device__ static inline void carry_count(int c, int lane, int32_t *slot)
-{
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1)
-        c += __shfl_down(c, s);
-    if (lane == 0 && c)
-        atomicAdd(slot, c);
-}
 
 __global__ __launch_bounds__(256) void carry_project_kernel(FinalCalib C, CarryArgs A, const ebvo_edge *__restrict__ kfL,
                                                             const ebvo_edge *__restrict__ kfR, const double *__restrict__ lam_in,
@@ -81,29 +61,17 @@ __global__ __launch_bounds__(256) void carry_project_kernel(FinalCalib C, CarryA
         out.index = i;
         out.pad = 0;
         double zp = 0.0, a = 0.0;
-        const bool source = carry_live_mate(G) && carry_finite(lam) && lam > 0.0 && info > 0.0 && nobs >= A.min_obs;
+        const bool source = live_mate(G) && finite_value(lam) && lam > 0.0 && info > 0.0 && nobs >= A.min_obs;
         if (source)
         {
             ++n_src;
             const double Gs[3] = {G[0] / lam, G[1] / lam, G[2] / lam};
-            double RG[3], X[3], q[3], T2[3], ray[3], t2d[3];
-            mv3(A.Rt, Gs, RG);
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-                X[k] = RG[k] + A.Rt[9 + k];
-            // align_project3 and align_orientation of align_kernels.hip, camera 0
-            mv3(A.Kl, X, q);
-            const double z = q[2];
-            q[0] /= z;
-            q[1] /= z;
-            q[2] /= z;
+            double RG[3], X[3], q[3], T2[3];
+            pose_point(A.Rt, A.Rt + 9, Gs, RG, X);
+            project3(A.Kl, X, q); // the alignment's association, camera 0
             mv3(A.Rt, T1, T2);
-            const double g[3] = {q[0] / q[2], q[1] / q[2], q[2] / q[2]};
-            mv3(C.Kli, g, ray);
-            project_tangent3(T2, ray, t2d);
-            const double o = ebvo_atan2(t2d[1], t2d[0]);
-            const bool live = q[0] > A.margin && q[1] > A.margin && q[0] < A.x_max && q[1] < A.y_max && X[2] > 0.0;
-            if (live)
+            const double o = mapped_orientation(T2, q, C.Kli);
+            if (live_projection(q[0], q[1], X[2], A.margin, A.x_max, A.y_max))
             {
                 ++n_live;
                 out.x = q[0];
@@ -120,8 +88,8 @@ __global__ __launch_bounds__(256) void carry_project_kernel(FinalCalib C, CarryA
         S.nobs[i] = nobs;
     }
     const int lane = threadIdx.x & 63;
-    carry_count(n_src, lane, &counts[0]);
-    carry_count(n_live, lane, &counts[1]);
+    wave_count(n_src, lane, &counts[0]);
+    wave_count(n_live, lane, &counts[1]);
 }
 
 // start == nullptr: no association was launched, every live mate is at its prior
@@ -141,7 +109,7 @@ __global__ __launch_bounds__(256) void carry_gather_kernel(FinalCalib C, CarryAr
         double l_out = 1.0, f_out = 0.0;
         int o_out = 0, best_i = -1;
         unsigned fl = 0;
-        if (!carry_live_mate(G))
+        if (!live_mate(G))
         {
             fl = EBVO_DEPTH_DEAD;
             ++n_dead;
@@ -152,7 +120,7 @@ __global__ __launch_bounds__(256) void carry_gather_kernel(FinalCalib C, CarryAr
             const double s = (A.sigma_disp * G[2]) / (A.Kl[0] * b);
             const double info0 = 1.0 / (s * s);
             f_out = info0;
-            const int cx = carry_cell(e.x, A.cell, A.gw), cy = carry_cell(e.y, A.cell, A.gh);
+            const int cx = grid_cell(e.x, A.cell, A.gw), cy = grid_cell(e.y, A.cell, A.gh);
             if (start && cx >= 0 && cy >= 0)
             {
                 double best_d2 = INFINITY;
@@ -185,7 +153,7 @@ __global__ __launch_bounds__(256) void carry_gather_kernel(FinalCalib C, CarryAr
                 const double lm = G[2] / S.zp[best_i];
                 const double c = lm * S.a[best_i];
                 const double im = (A.carry * S.info[best_i]) / (c * c);
-                bool ok = carry_finite(im) && im > 0.0;
+                bool ok = finite_value(im) && im > 0.0;
                 if (ok)
                 {
                     const double d = lm - 1.0;
@@ -215,13 +183,12 @@ __global__ __launch_bounds__(256) void carry_gather_kernel(FinalCalib C, CarryAr
         src[m] = best_i;
     }
     const int lane = threadIdx.x & 63;
-    carry_count(n_dead, lane, &counts[2]);
-    carry_count(n_assoc, lane, &counts[3]);
-    carry_count(n_carried, lane, &counts[4]);
-    carry_count(n_gated, lane, &counts[5]);
+    wave_count(n_dead, lane, &counts[2]);
+    wave_count(n_assoc, lane, &counts[3]);
+    wave_count(n_carried, lane, &counts[4]);
+    wave_count(n_gated, lane, &counts[5]);
 }
 
-inline size_t cy64(size_t v) { return (v + 63) & ~(size_t)63; }
 } // namespace
 
 int carry_run(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_oldL, const ebvo_edge *d_oldR, int n_old, const double *d_lam_in,
@@ -234,9 +201,9 @@ int carry_run(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_oldL, const ebvo_edge *
     const int gw = (int)(((int64_t)img_w + cell - 1) / cell), gh = (int)(((int64_t)img_h + cell - 1) / cell), n_cells = gw * gh;
     const size_t no = assoc ? (size_t)n_old : 0;
     // the counters, the projections, their four planes, the grid
-    const size_t o_cnt = 0, o_proj = cy64(sizeof(int32_t) * CARRY_COUNTS), o_zp = o_proj + cy64(sizeof(ebvo_edge) * no),
-                 o_a = o_zp + cy64(8 * no), o_info = o_a + cy64(8 * no), o_nobs = o_info + cy64(8 * no), o_grid = o_nobs + cy64(4 * no),
-                 total = o_grid + (assoc ? cy64(sizeof(int32_t) * align_grid_ints(n_old, n_cells)) : 0);
+    const size_t o_cnt = 0, o_proj = round_up64(sizeof(int32_t) * CARRY_COUNTS), o_zp = o_proj + round_up64(sizeof(ebvo_edge) * no),
+                 o_a = o_zp + round_up64(8 * no), o_info = o_a + round_up64(8 * no), o_nobs = o_info + round_up64(8 * no), o_grid = o_nobs + round_up64(4 * no),
+                 total = o_grid + (assoc ? round_up64(sizeof(int32_t) * align_grid_ints(n_old, n_cells)) : 0);
     if (int rc = ebvo_grow(ctx, s, s.carry_ws, total))
         return rc;
     char *base = (char *)s.carry_ws.p;

@@ -6,7 +6,7 @@
 //   depth_update_kernel   one thread per mate, everything in registers: the prior or the incoming state, both cameras' terms
 //                         at the incoming lambda, liveness and gate, `iterations` Gauss-Newton steps in one unknown, accept or
 //                         restore.  A workgroup walks whole tiles of 1024 mates, so that the two squared residuals of its mates
-//                         go through the alignment's trees (64-lane halving tree, 16 group sums through LDS) into the tile's
+//                         go through ebvo_gn6.h's trees (64-lane halving tree, 16 group sums through LDS) into the tile's
 //                         two sums; the counts are wave sums of integers and one atomic per wave and counter
 //   depth_finish_kernel   one thread: the tiles in ascending order from +0.0, the two rms values, the record
 // The pose, the calibration and the parameters are kernel arguments.  No host read between the launches, no spin-wait, no
@@ -20,6 +20,7 @@
 #include "ebvo_internal.h"
 #include "ebvo_math.h"
 #include "ebvo_geom.h"
+#include "ebvo_gn6.h"
 
 namespace
 {
@@ -34,15 +35,12 @@ struct DepthArgs
     int32_t n_kf, cameras, iterations, tiles, n_e[2];
 };
 
-__device__ static inline bool depth_finite(double v) { return fabs(v) < INFINITY; }
-__device__ static inline bool depth_live_mate(const double *G) { return depth_finite(G[0]) && depth_finite(G[1]) && depth_finite(G[2]) && G[2] > 0.0; }
-
 __global__ __launch_bounds__(256) void depth_scale_kernel(double *__restrict__ GT, int n, const double *__restrict__ lam)
 {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
     {
         const double G[3] = {GT[i], GT[(size_t)n + i], GT[2 * (size_t)n + i]};
-        if (!depth_live_mate(G))
+        if (!live_mate(G))
             continue;
         const double l = lam[i];
 #pragma unroll
@@ -81,31 +79,10 @@ __device__ static inline DepthEdge depth_edge(const ebvo_edge *__restrict__ E, i
 __device__ static inline void depth_camera(const double *K, const double *Rs, const double *Y, const double *RG, double lam, const DepthEdge &e,
                                            double &r, double &j, double &pix, double &piy)
 {
-    double p[3];
-    mv3(K, Y, p);
-    pix = p[0] / p[2];
-    piy = p[1] / p[2];
-    r = e.n0 * (pix - e.ex) + e.n1 * (piy - e.ey);
-    const double ip = 1.0 / p[2];
     double jx[3], jy[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-    {
-        jx[k] = ip * (K[k] - pix * K[6 + k]);
-        jy[k] = ip * (K[3 + k] - piy * K[6 + k]);
-    }
-    if (Rs)
-    {
-        double a[3], b[3];
-        mtv3(Rs, jx, a);
-        mtv3(Rs, jy, b);
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-        {
-            jx[k] = a[k];
-            jy[k] = b[k];
-        }
-    }
+    const double pz = camera_pixel(K, Y, pix, piy);
+    r = e.n0 * (pix - e.ex) + e.n1 * (piy - e.ey);
+    camera_rows(K, Rs, pz, pix, piy, jx, jy);
     double m[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k)
@@ -119,10 +96,7 @@ __device__ static inline void depth_eval(const DepthArgs &A, const double *G, do
 {
     const double Gs[3] = {G[0] / lam, G[1] / lam, G[2] / lam};
     double RG[3], X[3];
-    mv3(A.Rt, Gs, RG);
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-        X[k] = RG[k] + A.Rt[9 + k];
+    pose_point(A.Rt, A.Rt + 9, Gs, RG, X);
     r[0] = r[1] = j[0] = j[1] = pix[0] = pix[1] = piy[0] = piy[1] = yz[0] = yz[1] = 0.0;
     if (e0.has)
     {
@@ -132,38 +106,10 @@ __device__ static inline void depth_eval(const DepthArgs &A, const double *G, do
     if (e1.has)
     {
         double Y[3];
-        mv3(A.R21, X, Y);
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            Y[k] = Y[k] + A.T21[k];
+        stereo_point(A.R21, A.T21, X, Y);
         depth_camera(A.Kr, A.R21, Y, RG, lam, e1, r[1], j[1], pix[1], piy[1]);
         yz[1] = Y[2];
     }
-}
-
-// x of every lane of a wave -> *slot by the halving tree x[l] += x[l + s], s = 32 .. 1 (align_kernels.hip: align_wave_sum)
-__device__ static inline void depth_wave_sum(double x, int lane, double *slot)
-{
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1)
-        x = x + __shfl_down(x, s);
-    if (lane == 0)
-        *slot = x;
-}
-
-// the 16 group sums by the same tree, s = 8 .. 1 (align_group_sum)
-__device__ static inline double depth_group_sum(const double *part)
-{
-    double g[DP_GROUPS];
-#pragma unroll
-    for (int k = 0; k < DP_GROUPS; ++k)
-        g[k] = part[k];
-#pragma unroll
-    for (int s = DP_GROUPS / 2; s >= 1; s >>= 1)
-#pragma unroll
-        for (int l = 0; l < s; ++l)
-            g[l] = g[l] + g[l + s];
-    return g[0];
 }
 
 // Workgroup b walks tiles b, b + gridDim.x, ...  A block of 256 or 512 threads owns lanes v, v + blockDim, ...: a wave always
@@ -198,7 +144,7 @@ __global__ __launch_bounds__(DP_TILE) void depth_update_kernel(DepthArgs A, cons
                 double l_out = l_in, f_out = f_in;
                 int o_out = o_in;
                 unsigned fl;
-                if (!depth_live_mate(G))
+                if (!live_mate(G))
                 {
                     fl = EBVO_DEPTH_DEAD;
                     ++cnt[0];
@@ -233,7 +179,7 @@ __global__ __launch_bounds__(DP_TILE) void depth_update_kernel(DepthArgs A, cons
                             for (int c = 0; c < 2; ++c)
                             {
                                 const bool has = c ? e1.has : e0.has;
-                                const bool live = has && pix[c] > A.margin && piy[c] > A.margin && pix[c] < A.x_max && piy[c] < A.y_max && yz[c] > 0.0;
+                                const bool live = has && live_projection(pix[c], piy[c], yz[c], A.margin, A.x_max, A.y_max);
                                 const double rho = fabs(r[c]);
                                 surv[c] = live && rho <= A.gate && rho < INFINITY;
                                 if (live && !surv[c])
@@ -252,7 +198,7 @@ __global__ __launch_bounds__(DP_TILE) void depth_update_kernel(DepthArgs A, cons
                             if (surv[c])
                             {
                                 const double rho = fabs(r[c]);
-                                const double w = rho <= A.huber ? 1.0 : A.huber / rho;
+                                const double w = huber_weight(rho, A.huber);
                                 Sh = Sh + w * (j[c] * j[c]);
                                 Sg = Sg + w * (j[c] * r[c]);
                             }
@@ -262,7 +208,7 @@ __global__ __launch_bounds__(DP_TILE) void depth_update_kernel(DepthArgs A, cons
                         const double g = f_in * (lam - l_in) + Sg * A.iv;
                         lam = lam - g / h;
                     }
-                    const bool accept = depth_finite(lam) && lam >= A.lam_min && lam <= A.lam_max && (surv[0] || surv[1]) && depth_finite(h);
+                    const bool accept = finite_value(lam) && lam >= A.lam_min && lam <= A.lam_max && (surv[0] || surv[1]) && finite_value(h);
                     if (accept)
                     {
                         l_out = lam;
@@ -284,24 +230,17 @@ __global__ __launch_bounds__(DP_TILE) void depth_update_kernel(DepthArgs A, cons
                 nobs_out[i] = o_out;
                 flags[i] = (uint8_t)fl;
             }
-            depth_wave_sum(sq_b, lane, &part[0][v >> 6]);
-            depth_wave_sum(sq_a, lane, &part[1][v >> 6]);
+            wave_sum(sq_b, lane, &part[0][v >> 6]);
+            wave_sum(sq_a, lane, &part[1][v >> 6]);
         }
         __syncthreads();
         if (tid < 2)
-            tile_sums[2 * (size_t)tile + tid] = depth_group_sum(part[tid]);
+            tile_sums[2 * (size_t)tile + tid] = group_sum<DP_GROUPS>(part[tid], 1, 0);
         __syncthreads(); // part is written again by the next tile
     }
 #pragma unroll
     for (int k = 0; k < DP_COUNTS; ++k)
-    {
-        int c = cnt[k];
-#pragma unroll
-        for (int s = 32; s >= 1; s >>= 1)
-            c += __shfl_down(c, s);
-        if (lane == 0 && c)
-            atomicAdd(&counts[k], c);
-    }
+        wave_count(cnt[k], lane, &counts[k]);
 }
 
 __global__ __launch_bounds__(64) void depth_finish_kernel(int tiles, const double *__restrict__ tile_sums, const int32_t *__restrict__ counts,
@@ -327,8 +266,6 @@ __global__ __launch_bounds__(64) void depth_finish_kernel(int tiles, const doubl
     rec->n_gated[1] = counts[6];
     rec->pad = 0;
 }
-
-inline size_t dp64(size_t v) { return (v + 63) & ~(size_t)63; }
 } // namespace
 
 void depth_scale_enqueue(const Slot &s, double *d_gt, int n_kf, const double *d_lambda)
@@ -346,8 +283,8 @@ int depth_run(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d
     const int tiles = (n_kf + DP_TILE - 1) / DP_TILE;
     const size_t n = (size_t)n_kf;
     // the record, the seven counters, the tile sums, then the six planes
-    const size_t o_rec = 0, o_cnt = dp64(sizeof(DepthRecord)), o_tiles = o_cnt + dp64(sizeof(int32_t) * DP_COUNTS),
-                 o_gt = o_tiles + dp64(sizeof(double) * 2 * (size_t)tiles), total = o_gt + dp64(sizeof(double) * 6 * n);
+    const size_t o_rec = 0, o_cnt = round_up64(sizeof(DepthRecord)), o_tiles = o_cnt + round_up64(sizeof(int32_t) * DP_COUNTS),
+                 o_gt = o_tiles + round_up64(sizeof(double) * 2 * (size_t)tiles), total = o_gt + round_up64(sizeof(double) * 6 * n);
     if (int rc = ebvo_grow(ctx, s, s.depth_ws, total))
         return rc;
     char *base = (char *)s.depth_ws.p;

@@ -4,7 +4,10 @@
  * (tgt_kernels.hip): Gamma from
  * Utility::backproject_2D_point_to_3D_point_using_rays and T from reconstruct_3D_Tangent_through_intersection_of_planes
  * (src/utility.cpp:95-112).  The calibration inverses are formed once on the host (Eigen's cofactor inverse, restated),
- * every product / cross / normalize in Eigen's fixed-size order.  Compiled with -ffp-contract=off (no FMA).
+ * every product / cross / normalize in Eigen's fixed-size order.  Its second half is a keyframe mate under a relative pose:
+ * the reprojection, its Jacobian rows, the Huber function, the image and liveness tests and the grid cell that the pose
+ * refit, the edge alignment, the inverse-depth filter, the depth carry and the temporal ground truth share.
+ * Compiled with -ffp-contract=off (no FMA).
  */
 #ifndef EBVO_GEOM_H
 #define EBVO_GEOM_H
@@ -91,16 +94,137 @@ __device__ static inline void stereo_gamma_tangent(const FinalCalib &C, const eb
     G[2] = rho1 * g1[2];
 }
 
+// ---- a keyframe mate under a pose -------------------------------------------------------------------------------------
+// What the inlier refit (pose_refit_kernels.hip), the edge alignment (align_kernels.hip), the inverse-depth filter
+// (depth_kernels.hip), the depth carry (carry_kernels.hip) and the temporal ground truth and prior (tgt_kernels.hip) share.
+// The operation order of every function is part of their arithmetic contracts (include/ebvo_hip.h): each CPU oracle
+// (tests/oracle_*.py) restates it and the device matches bit for bit, so a change here changes all of them together.
+
+// RG = R Gamma and X = RG + t: the mate in the left camera of the current frame
+__device__ static inline void pose_point(const double *R, const double *t, const double *G, double *RG, double *X)
+{
+    mv3(R, G, RG);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        X[i] = RG[i] + t[i];
+}
+// Y = R21 X + T21: the same point in the right camera
+__device__ static inline void stereo_point(const double *R21, const double *T21, const double *X, double *Y)
+{
+    mv3(R21, X, Y);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        Y[i] = Y[i] + T21[i];
+}
+
+// pi(Y) = (K Y)_xy / (K Y)_z; the return value is (K Y)_z, which camera_rows takes
+__device__ static inline double camera_pixel(const double *K, const double *Y, double &pix, double &piy)
+{
+    double p[3];
+    mv3(K, Y, p);
+    pix = p[0] / p[2];
+    piy = p[1] / p[2];
+    return p[2];
+}
+// the two rows of d pi / d Y at that pixel, times Rs (R21 for the right camera; NULL for the identity).  A caller forms its
+// residual between camera_pixel and this: the rows are not live while the residual and its weight are computed.
+__device__ static inline void camera_rows(const double *K, const double *Rs, double pz, double pix, double piy, double *jx, double *jy)
+{
+    const double ip = 1.0 / pz;
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+    {
+        jx[j] = ip * (K[j] - pix * K[6 + j]);
+        jy[j] = ip * (K[3 + j] - piy * K[6 + j]);
+    }
+    if (Rs)
+    {
+        double a[3], b[3];
+        mtv3(Rs, jx, a); // row . R21
+        mtv3(Rs, jy, b);
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+        {
+            jx[j] = a[j];
+            jy[j] = b[j];
+        }
+    }
+}
+
+// Huber at delta on rho >= 0: the weight of the reweighted least squares and the cost
+__device__ static inline double huber_weight(double rho, double delta) { return rho <= delta ? 1.0 : delta / rho; }
+__device__ static inline double huber_cost(double rho, double delta)
+{
+    return rho <= delta ? (rho * rho) * 0.5 : delta * (rho - delta * 0.5);
+}
+
+// K * G, then `/= z` (src/Temporal_Matches.cpp:84-85): the three components by the z the product gave
+__device__ static inline void project3(const double *K, const double *G, double *p)
+{
+    mv3(K, G, p);
+    const double z = p[2];
+    p[0] /= z;
+    p[1] /= z;
+    p[2] /= z;
+}
+// orientation_mapping (src/Temporal_Matches.cpp:294-333) from T_2: the projected point over its own z, the ray K^-1 gamma,
+// the projected tangent
+__device__ static inline double mapped_orientation(const double *T2, const double *p, const double *Kinv)
+{
+    const double g[3] = {p[0] / p[2], p[1] / p[2], p[2] / p[2]};
+    double ray[3], t2d[3];
+    mv3(Kinv, g, ray);
+    project_tangent3(T2, ray, t2d);
+    return ebvo_atan2(t2d[1], t2d[0]);
+}
+
+// strictly inside the margin (a NaN or infinite coordinate is not), and that in front of the camera
+__device__ static inline bool inside_margin(double x, double y, double margin, double x_max, double y_max)
+{
+    return x > margin && y > margin && x < x_max && y < y_max;
+}
+__device__ static inline bool live_projection(double x, double y, double z, double margin, double x_max, double y_max)
+{
+    return inside_margin(x, y, margin, x_max, y_max) && z > 0.0;
+}
+
+__device__ static inline bool finite_value(double v) { return fabs(v) < INFINITY; }
+// a mate whose depth can be refined or carried: Gamma finite and in front of the keyframe's left camera
+__device__ static inline bool live_mate(const double *G)
+{
+    return finite_value(G[0]) && finite_value(G[1]) && finite_value(G[2]) && G[2] > 0.0;
+}
+
+// (int)v / cell inside [0, n_cells), or -1.  The comparison is made on the double, so that NaN and +-inf are in no cell and
+// the cast is defined: (int)v / cell >= 0 iff v > -cell, < n_cells iff v < n_cells * cell
+__device__ static inline int grid_cell(double v, int cell, int n_cells)
+{
+    if (!(v > -(double)cell && v < (double)n_cells * (double)cell))
+        return -1;
+    return (int)v / cell;
+}
+
+// the row of quad k in the CSR offsets rp [n_kf + 1]: the last i with rp[i] <= k (rp[0] = 0)
+__device__ static inline int quad_row(const int32_t *__restrict__ rp, int n_kf, int k)
+{
+    int lo = 0, hi = n_kf - 1;
+    while (lo < hi)
+    {
+        const int mid = (lo + hi + 1) >> 1;
+        if (rp[mid] <= k)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    return lo;
+}
+
 // score_Pose_Hypothesis for one quad: cv::norm(K (R Gamma + t) / z - left centre) < thr
 __device__ static inline bool pose_inlier(const double *Rt, const double *K, const double *G, double ux, double uy, double thr)
 {
-    double h[3], p[3];
-    mv3(Rt, G, h);
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        h[i] = h[i] + Rt[9 + i];
-    mv3(K, h, p);
-    const double x = p[0] / p[2], y = p[1] / p[2];
+    double RG[3], h[3], x, y;
+    pose_point(Rt, Rt + 9, G, RG, h);
+    camera_pixel(K, h, x, y);
     const double dx = x - ux, dy = y - uy;
     return sqrt(dx * dx + dy * dy) < thr;
 }

@@ -455,6 +455,9 @@ __device__ inline int64_t devcount(const DevCount &c)
             return ebvo_fail_hip((ctx), e_, #call, __FILE__, __LINE__);  \
     } while (0)
 
+// the next multiple of 64 bytes: where the next array of a carved workspace starts
+inline size_t round_up64(size_t v) { return (v + 63) & ~(size_t)63; }
+
 // grow a slot buffer (synchronises the slot's stream before freeing the old allocation)
 int ebvo_grow(ebvo_ctx *ctx, Slot &s, GrowBuf &b, size_t bytes);
 

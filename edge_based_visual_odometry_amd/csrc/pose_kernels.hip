@@ -50,15 +50,7 @@ __global__ void pose_prepare_kernel(FinalCalib C, const ebvo_edge *__restrict__ 
 {
     for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += gridDim.x * blockDim.x)
     {
-        int lo = 0, hi = n_kf - 1; // the row of quad k: the last i with rp[i] <= k (rp[0] = 0)
-        while (lo < hi)
-        {
-            const int mid = (lo + hi + 1) >> 1;
-            if (rp[mid] <= k)
-                lo = mid;
-            else
-                hi = mid - 1;
-        }
+        const int lo = quad_row(rp, n_kf, k);
         double G[3], Gb[3], T[3], Tb[3], g1[3], g2[3];
         stereo_gamma_tangent(C, kfL[lo], kfR[lo], G, T, g1, g2);
         const ebvo_edge cl = cfL[k];

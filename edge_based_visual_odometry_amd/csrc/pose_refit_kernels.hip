@@ -41,15 +41,7 @@ __global__ void pose_refit_prepare_kernel(FinalCalib C, const ebvo_edge *__restr
 {
     for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += gridDim.x * blockDim.x)
     {
-        int lo = 0, hi = n_kf - 1; // the row of quad k: the last i with rp[i] <= k (rp[0] = 0)
-        while (lo < hi)
-        {
-            const int mid = (lo + hi + 1) >> 1;
-            if (rp[mid] <= k)
-                lo = mid;
-            else
-                hi = mid - 1;
-        }
+        const int lo = quad_row(rp, n_kf, k);
         double G[3], T[3], g1[3], g2[3];
         stereo_gamma_tangent(C, kfL[lo], kfR[lo], G, T, g1, g2);
         const ebvo_edge cl = cfL[k], cr = cfR[k];
@@ -73,36 +65,15 @@ struct RefitCam
 __device__ static inline void refit_camera(const double *K, const double *Y, const double *RG, const double *Rs, double cx, double cy,
                                            double delta, RefitCam &o)
 {
-    double p[3];
-    mv3(K, Y, p);
-    const double pix = p[0] / p[2], piy = p[1] / p[2];
+    double pix, piy, jx[3], jy[3];
+    const double pz = camera_pixel(K, Y, pix, piy);
     o.rx = pix - cx;
     o.ry = piy - cy;
     const double rho = sqrt(o.rx * o.rx + o.ry * o.ry);
     o.valid = rho < INFINITY;
-    const bool small = rho <= delta;
-    o.w = small ? 1.0 : delta / rho;
-    o.cost = small ? (rho * rho) * 0.5 : delta * (rho - delta * 0.5);
-    const double ip = 1.0 / p[2];
-    double jx[3], jy[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-    {
-        jx[j] = ip * (K[j] - pix * K[6 + j]);
-        jy[j] = ip * (K[3 + j] - piy * K[6 + j]);
-    }
-    if (Rs)
-    {
-        double a[3], b[3];
-        mtv3(Rs, jx, a); // row . R21
-        mtv3(Rs, jy, b);
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-        {
-            jx[j] = a[j];
-            jy[j] = b[j];
-        }
-    }
+    o.w = huber_weight(rho, delta);
+    o.cost = huber_cost(rho, delta);
+    camera_rows(K, Rs, pz, pix, piy, jx, jy);
     cross3(RG, jx, o.Jx); // m . -[R Gamma]x = R Gamma x m
     cross3(RG, jy, o.Jy);
 #pragma unroll
@@ -118,14 +89,8 @@ __device__ static inline void refit_accumulate(const RefitArgs &A, const double 
                                                double by, double *acc)
 {
     double RG[3], X[3], Y[3];
-    mv3(Rt, G, RG);
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        X[i] = RG[i] + Rt[9 + i];
-    mv3(A.R21, X, Y);
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        Y[i] = Y[i] + A.T21[i];
+    pose_point(Rt, Rt + 9, G, RG, X);
+    stereo_point(A.R21, A.T21, X, Y);
     RefitCam L, R;
     refit_camera(A.K, X, RG, nullptr, ux, uy, A.huber, L);
     refit_camera(A.K, Y, RG, A.R21, bx, by, A.huber, R);
@@ -185,65 +150,6 @@ struct RefitState
     double c_first, c_last, c_prev;
     int32_t status, stop, rounds_run, steps, fitn, go;
 };
-
-// what follows the 28 sums of step `it` of round `rnd`; go = 0 ends the round
-__device__ static inline void refit_decide(const RefitArgs &A, int rnd, int it, const double *sums, RefitState &st)
-{
-    const double cost = sums[27];
-    st.go = 0;
-    if (it == 0)
-        st.c_first = cost;
-    if (it > 0 && !(cost <= st.c_prev)) // the cost rose (a NaN counts as larger): back to the pose before
-    {
-#pragma unroll
-        for (int i = 0; i < 12; ++i)
-            st.Rt[i] = st.Pv[i];
-        --st.steps;
-        st.stop = 2;
-        return;
-    }
-    st.c_last = cost;
-    if (it == A.iterations)
-    {
-        st.stop = 1;
-        return;
-    }
-    double d[6];
-    if (!refit_solve(sums, d))
-    {
-        st.stop = 3;
-        if (rnd == 0 && it == 0)
-            st.status = 2;
-        return;
-    }
-    double Rt[12];
-#pragma unroll
-    for (int i = 0; i < 12; ++i)
-        st.Pv[i] = Rt[i] = st.Rt[i];
-    st.c_prev = cost;
-    refit_rotate(d, Rt);
-    double m = 0.0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        Rt[9 + i] = Rt[9 + i] + d[3 + i];
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-    {
-        const double a = fabs(d[i]);
-        if (a > m)
-            m = a;
-    }
-#pragma unroll
-    for (int i = 0; i < 12; ++i)
-        st.Rt[i] = Rt[i];
-    ++st.steps;
-    if (m < A.eps)
-    {
-        st.stop = 0;
-        return;
-    }
-    st.go = 1;
-}
 
 // fit: n bytes of scratch (the fit set of the round); mask: the inliers of the returned pose, at map[k] (or k)
 __global__ __launch_bounds__(RF_LANES) void pose_refit_kernel(RefitArgs A, const double *__restrict__ pts, const int32_t *__restrict__ map,
@@ -309,32 +215,14 @@ __global__ __launch_bounds__(RF_LANES) void pose_refit_kernel(RefitArgs A, const
                 }
 #pragma unroll
                 for (int i = 0; i < RF_SUMS; ++i)
-                {
-                    double x = acc[i];
-#pragma unroll
-                    for (int s = 32; s >= 1; s >>= 1) // lane 0 ends with the halving tree x[l] += x[l + s], l < s
-                        x = x + __shfl_down(x, s);
-                    if (lane == 0)
-                        part[(v >> 6) * RF_SUMS + i] = x;
-                }
+                    wave_sum(acc[i], lane, &part[(v >> 6) * RF_SUMS + i]);
             }
             __syncthreads();
             if (tid < RF_SUMS)
-            {
-                double g[RF_GROUPS];
-#pragma unroll
-                for (int j = 0; j < RF_GROUPS; ++j)
-                    g[j] = part[j * RF_SUMS + tid];
-#pragma unroll
-                for (int s = RF_GROUPS / 2; s >= 1; s >>= 1)
-#pragma unroll
-                    for (int l = 0; l < s; ++l)
-                        g[l] = g[l] + g[l + s];
-                sums[tid] = g[0];
-            }
+                sums[tid] = group_sum<RF_GROUPS>(part, RF_SUMS, tid);
             __syncthreads();
-            if (tid == 0)
-                refit_decide(A, rnd, it, sums, st);
+            if (tid == 0) // go = 0 ends the round
+                gn6_decide(rnd, it, A.iterations, A.eps, sums, st);
             __syncthreads();
             if (!st.go)
                 break;
@@ -366,8 +254,7 @@ int pose_refit_device(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo
                       PoseRefitOut *res, uint8_t *inlier)
 {
     const size_t nz = (size_t)n, fz = (size_t)n_full;
-    const size_t o_fit = sizeof(double) * RF_PLANES * nz, o_mask = o_fit + ((nz + 63) & ~(size_t)63),
-                 o_out = o_mask + ((fz + 63) & ~(size_t)63);
+    const size_t o_fit = sizeof(double) * RF_PLANES * nz, o_mask = o_fit + round_up64(nz), o_out = o_mask + round_up64(fz);
     if (int rc = ebvo_grow(ctx, s, s.pose_refit, o_out + sizeof(PoseRefitOut)))
         return rc;
     char *base = (char *)s.pose_refit.p;

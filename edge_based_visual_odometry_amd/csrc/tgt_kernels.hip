@@ -31,29 +31,10 @@ struct TgtPose
     FinalCalib C;   // K_left^-1, K_right^-1, R21, T21
 };
 
-// K * G, then `/= z` (:84-85): the three components by the z the product gave
-__device__ inline void project3(const double *K, const double *G, double *p)
-{
-    mv3(K, G, p);
-    const double z = p[2];
-    p[0] /= z;
-    p[1] /= z;
-    p[2] /= z;
-}
-
-// orientation_mapping (:294-333) from T_2: the projected point over its own z, the ray K^-1 gamma, the projected tangent
-__device__ inline double mapped_orientation(const double *T2, const double *p, const double *Kinv)
-{
-    const double g[3] = {p[0] / p[2], p[1] / p[2], p[2] / p[2]};
-    double ray[3], t2d[3];
-    mv3(Kinv, g, ray);
-    project_tangent3(T2, ray, t2d);
-    return ebvo_atan2(t2d[1], t2d[0]);
-}
-
 // :82-105 for one keyframe mate: both projections (over their own z), both mapped orientations and the two camera-frame
 // points.  Shared by tgt_project_kernel and tprior_project_kernel, so that the prior stage searches at exactly the points
-// the ground truth evaluates.
+// the ground truth evaluates.  The pose step, project3 (:84-85) and mapped_orientation (:294-333) are ebvo_geom.h's, which
+// the alignment and the depth carry project with too.
 struct MateProjection
 {
     double ql[3], qr[3], ol, orr, Gc[3], Gr[3];
@@ -69,16 +50,10 @@ __device__ inline void project_mate(const TgtPose &P, const ebvo_edge &kl, const
         G[1] = gamma_i[1];
         G[2] = gamma_i[2];
     }
-    double T2l[3], T2r[3];
-    mv3(P.R, G, m.Gc); // :83
-    m.Gc[0] += P.t[0];
-    m.Gc[1] += P.t[1];
-    m.Gc[2] += P.t[2];
+    double RG[3], T2l[3], T2r[3];
+    pose_point(P.R, P.t, G, RG, m.Gc); // :83
     project3(P.Kl, m.Gc, m.ql);
-    mv3(P.C.R21, m.Gc, m.Gr); // :87
-    m.Gr[0] += P.C.T21[0];
-    m.Gr[1] += P.C.T21[1];
-    m.Gr[2] += P.C.T21[2];
+    stereo_point(P.C.R21, P.C.T21, m.Gc, m.Gr); // :87
     project3(P.Kr, m.Gr, m.qr);
     mv3(P.R, T1, T2l);    // :317
     mv3(P.R21R, T1, T2r); // :321
@@ -90,8 +65,7 @@ __device__ inline void project_mate(const TgtPose &P, const ebvo_edge &kl, const
 // reference would cast it to an int, which is undefined); neither is an infinite one.
 __device__ inline bool projections_inside(const MateProjection &m, double margin, double x_max, double y_max)
 {
-    return m.ql[0] > margin && m.ql[1] > margin && m.ql[0] < x_max && m.ql[1] < y_max && m.qr[0] > margin && m.qr[1] > margin &&
-           m.qr[0] < x_max && m.qr[1] < y_max;
+    return inside_margin(m.ql[0], m.ql[1], margin, x_max, y_max) && inside_margin(m.qr[0], m.qr[1], margin, x_max, y_max);
 }
 
 // :82-105 per keyframe mate.  The orientations are computed before the margin test, as there.

@@ -1001,7 +1001,7 @@ int ebvo_pose_align_edges_depth(ebvo_ctx *ctx, const ebvo_edge *kf_left, const e
  *   > 0): lambda 1.0, info +0.0, n_obs 0, flag EBVO_DEPTH_DEAD, src_index -1.  A live mate's prior is the filter's:
  *   b = sqrt(dot3(T21, T21)), s' = (sigma_disp_px Gamma'_z) / (K_left[0] b), info0' = 1.0 / (s' s').
  * Association (a gather: the new mate looks for old projections, so no two sources ever write the same state).  The grid is
- *   the alignment's (cell_size; a projection is in cell ((int)q_x / cell_size, (int)q_y / cell_size) by align_cell's rule),
+ *   the alignment's (cell_size; a projection is in cell ((int)q_x / cell_size, (int)q_y / cell_size) by grid_cell's rule),
  *   built over the live sources' projections.  With e = new_left[m]: the candidates of a live mate m are the live sources i
  *   in the cells within ceil(radius / cell_size) of e's cell (by the same rule; a mate whose e.x or e.y is in no cell has no
  *   candidate), clipped to the grid, with
