@@ -1168,9 +1168,9 @@ __device__ inline ColMask column_mask(int w, int j)
 // `fast`: wave-uniform promise that the whole 19 x 19 window of every lane lies inside the image (no masking).
 // Otherwise the five words are masked BEFORE the bytes are taken apart (ten instructions a row): selecting per byte
 // cost one instruction per pixel on both paths (the unmasked path paid them as register copies where the two paths merge).
-__device__ inline void unpack_row(const Row24 &r, int h, int ii, const ColMask &cm, bool fast, int v[19])
+__device__ inline void mask_row(const Row24 &r, int h, int ii, const ColMask &cm, bool fast, unsigned d[5])
 {
-    unsigned d[5] = {(unsigned)r.w0, (unsigned)(r.w0 >> 32), (unsigned)r.w1, (unsigned)(r.w1 >> 32), (unsigned)r.w2};
+    d[0] = (unsigned)r.w0, d[1] = (unsigned)(r.w0 >> 32), d[2] = (unsigned)r.w1, d[3] = (unsigned)(r.w1 >> 32), d[4] = (unsigned)r.w2;
     if (!fast)
     {
         const bool rok = ii >= 0 && ii < h;
@@ -1178,6 +1178,21 @@ __device__ inline void unpack_row(const Row24 &r, int h, int ii, const ColMask &
         for (int k = 0; k < 5; ++k)
             d[k] = rok ? (d[k] & cm.m[k]) : 0u;
     }
+}
+
+// tap q of a masked row: byte 9 - q of the run.  The half-pixel phases take the byte apart where it is used: it goes
+// straight into the low word of ONE register pair whose high word stays zero (byte_as_subnormal).  Taken apart up
+// front (unpack_row) the 19 pairs of a row are live together and each gets a v_mov for its high word.
+__device__ inline int row_tap(const unsigned d[5], int q)
+{
+    const int k = 9 - q;
+    return (int)((d[k >> 2] >> (8 * (k & 3))) & 0xffu);
+}
+
+__device__ inline void unpack_row(const Row24 &r, int h, int ii, const ColMask &cm, bool fast, int v[19])
+{
+    unsigned d[5];
+    mask_row(r, h, ii, cm, fast, d);
 #pragma unroll
     for (int k = 0; k < 19; ++k) // byte k of the run is column j - 9 + k, i.e. tap q = 9 - k
         v[18 - k] = (int)((d[k >> 2] >> (8 * (k & 3))) & 0xffu);
@@ -1195,18 +1210,45 @@ __device__ inline bool window_inside(int h, int w, int i, int j)
 // Every lane of a wave reads the same address, so the reads are conflict-free broadcasts and the taps arrive as
 // vector operands: no SGPR file pressure (76 tap doubles do not fit it; they used to come back through
 // v_readlane), no scalar-load waits in the tap loop.
+//
+// Scaled copies for the three non-integer phases.  There a pixel enters the arithmetic only as
+// (v * ck) * rk.  The byte written into the low word of a register pair whose high word is zero IS the fp64 subnormal
+// v * 2^-1074, so with ctap = tap * 2^TAP_K1 and rtap = tap * 2^TAP_K2, TAP_K1 + TAP_K2 = 1074, the conversion of the
+// byte goes away and every term keeps its bits: fl(v 2^-1074 * ck 2^K1) = fl(v * ck) * 2^-K2 and the second product is
+// fl(fl(v * ck) * rk), exactly.  Two conditions on the split, both checked over the committed tables by
+// tests/test_exact_scaled_taps.py:
+//   (1) every scaled tap is finite (largest: 2.1e300 as a column tap);
+//   (2) every non-zero column product v 2^-1074 * ck 2^K1 is a normal number (smallest: 1.3e-28), so that its rounding
+//       sees the same 53-bit significand as fl(v * ck).
+// The scaling is an exact power-of-two multiply (ldexp).  The integer phase multiplies v by prod_fx / prod_fy directly
+// (prod * 2^1074 overflows): it keeps the conversion and the unscaled tables.
+constexpr int TAP_K1 = 1000, TAP_K2 = 74;
+static_assert(TAP_K1 + TAP_K2 == 1074, "a byte in the low word of a zero register pair is byte * 2^-1074");
 struct ExactTaps
 {
-    double tap[2][19][4];
+    // the column taps are read at constant offsets from the struct: the tables indexed that way come first, within the
+    // 2040 bytes an offset field of ds_read2_b64 reaches (further back every read pays an address add)
+    double ctap[2][19][4]; // tap * 2^TAP_K1: column role, non-integer phases
+    double tap[2][19][4];  // integer phase: only tap[0] is read at constant offsets
+    double rtap[2][19][4]; // tap * 2^TAP_K2: row role, non-integer phases
     double prod[17][17][2];
 };
+
+// a pixel byte as the fp64 subnormal byte * 2^-1074: no conversion instruction, the high word is a constant zero
+__device__ inline double byte_as_subnormal(int b)
+{
+    return __builtin_bit_cast(double, (unsigned long long)(unsigned)b);
+}
 
 __device__ inline void load_exact_taps(ExactTaps &L, const ToedTables *__restrict__ T)
 {
     for (int t = threadIdx.x; t < 2 * 19 * 4; t += blockDim.x)
     {
         const int half = t / 76, k = (t % 76) / 4, d = t & 3;
-        L.tap[half][k][d] = half ? T->tap_half[d][k] : T->tap_int[d][k];
+        const double v = half ? T->tap_half[d][k] : T->tap_int[d][k];
+        L.tap[half][k][d] = v;
+        L.ctap[half][k][d] = ldexp(v, TAP_K1);
+        L.rtap[half][k][d] = ldexp(v, TAP_K2);
     }
     for (int t = threadIdx.x; t < 17 * 17; t += blockDim.x)
     {
@@ -1222,8 +1264,8 @@ __device__ inline void exact9(const uint8_t *__restrict__ img, int h, int w, con
                               double f[9])
 {
     constexpr bool IP = (SY == 0 && SX == 0);
-    const double(*ck)[4] = L.tap[SX];
-    const double(*rk)[4] = L.tap[SY];
+    const double(*ck)[4] = IP ? L.tap[SX] : L.ctap[SX];
+    const double(*rk)[4] = IP ? L.tap[SY] : L.rtap[SY];
 #pragma unroll
     for (int r = 0; r < 9; ++r)
         f[r] = 0.0;
@@ -1237,7 +1279,11 @@ __device__ inline void exact9(const uint8_t *__restrict__ img, int h, int w, con
         const Row24 cur = nxt;
         nxt = fetch_row(img, h, w, i - min(p + 1, PM), j); // next row in flight while this one is accumulated
         int vb[19];
-        unpack_row(cur, h, i - p, cm, fast, vb);
+        unsigned dw[5];
+        if (IP)
+            unpack_row(cur, h, i - p, cm, fast, vb);
+        else
+            mask_row(cur, h, i - p, cm, fast, dw);
         double rr[4];
 #pragma unroll
         for (int d = 0; d < 4; ++d)
@@ -1245,7 +1291,7 @@ __device__ inline void exact9(const uint8_t *__restrict__ img, int h, int w, con
 #pragma unroll
         for (int q = -PM; q <= PM; ++q)
         {
-            const double v = (double)vb[q + 9];
+            const double v = IP ? (double)vb[q + 9] : byte_as_subnormal(row_tap(dw, q));
             // the column taps are re-read from LDS a few taps at a time: a laundered zero offset keeps the reads in the
             // row loop (hoisted, the 76 doubles would occupy 152 VGPRs and halve the occupancy)
             int lz = 0;
@@ -1282,8 +1328,8 @@ __device__ inline double exact_mag(const uint8_t *__restrict__ img, int h, int w
 {
     constexpr bool IP = (SY == 0 && SX == 0);
     const int i = I >> 1, j = J >> 1;
-    const double(*ck)[4] = L.tap[SX];
-    const double(*rk)[4] = L.tap[SY];
+    const double(*ck)[4] = IP ? L.tap[SX] : L.ctap[SX];
+    const double(*rk)[4] = IP ? L.tap[SY] : L.rtap[SY];
     double fx = 0.0, fy = 0.0;
     constexpr int PM = IP ? 8 : 9;
     const bool fast = __all(window_inside(h, w, i, j));
@@ -1295,7 +1341,11 @@ __device__ inline double exact_mag(const uint8_t *__restrict__ img, int h, int w
         const Row24 cur = nxt;
         nxt = fetch_row(img, h, w, i - min(p + 1, PM), j);
         int vb[19];
-        unpack_row(cur, h, i - p, cm, fast, vb);
+        unsigned dw[5];
+        if (IP)
+            unpack_row(cur, h, i - p, cm, fast, vb);
+        else
+            mask_row(cur, h, i - p, cm, fast, dw);
         const double r0 = rk[p + 9][0], r1 = rk[p + 9][1];
         int lz = 0;
         asm volatile("" : "+v"(lz)); // keeps the column-tap reads in the row loop (see exact9)
@@ -1303,7 +1353,7 @@ __device__ inline double exact_mag(const uint8_t *__restrict__ img, int h, int w
 #pragma unroll
         for (int q = -PM; q <= PM; ++q)
         {
-            const double v = (double)vb[q + 9];
+            const double v = IP ? (double)vb[q + 9] : byte_as_subnormal(row_tap(dw, q));
             if (IP)
             {
                 fx += v * L.prod[p + 8][q + 8][0];
