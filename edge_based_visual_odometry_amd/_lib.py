@@ -63,6 +63,9 @@ ABI_SYMBOLS = (
     "ebvo_depth_default_params", "ebvo_depth_refine_edges", "ebvo_temporal_refine_depth", "ebvo_temporal_depth_fetch",
     "ebvo_temporal_depth_reset", "ebvo_temporal_use_depth", "ebvo_pose_align_edges_depth",
     "ebvo_depth_carry_default_params", "ebvo_depth_carry", "ebvo_temporal_promote_keyframe", "ebvo_temporal_depth_source",
+    "ebvo_cover_default_params", "ebvo_keyframe_cover_edges", "ebvo_temporal_keyframe_cover", "ebvo_temporal_cover_size",
+    "ebvo_keyframe_policy_default",
+    "ebvo_keyframe_decide", "ebvo_temporal_keyframe_pose", "ebvo_track_default_params", "ebvo_temporal_track_frame",
 )
 
 
@@ -181,6 +184,40 @@ class DepthCarried(C.Structure):
 class DepthRefined(C.Structure):
     _fields_ = [("n_kf", C.c_int32), ("n_dead", C.c_int32), ("n_updated", C.c_int32), ("n_restored", C.c_int32),
                 ("n_terms", C.c_int32 * 2), ("n_gated", C.c_int32 * 2), ("rms_before", C.c_double), ("rms_after", C.c_double)]
+
+
+COVER_BINS = 64
+COVER_DEAD, COVER_IN_FRAME, COVER_ASSOCIATED, COVER_INLIER = 1, 2, 4, 8                          # flags of ebvo_keyframe_cover_edges
+KF_LOST, KF_LOW_OVERLAP, KF_LOW_ASSOC, KF_NEW_CONTENT, KF_PARALLAX = 1, 2, 4, 8, 16              # reasons of ebvo_keyframe_decide
+(TRACK_STAGE_NONE, TRACK_STAGE_ALIGN, TRACK_STAGE_DEPTH, TRACK_STAGE_COVER, TRACK_STAGE_FINALIZE, TRACK_STAGE_PROMOTE) = range(6)
+
+
+class CoverParams(C.Structure):
+    _fields_ = [("radius", C.c_double), ("orient_thr_deg", C.c_double), ("img_margin", C.c_double), ("inlier_px", C.c_double),
+                ("bin_px", C.c_double), ("cell_size", C.c_int32), ("cover_cell", C.c_int32), ("min_cell_edges", C.c_int32),
+                ("min_cell_explained", C.c_int32), ("reserved", C.c_int32), ("pad", C.c_int32)]
+
+
+class KeyframeCover(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("n_kf", "n_dead", "n_in_frame", "n_assoc", "n_inliers", "n_edges", "n_explained", "cw", "ch",
+                                         "n_cells_cur", "n_cells_covered", "disp_median_bin")] + [("hist", C.c_int32 * COVER_BINS)]
+
+
+class KeyframePolicy(C.Structure):
+    _fields_ = [("min_assoc", C.c_int32), ("max_disp_bins", C.c_int32), ("min_in_frame_share", C.c_double),
+                ("min_assoc_share", C.c_double), ("min_cell_cover", C.c_double)]
+
+
+class TrackParams(C.Structure):
+    _fields_ = [("align", AlignParams), ("depth", DepthParams), ("cover", CoverParams), ("carry", DepthCarryParams),
+                ("finalize", FinalizeParams), ("policy", KeyframePolicy), ("refine_depth", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TrackedFrame(C.Structure):
+    _fields_ = [("pose", AlignedPose), ("depth", DepthRefined), ("cover", KeyframeCover), ("carried", DepthCarried),
+                ("finalized", FinalizeCounts), ("R_seq", C.c_double * 9), ("t_seq", C.c_double * 3), ("reasons", C.c_uint32),
+                ("decision", C.c_int32), ("switched", C.c_int32), ("tracked", C.c_int32), ("failed_stage", C.c_int32),
+                ("pad", C.c_int32)]
 
 
 DEPTH_DEAD, DEPTH_UPDATED, DEPTH_RESTORED, DEPTH_GATED_LEFT, DEPTH_GATED_RIGHT = 1, 2, 4, 8, 16   # flags of one update
@@ -442,6 +479,27 @@ def load_library() -> C.CDLL:
                                                    C.POINTER(DepthCarried)]
     lib.ebvo_temporal_depth_source.restype = i32
     lib.ebvo_temporal_depth_source.argtypes = [vp, vp]
+    lib.ebvo_cover_default_params.restype = None
+    lib.ebvo_cover_default_params.argtypes = [C.POINTER(CoverParams)]
+    lib.ebvo_keyframe_cover_edges.restype = i32
+    lib.ebvo_keyframe_cover_edges.argtypes = [vp, vp, vp, vp, i32, vp, i32, i32, i32, C.POINTER(StereoCalib), C.POINTER(CoverParams), vp, vp,
+                                              C.POINTER(KeyframeCover), vp, vp, vp, vp, vp, vp]
+    lib.ebvo_temporal_keyframe_cover.restype = i32
+    lib.ebvo_temporal_keyframe_cover.argtypes = [vp, i32, C.POINTER(StereoCalib), C.POINTER(CoverParams), vp, vp, C.POINTER(KeyframeCover),
+                                                 vp, vp, vp, vp, vp, vp]
+    lib.ebvo_temporal_cover_size.restype = i32
+    lib.ebvo_temporal_cover_size.argtypes = [vp, i32, C.POINTER(CoverParams), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.ebvo_keyframe_policy_default.restype = None
+    lib.ebvo_keyframe_policy_default.argtypes = [C.POINTER(KeyframePolicy)]
+    lib.ebvo_keyframe_decide.restype = i32
+    lib.ebvo_keyframe_decide.argtypes = [C.POINTER(KeyframeCover), C.POINTER(KeyframePolicy), C.POINTER(C.c_uint32)]
+    lib.ebvo_temporal_keyframe_pose.restype = i32
+    lib.ebvo_temporal_keyframe_pose.argtypes = [vp, vp, vp]
+    lib.ebvo_track_default_params.restype = None
+    lib.ebvo_track_default_params.argtypes = [C.POINTER(TrackParams)]
+    lib.ebvo_temporal_track_frame.restype = i32
+    lib.ebvo_temporal_track_frame.argtypes = [vp, i32, C.POINTER(StereoCalib), C.POINTER(TrackParams), vp, vp, C.POINTER(TrackedFrame)]
     lib.ebvo_gt_default_params.restype = None
     lib.ebvo_gt_default_params.argtypes = [C.POINTER(GtParams)]
     lib.ebvo_stereo_set_gt.argtypes = [vp, i32, vp, i32, i32, ssz, C.POINTER(StereoCalib), C.POINTER(GtParams)]

@@ -1108,6 +1108,147 @@ class Context:
         self._check(self.lib.ebvo_temporal_depth_source(self._ctx, ptr(src)), "ebvo_temporal_depth_source")
         return src
 
+    # -- keyframe coverage, the switch policy and the frame step (the contract is in ebvo_hip.h) -------------------------------
+    @staticmethod
+    def _with(p, what: str, kw: dict):
+        fields = {name for name, _ in p._fields_}
+        for k, v in kw.items():
+            if k not in fields:
+                raise TypeError(f"{what}: unknown parameter {k!r}")
+            setattr(p, k, v)
+        return p
+
+    def cover_params(self, **kw) -> _lib.CoverParams:
+        """ebvo_cover_params: the defaults of ebvo_cover_default_params with `kw` applied."""
+        p = _lib.CoverParams()
+        self.lib.ebvo_cover_default_params(C.byref(p))
+        return self._with(p, "cover", kw)
+
+    def keyframe_policy(self, **kw) -> _lib.KeyframePolicy:
+        """ebvo_keyframe_policy: the defaults of ebvo_keyframe_policy_default with `kw` applied."""
+        p = _lib.KeyframePolicy()
+        self.lib.ebvo_keyframe_policy_default(C.byref(p))
+        return self._with(p, "keyframe policy", kw)
+
+    @staticmethod
+    def _cover_dict(r) -> dict:
+        out = {k: int(getattr(r, k)) for k, _ in r._fields_ if k != "hist"}
+        out["hist"] = np.array(r.hist[:], dtype=np.int32)
+        return out
+
+    @staticmethod
+    def _cover_record(cover) -> _lib.KeyframeCover:
+        r = _lib.KeyframeCover()
+        for k, _ in r._fields_:
+            if k == "hist":
+                for b, v in enumerate(np.asarray(cover.get("hist", np.zeros(_lib.COVER_BINS)), dtype=np.int64)):
+                    r.hist[b] = int(v)
+            else:
+                setattr(r, k, int(cover[k]))
+        return r
+
+    @staticmethod
+    def _cover_outputs(n_kf: int, n0: int, w: int, h: int, cover_cell: int, arrays: bool):
+        if not arrays:
+            return [None] * 6
+        nc = ((w + cover_cell - 1) // cover_cell) * ((h + cover_cell - 1) // cover_cell)
+        return [np.zeros(n_kf, dtype=np.uint8), np.full(n_kf, -1, dtype=np.int32), np.full(n_kf, np.nan), np.zeros(n0, dtype=np.uint8),
+                np.zeros(nc, dtype=np.int32), np.zeros(nc, dtype=np.int32)]
+
+    _COVER_ARRAYS = ("flags", "assoc", "disp", "explained", "cell_edges", "cell_explained")
+
+    def keyframe_cover_edges(self, kf_left, kf_right, cf_edges_left, img_w: int, img_h: int, calib, R, t, lambda_=None, arrays=True,
+                             **params) -> dict:
+        """How much of the keyframe explains the current frame's kept left edges under (R, t), on host arrays
+        (ebvo_keyframe_cover_edges).  lambda_: one double per mate (None: the triangulated depths).  params: the fields of
+        ebvo_cover_params.  Returns the fields of ebvo_keyframe_cover and, with arrays, flags / assoc / disp per mate, explained
+        per edge and the two cell planes (cw * ch)."""
+        kfL, kfR, E0 = _edges(kf_left), _edges(kf_right), _edges(cf_edges_left)
+        n = len(kfL)
+        if len(kfR) != n:
+            raise ValueError("kf_left and kf_right differ in length")
+        p, cal, r = self.cover_params(**params), self._calib(calib), _lib.KeyframeCover()
+        R, t = self._start_pose(R, t)
+        lam = None
+        if lambda_ is not None:
+            lam = np.ascontiguousarray(lambda_, dtype=np.float64)
+            if lam.shape != (n,):
+                raise ValueError("lambda_ needs one value per keyframe mate")
+        outs = self._cover_outputs(n, len(E0), int(img_w), int(img_h), max(int(p.cover_cell), 1), arrays)
+        self._check(self.lib.ebvo_keyframe_cover_edges(self._ctx, ptr(kfL), ptr(kfR), ptr(lam), n, ptr(E0), len(E0), int(img_w), int(img_h),
+                                                       C.byref(cal), C.byref(p), ptr(R), ptr(t), C.byref(r), *[ptr(a) for a in outs]),
+                    "ebvo_keyframe_cover_edges")
+        out = self._cover_dict(r)
+        if arrays:
+            out.update(zip(self._COVER_ARRAYS, outs))
+        return out
+
+    def temporal_keyframe_cover(self, calib, R, t, slot: int = 0, arrays=True, **params) -> dict:
+        """The same with the context's keyframe mates (on Gamma / lambda while temporal_use_depth is on) against the kept left
+        edge list the slot's pair left resident (ebvo_temporal_keyframe_cover)."""
+        p, cal, r = self.cover_params(**params), self._calib(calib), _lib.KeyframeCover()
+        R, t = self._start_pose(R, t)
+        outs = [None] * 6
+        if arrays:
+            n_kf, n0 = C.c_int32(), C.c_int32()
+            cw, ch = C.c_int32(), C.c_int32()
+            self._check(self.lib.ebvo_temporal_cover_size(self._ctx, slot, C.byref(p), C.byref(n_kf), C.byref(n0), C.byref(cw), C.byref(ch)),
+                        "ebvo_temporal_cover_size")
+            outs = self._cover_outputs(n_kf.value, n0.value, cw.value, ch.value, 1, True)
+        self._check(self.lib.ebvo_temporal_keyframe_cover(self._ctx, slot, C.byref(cal), C.byref(p), ptr(R), ptr(t), C.byref(r),
+                                                          *[ptr(a) for a in outs]), "ebvo_temporal_keyframe_cover")
+        out = self._cover_dict(r)
+        if arrays:
+            out.update(zip(self._COVER_ARRAYS, outs))
+        return out
+
+    def keyframe_decide(self, cover: dict, **policy):
+        """(decision, reasons) of ebvo_keyframe_decide on a cover record (a dict of its fields): 0 keep, 1 switch, 2 lost."""
+        p, r, reasons = self.keyframe_policy(**policy), self._cover_record(cover), C.c_uint32()
+        d = self.lib.ebvo_keyframe_decide(C.byref(r), C.byref(p), C.byref(reasons))
+        self._check(min(d, 0), "ebvo_keyframe_decide")
+        return int(d), int(reasons.value)
+
+    def temporal_keyframe_pose(self):
+        """(Rk, tk): the keyframe's pose in the sequence frame, X_kf = Rk X_seq + tk (ebvo_temporal_keyframe_pose)."""
+        R, t = np.zeros(9), np.zeros(3)
+        self._check(self.lib.ebvo_temporal_keyframe_pose(self._ctx, ptr(R), ptr(t)), "ebvo_temporal_keyframe_pose")
+        return R.reshape(3, 3), t
+
+    def track_params(self, align=None, depth=None, cover=None, carry=None, finalize=None, policy=None, refine_depth=True) -> _lib.TrackParams:
+        """ebvo_track_params: the defaults of ebvo_track_default_params with a dict of fields applied per stage (finalize: the
+        fields of ebvo_finalize_params, `gn` a dict of ebvo_gn_params fields)."""
+        p = _lib.TrackParams()
+        self.lib.ebvo_track_default_params(C.byref(p))
+        for name, kw in (("align", align), ("depth", depth), ("cover", cover), ("carry", carry), ("policy", policy)):
+            self._with(getattr(p, name), name, dict(kw or {}))
+        fin = dict(finalize or {})
+        self._with(p.finalize.gn, "finalize gn", dict(fin.pop("gn", {})))
+        self._with(p.finalize, "finalize", fin)
+        p.refine_depth = 1 if refine_depth else 0
+        return p
+
+    def temporal_track_frame(self, calib, R, t, slot: int = 0, **stages) -> dict:
+        """One frame step on a waited slot (ebvo_temporal_track_frame): align from (R, t), refine the keyframe's depths, measure
+        the coverage, decide and -- on decision 1 -- finalise the slot and promote it.  stages: the arguments of track_params.
+        Returns pose / depth / cover / carried / finalized (dicts of the records), reasons, decision, switched, tracked,
+        failed_stage, R_seq (3x3), t_seq.  A refusal raises EbvoError; its `stage` names the stage."""
+        p, cal, r = self.track_params(**stages), self._calib(calib), _lib.TrackedFrame()
+        R, t = self._start_pose(R, t)
+        rc = self.lib.ebvo_temporal_track_frame(self._ctx, slot, C.byref(cal), C.byref(p), ptr(R), ptr(t), C.byref(r))
+        if rc:
+            try:
+                self._check(rc, f"ebvo_temporal_track_frame (stage {r.failed_stage})")
+            except _lib.EbvoError as e:
+                e.stage = int(r.failed_stage)
+                raise
+        out = dict(pose=self._aligned_dict(r.pose, None, None), depth=self._depth_dict(r.depth), cover=self._cover_dict(r.cover),
+                   carried=self._carried_dict(r.carried), finalized={k: int(getattr(r.finalized, k)) for k, _ in r.finalized._fields_},
+                   reasons=int(r.reasons), decision=int(r.decision), switched=int(r.switched), tracked=int(r.tracked),
+                   failed_stage=int(r.failed_stage), R_seq=np.array(r.R_seq[:], dtype=np.float64).reshape(3, 3),
+                   t_seq=np.array(r.t_seq[:], dtype=np.float64))
+        return out
+
     # -- ground-truth evaluation from a disparity map (Find_Stereo_GT_Locations, get_Stereo_Edge_GT_Pairs,
     # -- Evaluate_Stereo_Edge_Correspondences) ---------------------------------------------------------------
     def gt_params(self, **kw) -> _lib.GtParams:

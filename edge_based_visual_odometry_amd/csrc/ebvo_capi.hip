@@ -175,7 +175,7 @@ static void slot_destroy(Slot *s)
                        &s->keep,         &s->patches_raw,  &s->patches_norm,   &s->patches_flag,   &s->patches_norm_r,
                        &s->patches_flag_r, &s->pair_left,  &s->sincos,         &s->scratch_b,      &s->scratch_c,
                        &s->scratch_d,    &s->fetch_pack,   &s->pose_in,        &s->pose_geom,      &s->pose_order,
-                       &s->pose_draw,    &s->pose_hyp,       &s->pose_sel,       &s->pose_casc,       &s->pose_refit,     &s->align_up,       &s->align_ws,       &s->depth_up,       &s->depth_ws,       &s->carry_up,       &s->carry_ws,       &s->gt_disp,        &s->gt_geom,        &s->gt_flags,
+                       &s->pose_draw,    &s->pose_hyp,       &s->pose_sel,       &s->pose_casc,       &s->pose_refit,     &s->align_up,       &s->align_ws,       &s->depth_up,       &s->depth_ws,       &s->carry_up,       &s->carry_ws,       &s->cover_up,       &s->cover_ws,       &s->gt_disp,        &s->gt_geom,        &s->gt_flags,
                        &s->gt_boxes,     &s->gt_pool_i32,  &s->gt_pool_idx,    &s->gt_rows,        &s->gt_tot,
                        &s->gt_up,        &s->tgt_geom,     &s->tgt_i32,        &s->tgt_idx,        &s->tgt_u8,
                        &s->tgt_rows,     &s->tgt_flags,    &s->tgt_tot,        &s->tgt_up,
@@ -3350,7 +3350,13 @@ extern "C" int ebvo_temporal_set_keyframe(ebvo_ctx *ctx, int slot)
         return EBVO_ERR_ARG;
     if (int rc = keyframe_slot_state(ctx, *sp))
         return rc;
-    return keyframe_install(ctx, *sp);
+    if (int rc = keyframe_install(ctx, *sp))
+        return rc;
+    // the sequence frame is this keyframe's
+    for (int i = 0; i < 9; ++i)
+        ctx->kf_Rk[i] = i % 4 == 0 ? 1.0 : 0.0;
+    ctx->kf_tk[0] = ctx->kf_tk[1] = ctx->kf_tk[2] = 0.0;
+    return EBVO_OK;
 }
 
 // developer key 22 holds for the launches of temporal_stage0_enqueue and temporal_chain only: the helpers they share with
@@ -4959,6 +4965,18 @@ extern "C" int ebvo_depth_carry(ebvo_ctx *ctx, const ebvo_edge *kf_left, const e
     return EBVO_OK;
 }
 
+// (R, t) after (Rk, tk): Ro = R Rk, every entry (R_i0 Rk_0j + R_i1 Rk_1j) + R_i2 Rk_2j, and to = mv3(R, tk) + t; one rounding
+// per operation (-ffp-contract=off holds for the host code of this file too)
+static void seq_compose(const double *R, const double *t, const double *Rk, const double *tk, double *Ro, double *to)
+{
+    for (int i = 0; i < 3; ++i)
+    {
+        for (int j = 0; j < 3; ++j)
+            Ro[3 * i + j] = (R[3 * i] * Rk[j] + R[3 * i + 1] * Rk[3 + j]) + R[3 * i + 2] * Rk[6 + j];
+        to[i] = ((R[3 * i] * tk[0] + R[3 * i + 1] * tk[1]) + R[3 * i + 2] * tk[2]) + t[i];
+    }
+}
+
 // the second set of state arrays holds n values (the set the next promotion writes)
 static int carry_alt_ensure(ebvo_ctx *ctx, size_t n)
 {
@@ -5045,6 +5063,11 @@ extern "C" int ebvo_temporal_promote_keyframe(ebvo_ctx *ctx, int slot, const ebv
     ctx->kf_promoted = true;
     ctx->kf_src_none = !carry;
     carry_publish(counts, n_old, n_new, out);
+    // the new keyframe's pose in the sequence frame: Rk <- R Rk, tk <- R tk + t
+    double Rk[9], tk[3];
+    seq_compose(R, t, ctx->kf_Rk, ctx->kf_tk, Rk, tk);
+    memcpy(ctx->kf_Rk, Rk, sizeof Rk);
+    memcpy(ctx->kf_tk, tk, sizeof tk);
     return EBVO_OK;
 }
 
@@ -5068,6 +5091,278 @@ extern "C" int ebvo_temporal_depth_source(ebvo_ctx *ctx, int32_t *src_index)
     }
     EBVO_HIP(ctx, hipSetDevice(ctx->device));
     EBVO_HIP(ctx, hipMemcpy(src_index, ctx->kf_src, 4 * n, hipMemcpyDeviceToHost));
+    return EBVO_OK;
+}
+
+// ---- keyframe coverage, the switch policy and the frame step (cover_kernels.hip) ------------------------------------------
+extern "C" void ebvo_cover_default_params(ebvo_cover_params *p)
+{
+    if (!p)
+        return;
+    p->radius = 4.0;
+    p->orient_thr_deg = 10.0;
+    p->img_margin = 10.0;
+    p->inlier_px = 1.0;
+    p->bin_px = 1.0;
+    p->cell_size = 4;
+    p->cover_cell = 32;
+    p->min_cell_edges = 4;
+    p->min_cell_explained = 2;
+    p->reserved = 0;
+    p->pad = 0;
+}
+
+static bool cover_args_ok(const ebvo_stereo_calib *cal, const ebvo_cover_params *cp, const double *R, const double *t,
+                          const ebvo_keyframe_cover *out, int img_w, int img_h)
+{
+    if (!cal || !cp || !R || !t || !out || img_w < 1 || img_h < 1)
+        return false;
+    for (int i = 0; i < 9; ++i)
+        if (!std::isfinite(R[i]))
+            return false;
+    for (int i = 0; i < 3; ++i)
+        if (!std::isfinite(t[i]))
+            return false;
+    // every comparison is false for a NaN
+    if (!(std::isfinite(cp->radius) && cp->radius > 0 && cp->cell_size >= 1 && cp->orient_thr_deg >= 0 && cp->img_margin >= 0 &&
+          cp->inlier_px >= 0 && std::isfinite(cp->bin_px) && cp->bin_px > 0 && cp->cover_cell >= 1 && cp->min_cell_edges >= 1 &&
+          cp->min_cell_explained >= 1 && cp->reserved == 0 && cp->pad == 0))
+        return false;
+    if (!(ceil(cp->radius / cp->cell_size) <= 8.0))
+        return false;
+    const int64_t gw = ((int64_t)img_w + cp->cell_size - 1) / cp->cell_size, gh = ((int64_t)img_h + cp->cell_size - 1) / cp->cell_size;
+    const int64_t cw = ((int64_t)img_w + cp->cover_cell - 1) / cp->cover_cell, ch = ((int64_t)img_h + cp->cover_cell - 1) / cp->cover_cell;
+    return gw * gh <= (1 << 26) && cw * ch <= (1 << 26);
+}
+
+// nothing to launch: the record and every output that was asked for
+static void cover_nothing(const ebvo_cover_params *cp, int n_kf, int n0, int img_w, int img_h, ebvo_keyframe_cover *out, uint8_t *flags,
+                          int32_t *assoc, double *disp, uint8_t *explained, int32_t *cell_edges, int32_t *cell_explained)
+{
+    memset(out, 0, sizeof *out);
+    out->n_kf = n_kf;
+    out->n_edges = n0;
+    out->cw = (int32_t)(((int64_t)img_w + cp->cover_cell - 1) / cp->cover_cell);
+    out->ch = (int32_t)(((int64_t)img_h + cp->cover_cell - 1) / cp->cover_cell);
+    out->disp_median_bin = -1;
+    for (int i = 0; i < n_kf; ++i)
+    {
+        if (flags)
+            flags[i] = 0;
+        if (assoc)
+            assoc[i] = -1;
+        if (disp)
+            disp[i] = NAN;
+    }
+    if (explained && n0 > 0)
+        memset(explained, 0, (size_t)n0);
+    const size_t nc = (size_t)out->cw * (size_t)out->ch;
+    if (cell_edges)
+        memset(cell_edges, 0, sizeof(int32_t) * nc);
+    if (cell_explained)
+        memset(cell_explained, 0, sizeof(int32_t) * nc);
+}
+
+extern "C" int ebvo_keyframe_cover_edges(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *kf_right, const double *lambda, int n_kf,
+                                         const ebvo_edge *cf_edges_left, int n0, int img_w, int img_h, const ebvo_stereo_calib *cal,
+                                         const ebvo_cover_params *params, const double R[9], const double t[3], ebvo_keyframe_cover *out,
+                                         uint8_t *flags, int32_t *assoc, double *disp, uint8_t *explained, int32_t *cell_edges,
+                                         int32_t *cell_explained)
+{
+    if (!ctx || !cover_args_ok(cal, params, R, t, out, img_w, img_h) || n_kf < 0 || n0 < 0 || (n_kf > 0 && (!kf_left || !kf_right)) ||
+        (n0 > 0 && !cf_edges_left))
+        return EBVO_ERR_ARG;
+    int rc;
+    Slot *sp;
+    if ((rc = gt_host_slot(ctx, &sp)))
+        return rc;
+    Slot &s = *sp;
+    if (n_kf == 0 || n0 == 0)
+    {
+        cover_nothing(params, n_kf, n0, img_w, img_h, out, flags, assoc, disp, explained, cell_edges, cell_explained);
+        return EBVO_OK;
+    }
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nz = (size_t)n_kf, eb = sizeof(ebvo_edge);
+    auto up64 = [](size_t v) { return (v + 63) & ~(size_t)63; };
+    const size_t o_kfR = up64(eb * nz), o_E0 = o_kfR + up64(eb * nz), o_lam = o_E0 + up64(eb * (size_t)n0), total = o_lam + up64(8 * nz);
+    if ((rc = gt_grow(ctx, s, s.cover_up, total)))
+        return rc;
+    char *base = (char *)s.cover_up.p;
+    ebvo_edge *kfL = (ebvo_edge *)base, *kfR = (ebvo_edge *)(base + o_kfR), *E0 = (ebvo_edge *)(base + o_E0);
+    double *d_lam = lambda ? (double *)(base + o_lam) : nullptr;
+    hipStream_t st = s.stream;
+    ebvo_keyframe_cover rec;
+    auto enqueue = [&]() -> int {
+        EBVO_HIP(ctx, hipMemcpyAsync(kfL, kf_left, eb * nz, hipMemcpyHostToDevice, st));
+        EBVO_HIP(ctx, hipMemcpyAsync(kfR, kf_right, eb * nz, hipMemcpyHostToDevice, st));
+        EBVO_HIP(ctx, hipMemcpyAsync(E0, cf_edges_left, eb * (size_t)n0, hipMemcpyHostToDevice, st));
+        if (lambda)
+            EBVO_HIP(ctx, hipMemcpyAsync(d_lam, lambda, 8 * nz, hipMemcpyHostToDevice, st));
+        const TemporalGridScope grid_scope(ctx, s);
+        return cover_run(ctx, s, kfL, kfR, n_kf, d_lam, E0, n0, img_w, img_h, cal, params, R, t, &rec, flags, assoc, disp, explained, cell_edges,
+                         cell_explained);
+    };
+    rc = enqueue();
+    const hipError_t e = hipStreamSynchronize(st); // the copies read and write the caller's arrays: none of them outlives the call
+    if (rc)
+        return rc;
+    EBVO_HIP(ctx, e);
+    *out = rec;
+    return EBVO_OK;
+}
+
+extern "C" int ebvo_temporal_keyframe_cover(ebvo_ctx *ctx, int slot, const ebvo_stereo_calib *cal, const ebvo_cover_params *params,
+                                            const double R[9], const double t[3], ebvo_keyframe_cover *out, uint8_t *flags, int32_t *assoc,
+                                            double *disp, uint8_t *explained, int32_t *cell_edges, int32_t *cell_explained)
+{
+    Slot *sp;
+    if (get_slot(ctx, slot, &sp))
+        return EBVO_ERR_ARG;
+    Slot &s = *sp;
+    // the frame's size enters the accepted ranges through the grids; a slot without a pair has none yet
+    if (!cover_args_ok(cal, params, R, t, out, s.have_run ? s.cur_w : 1, s.have_run ? s.cur_h : 1))
+        return EBVO_ERR_ARG;
+    if (int rc = align_slot_state(ctx, s))
+        return rc;
+    const int n_kf = ctx->kf_n, n0 = s.im[0].n_kept;
+    if (n_kf == 0 || n0 == 0)
+    {
+        cover_nothing(params, n_kf, n0, s.cur_w, s.cur_h, out, flags, assoc, disp, explained, cell_edges, cell_explained);
+        return EBVO_OK;
+    }
+    EBVO_HIP(ctx, hipSetDevice(ctx->device));
+    ebvo_keyframe_cover rec;
+    int rc;
+    {
+        const TemporalGridScope grid_scope(ctx, s);
+        // the keyframe's refined depths, when they are in use and a frame has been fused (at the prior lambda is 1)
+        const double *d_lam = ctx->use_depth && !ctx->kf_depth_fresh ? ctx->kf_lambda : nullptr;
+        rc = cover_run(ctx, s, ctx->kf_L, ctx->kf_R, n_kf, d_lam, s.im[0].edges, n0, s.cur_w, s.cur_h, cal, params, R, t, &rec, flags, assoc, disp,
+                       explained, cell_edges, cell_explained);
+    }
+    const hipError_t e = hipStreamSynchronize(s.stream);
+    if (rc)
+        return rc;
+    EBVO_HIP(ctx, e);
+    *out = rec;
+    return EBVO_OK;
+}
+
+extern "C" int ebvo_temporal_cover_size(ebvo_ctx *ctx, int slot, const ebvo_cover_params *params, int32_t *n_kf, int32_t *n0, int32_t *cw,
+                                        int32_t *ch)
+{
+    Slot *sp;
+    if (get_slot(ctx, slot, &sp) || !params || params->cover_cell < 1 || !n_kf || !n0 || !cw || !ch)
+        return EBVO_ERR_ARG;
+    if (int rc = align_slot_state(ctx, *sp))
+        return rc;
+    *n_kf = ctx->kf_n;
+    *n0 = sp->im[0].n_kept;
+    *cw = (int32_t)(((int64_t)sp->cur_w + params->cover_cell - 1) / params->cover_cell);
+    *ch = (int32_t)(((int64_t)sp->cur_h + params->cover_cell - 1) / params->cover_cell);
+    return EBVO_OK;
+}
+
+extern "C" void ebvo_keyframe_policy_default(ebvo_keyframe_policy *p)
+{
+    if (!p)
+        return;
+    p->min_assoc = 50;
+    p->max_disp_bins = 30;
+    p->min_in_frame_share = 0.7;
+    p->min_assoc_share = 0.5;
+    p->min_cell_cover = 0.6;
+}
+
+extern "C" int ebvo_keyframe_decide(const ebvo_keyframe_cover *c, const ebvo_keyframe_policy *p, uint32_t *reasons)
+{
+    if (!c || !p)
+        return EBVO_ERR_ARG;
+    uint32_t r = 0;
+    if (c->n_assoc < p->min_assoc)
+        r |= EBVO_KF_LOST;
+    if ((double)c->n_in_frame < p->min_in_frame_share * (double)(c->n_kf - c->n_dead))
+        r |= EBVO_KF_LOW_OVERLAP;
+    if ((double)c->n_assoc < p->min_assoc_share * (double)c->n_in_frame)
+        r |= EBVO_KF_LOW_ASSOC;
+    if ((double)c->n_cells_covered < p->min_cell_cover * (double)c->n_cells_cur)
+        r |= EBVO_KF_NEW_CONTENT;
+    if (c->disp_median_bin >= p->max_disp_bins)
+        r |= EBVO_KF_PARALLAX;
+    if (reasons)
+        *reasons = r;
+    return (r & EBVO_KF_LOST) ? 2 : r ? 1 : 0;
+}
+
+extern "C" int ebvo_temporal_keyframe_pose(ebvo_ctx *ctx, double R[9], double t[3])
+{
+    if (!ctx)
+        return EBVO_ERR_ARG;
+    if (ctx->kf_n < 0)
+    {
+        ctx->last_error = "no keyframe (ebvo_temporal_set_keyframe first)";
+        return EBVO_ERR_STATE;
+    }
+    if (R)
+        memcpy(R, ctx->kf_Rk, sizeof ctx->kf_Rk);
+    if (t)
+        memcpy(t, ctx->kf_tk, sizeof ctx->kf_tk);
+    return EBVO_OK;
+}
+
+extern "C" void ebvo_track_default_params(ebvo_track_params *p)
+{
+    if (!p)
+        return;
+    memset(p, 0, sizeof *p);
+    ebvo_align_default_params(&p->align);
+    ebvo_depth_default_params(&p->depth);
+    ebvo_cover_default_params(&p->cover);
+    ebvo_depth_carry_default_params(&p->carry);
+    ebvo_finalize_default_params(&p->finalize);
+    ebvo_keyframe_policy_default(&p->policy);
+    p->refine_depth = 1;
+    p->reserved = 0;
+}
+
+extern "C" int ebvo_temporal_track_frame(ebvo_ctx *ctx, int slot, const ebvo_stereo_calib *cal, const ebvo_track_params *params,
+                                         const double R0[9], const double t0[3], ebvo_tracked_frame *out)
+{
+    if (!ctx || !params || !out || (params->refine_depth != 0 && params->refine_depth != 1) || params->reserved != 0)
+        return EBVO_ERR_ARG;
+    memset(out, 0, sizeof *out);
+    out->cover.disp_median_bin = -1;
+    out->decision = 2;
+    int rc;
+    auto failed = [&](int stage, int status) {
+        out->failed_stage = stage;
+        return status;
+    };
+    // (a) the pose
+    if ((rc = ebvo_temporal_align_pose(ctx, slot, cal, &params->align, R0, t0, &out->pose, nullptr, nullptr)))
+        return failed(EBVO_TRACK_STAGE_ALIGN, rc);
+    const double *R = out->pose.R, *t = out->pose.t;
+    seq_compose(R, t, ctx->kf_Rk, ctx->kf_tk, out->R_seq, out->t_seq);
+    if (out->pose.status != 0)
+        return EBVO_OK; // tracking lost: tracked 0, decision 2
+    out->tracked = 1;
+    // (b) the keyframe's depths
+    if (params->refine_depth && (rc = ebvo_temporal_refine_depth(ctx, slot, cal, &params->align, &params->depth, R, t, &out->depth)))
+        return failed(EBVO_TRACK_STAGE_DEPTH, rc);
+    // (c) the measurement, (d) the decision
+    if ((rc = ebvo_temporal_keyframe_cover(ctx, slot, cal, &params->cover, R, t, &out->cover, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                           nullptr)))
+        return failed(EBVO_TRACK_STAGE_COVER, rc);
+    out->decision = ebvo_keyframe_decide(&out->cover, &params->policy, &out->reasons);
+    if (out->decision != 1)
+        return EBVO_OK;
+    // (e) the switch
+    if ((rc = ebvo_stereo_finalize(ctx, slot, &params->finalize, cal, &out->finalized)))
+        return failed(EBVO_TRACK_STAGE_FINALIZE, rc);
+    if ((rc = ebvo_temporal_promote_keyframe(ctx, slot, cal, &params->carry, R, t, &out->carried)))
+        return failed(EBVO_TRACK_STAGE_PROMOTE, rc);
+    out->switched = 1;
     return EBVO_OK;
 }
 

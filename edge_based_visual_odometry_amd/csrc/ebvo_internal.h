@@ -190,6 +190,8 @@ struct Slot
                                  // the tile sums and the record of either call
     GrowBuf carry_up, carry_ws;  // handover of the depths on promotion (carry_kernels.hip): the uploaded arrays and the outgoing state
                                  // of the host-array call; the counters, the old mates' projections, their planes and grid of either call
+    GrowBuf cover_up, cover_ws;  // keyframe coverage (cover_kernels.hip): the uploaded arrays of the host-array call; the record, the
+                                 // counters, the bins, the cell planes and the per-mate and per-edge outputs of either call
     GrowBuf pose_refit;          // inlier refit (pose_refit_kernels.hip): seven planes per quad, the fit set, the mask, the result
     // ground-truth evaluation (gt_kernels.hip, ebvo_stereo_set_gt): armed = the buffers below describe the resident pair
     GrowBuf gt_disp, gt_geom, gt_flags, gt_boxes, gt_pool_i32, gt_pool_idx, gt_rows, gt_tot;
@@ -362,6 +364,9 @@ struct ebvo_ctx
     bool kf_promoted = false;  // the keyframe was installed by a promotion (ebvo_temporal_depth_source)
     bool kf_src_none = true;   // ... whose old keyframe had nothing to carry: every src_index is -1
     bool use_depth = false;    // ebvo_temporal_use_depth
+    // the keyframe's pose in the sequence frame, X_kf = Rk X_seq + tk (ebvo_temporal_keyframe_pose): the identity after
+    // ebvo_temporal_set_keyframe, composed with the pose of every promotion
+    double kf_Rk[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, kf_tk[3] = {0, 0, 0};
     bool undist_on = false;    // ebvo_stereo_set_undistort
     ebvo_undistort_params undist{};
     int lanes = 4;             // streams the kernels of submitted pairs are dealt to from four slots on (ebvo_stereo_submit)
@@ -792,6 +797,14 @@ int carry_run(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_oldL, const ebvo_edge *
               const double *d_info_in, const int32_t *d_nobs_in, const ebvo_edge *d_newL, const ebvo_edge *d_newR, int n_new, int img_w,
               int img_h, const ebvo_stereo_calib *cal, const ebvo_depth_carry_params *cp, const double *R, const double *t, double *d_lam,
               double *d_info, int32_t *d_nobs, uint8_t *d_flags, int32_t *d_src, int32_t *counts);
+// cover_kernels.hip: the coverage of n0 >= 1 current left edges by n_kf >= 1 keyframe mates under (R, t), enqueued and NOT waited
+// for (the copies of the record and of every output that is not NULL -- host pointers -- included).  d_lambda (device, may be
+// NULL): the inverse-depth ratio per mate.  The association is align_associate_once's (s.align_ws); the workspace is
+// s.cover_ws; developer key 22 (Slot::tq_blocks) caps its grid-stride launches.
+int cover_run(ebvo_ctx *ctx, Slot &s, const ebvo_edge *d_kfL, const ebvo_edge *d_kfR, int n_kf, const double *d_lambda, const ebvo_edge *d_E0,
+              int n0, int img_w, int img_h, const ebvo_stereo_calib *cal, const ebvo_cover_params *cp, const double *R, const double *t,
+              ebvo_keyframe_cover *out, uint8_t *flags, int32_t *assoc, double *disp, uint8_t *explained, int32_t *cell_edges,
+              int32_t *cell_explained);
 int misc_fp64_peak(ebvo_ctx *ctx, Slot &s, int iters, double *tf_muladd, double *tf_fma);
 
 #endif

@@ -32,6 +32,7 @@
 #include <fstream>
 #include <cstring>
 #include <iomanip>
+#include <limits>
 #include <memory>
 #include <ostream>
 #include <string>
@@ -1131,6 +1132,106 @@ class MotionTrackerHIP
         return report(*ctx_, last_status, "ebvo_temporal_depth_source");
     }
 
+    // How much of the keyframe still explains the current frame and how much of the current frame it does not explain, the
+    // policy that reads the measurement and one call per frame that ties the stages together (this project's own; the
+    // contract is in ebvo_hip.h).
+    struct Cover_Options
+    {
+        ebvo_cover_params p;
+        Cover_Options() { ebvo_cover_default_params(&p); }
+    };
+    struct Switch_Policy
+    {
+        ebvo_keyframe_policy p;
+        Switch_Policy() { ebvo_keyframe_policy_default(&p); }
+    };
+    struct Keyframe_Coverage
+    {
+        ebvo_keyframe_cover cover{};
+        std::vector<uint8_t> flags;      // per keyframe mate: EBVO_COVER_*                    (the arrays when asked for)
+        std::vector<int32_t> assoc;      // per keyframe mate: edge index or -1
+        std::vector<double> disp;        // per keyframe mate: displacement from its keyframe position, NaN when not in frame
+        std::vector<uint8_t> explained;  // per current left edge
+        std::vector<int32_t> cell_edges, cell_explained; // cover.cw * cover.ch
+    };
+
+    // the context's keyframe against the slot's waited pair under the pose (state.R, state.t)
+    bool keyframe_Coverage(int slot, const Cover_Options &opt, const Align_State &state, Keyframe_Coverage &out, bool want_arrays = false)
+    {
+        out = Keyframe_Coverage{};
+        if (want_arrays)
+        {
+            int32_t n_kf = 0, n0 = 0, cw = 0, ch = 0;
+            last_status = ebvo_temporal_cover_size(ctx_->get(), slot, &opt.p, &n_kf, &n0, &cw, &ch);
+            if (!report(*ctx_, last_status, "ebvo_temporal_cover_size"))
+                return false;
+            size_cover(out, (size_t)n_kf, (size_t)n0, (size_t)cw * (size_t)ch);
+        }
+        last_status = ebvo_temporal_keyframe_cover(ctx_->get(), slot, &calib_, &opt.p, state.R.data(), state.t.data(), &out.cover,
+                                                   want_arrays ? out.flags.data() : nullptr, want_arrays ? out.assoc.data() : nullptr,
+                                                   want_arrays ? out.disp.data() : nullptr, want_arrays ? out.explained.data() : nullptr,
+                                                   want_arrays ? out.cell_edges.data() : nullptr,
+                                                   want_arrays ? out.cell_explained.data() : nullptr);
+        return report(*ctx_, last_status, "ebvo_temporal_keyframe_cover");
+    }
+
+    // the same on host arrays: keyframe mates, their lambda (empty: the triangulated depths) and the left edge list of a frame
+    // of img_w x img_h
+    bool keyframe_Coverage(const std::vector<ebvo_edge> &kf_left, const std::vector<ebvo_edge> &kf_right, const std::vector<double> &lambda,
+                           const std::vector<ebvo_edge> &edges_left, int img_w, int img_h, const Cover_Options &opt, const Align_State &state,
+                           Keyframe_Coverage &out, bool want_arrays = true)
+    {
+        out = Keyframe_Coverage{};
+        const size_t n = kf_left.size();
+        if (kf_right.size() != n || (!lambda.empty() && lambda.size() != n) || img_w < 1 || img_h < 1 || opt.p.cover_cell < 1)
+        {
+            last_status = EBVO_ERR_ARG;
+            return false;
+        }
+        if (want_arrays)
+            size_cover(out, n, edges_left.size(),
+                       (size_t)((img_w + (int64_t)opt.p.cover_cell - 1) / opt.p.cover_cell) *
+                           (size_t)((img_h + (int64_t)opt.p.cover_cell - 1) / opt.p.cover_cell));
+        last_status = ebvo_keyframe_cover_edges(ctx_->get(), kf_left.data(), kf_right.data(), lambda.empty() ? nullptr : lambda.data(), (int)n,
+                                                edges_left.data(), (int)edges_left.size(), img_w, img_h, &calib_, &opt.p, state.R.data(),
+                                                state.t.data(), &out.cover, want_arrays ? out.flags.data() : nullptr,
+                                                want_arrays ? out.assoc.data() : nullptr, want_arrays ? out.disp.data() : nullptr,
+                                                want_arrays ? out.explained.data() : nullptr, want_arrays ? out.cell_edges.data() : nullptr,
+                                                want_arrays ? out.cell_explained.data() : nullptr);
+        return report(*ctx_, last_status, "ebvo_keyframe_cover_edges");
+    }
+
+    // 0 keep, 1 switch, 2 lost; reasons: EBVO_KF_* bits.  A pure host function of the record.
+    int should_Switch_Keyframe(const ebvo_keyframe_cover &cover, const Switch_Policy &policy, uint32_t *reasons = nullptr) const
+    {
+        return ebvo_keyframe_decide(&cover, &policy.p, reasons);
+    }
+
+    struct Track_Options
+    {
+        ebvo_track_params p;
+        Track_Options() { ebvo_track_default_params(&p); }
+    };
+
+    // One frame on a slot whose pair has been waited for: align from (state.R, state.t), refine the keyframe's depths, measure
+    // the coverage, decide and -- on decision 1 -- finalise the slot and promote it.  true when the frame was tracked
+    // (frame.tracked == 1); a refusal leaves last_status and frame.failed_stage.
+    bool track_Frame(int slot, const Track_Options &opt, const Align_State &state, ebvo_tracked_frame &frame)
+    {
+        frame = ebvo_tracked_frame{};
+        last_status = ebvo_temporal_track_frame(ctx_->get(), slot, &calib_, &opt.p, state.R.data(), state.t.data(), &frame);
+        if (!report(*ctx_, last_status, "ebvo_temporal_track_frame"))
+            return false;
+        return frame.tracked == 1;
+    }
+
+    // the keyframe's pose in the sequence frame: X_kf = R X_seq + t (the identity after set_Keyframe, composed by every promotion)
+    bool keyframe_Pose(std::array<double, 9> &R, std::array<double, 3> &t)
+    {
+        last_status = ebvo_temporal_keyframe_pose(ctx_->get(), R.data(), t.data());
+        return report(*ctx_, last_status, "ebvo_temporal_keyframe_pose");
+    }
+
     // n_runs calls of the reference's Solution_Constraints_Application (src/Pipeline.cpp:198-203 makes 20) in one device
     // call: one vector of five stages per run.  Empty on an error (last_status) and when the slot has too few quads.
     std::vector<std::vector<Quad_Pair_Evaluation_Metrics>> Solution_Constraints_Application(int slot, const Ransac_Options &opt,
@@ -1195,6 +1296,15 @@ class MotionTrackerHIP
     {
         state.assoc_left.assign(n, -1);
         state.assoc_right.assign(n, -1);
+    }
+    static void size_cover(Keyframe_Coverage &out, size_t n_kf, size_t n0, size_t n_cells)
+    {
+        out.flags.assign(n_kf, 0);
+        out.assoc.assign(n_kf, -1);
+        out.disp.assign(n_kf, std::numeric_limits<double>::quiet_NaN());
+        out.explained.assign(n0, 0);
+        out.cell_edges.assign(n_cells, 0);
+        out.cell_explained.assign(n_cells, 0);
     }
     Context::Ptr ctx_;
     ebvo_stereo_calib calib_;

@@ -49,7 +49,13 @@ extern "C" {
                               ebvo_temporal_use_depth, ebvo_pose_align_edges_depth; and with the additive handover of
                               the depths on promotion: ebvo_depth_carry_params, ebvo_depth_carried,
                               ebvo_depth_carry_default_params, ebvo_depth_carry, ebvo_temporal_promote_keyframe,
-                              ebvo_temporal_depth_source */
+                              ebvo_temporal_depth_source; and with the additive keyframe coverage, switch policy and
+                              frame step: ebvo_cover_params, ebvo_keyframe_cover, ebvo_cover_default_params,
+                              ebvo_keyframe_cover_edges, ebvo_temporal_keyframe_cover, ebvo_temporal_cover_size,
+                              ebvo_keyframe_policy,
+                              ebvo_keyframe_policy_default, ebvo_keyframe_decide, ebvo_temporal_keyframe_pose,
+                              ebvo_track_params, ebvo_tracked_frame, ebvo_track_default_params,
+                              ebvo_temporal_track_frame */
 
 typedef struct ebvo_ctx ebvo_ctx;
 
@@ -1062,6 +1068,161 @@ int ebvo_temporal_promote_keyframe(ebvo_ctx *ctx, int slot, const ebvo_stereo_ca
 /* src_index of the last promotion: n_kf int32 (all -1 when the old keyframe had nothing to carry).  EBVO_ERR_STATE when the
  * keyframe was not installed by a promotion. */
 int ebvo_temporal_depth_source(ebvo_ctx *ctx, int32_t *src_index);
+
+/* ---- keyframe coverage, a switch policy and a frame step (this project's own stage) ---------------------------------- */
+/* How much of the keyframe still explains the current frame, and how much of the current frame the keyframe does not
+ * explain: the measurement a caller needs to decide when to switch keyframes.  This comment is the arithmetic contract;
+ * tests/oracle_cover.py restates it and the device matches it bit for bit.  fp64, no FMA, IEEE division and sqrt; mv3 of
+ * csrc/ebvo_geom.h; ebvo_sincos and ebvo_atan2 of csrc/ebvo_math.h.  Camera 0 only: a keyframe decision is about the left
+ * image.  Additive: the ABI version stays 6.
+ * Inputs: the keyframe's mates kf_left[i], kf_right[i], i < n_kf; lambda [n_kf] or NULL (NULL: the triangulated Gamma, as
+ *   ebvo_pose_align_edges_depth treats it); the current frame's kept LEFT edge list E0[j], j < n0; its size w x h; the
+ *   calibration; a pose (R, t) in the convention of the pose search (Gc = R Gamma + t in the left camera).
+ * Mate i: Gamma exactly as the alignment's align_prepare_kernel forms it.  The mate is DEAD by the filter's rule (a component
+ *   of Gamma not finite, or Gamma_z not > 0): flags EBVO_COVER_DEAD alone, assoc -1, disp NaN, and nothing below applies to
+ *   it.  Of a live mate, with lambda given, Gs = Gamma / lambda_i (three divisions, the rule of the filter's scaling step),
+ *   else Gs = Gamma; RG = mv3(R, Gs); X = RG + t; p = mv3(K_left, X), q = p / p2.  It is IN FRAME by the alignment's camera-0
+ *   test: img_margin < q_x < w - img_margin, img_margin < q_y < h - img_margin and X_z > 0 (NaN, +-inf: not in frame).
+ * Association: the alignment's own, camera 0, under (R, t), with radius, cell_size, orient_thr_deg and img_margin: the mapped
+ *   orientation, the grid over E0, the candidates and the pick of the smallest (d2, j) are those of ebvo_pose_align_edges
+ *   (one association, no step).  assoc[i] = j or -1; only a mate in frame can be associated.
+ * Residual of an associated mate, as the alignment forms it: (sn, cs) = ebvo_sincos(E0[j].theta), n = (sn, -cs),
+ *   r = n_0 (q_x - E0[j].x) + n_1 (q_y - E0[j].y).  It is an INLIER iff |r| < inlier_px (strict; NaN: not).
+ * Displacement of a mate in frame from its keyframe position: dx = q_x - kf_left[i].x, dy = q_y - kf_left[i].y,
+ *   d = sqrt(dx dx + dy dy); disp[i] = d (NaN for a mate that is not in frame).  b = d / bin_px; the mate counts in bin 63 of
+ *   hist if b >= 63.0, else in bin (int)b.  disp_median_bin is the smallest b with 2 (hist[0] + .. + hist[b]) >= n_in_frame,
+ *   or -1 when n_in_frame = 0.
+ * Current edge j: explained[j] = 1 iff some (live) mate's association is j, else 0; n_explained counts them (two mates on
+ *   one edge count once).
+ * Coarse cells: cw = ceil(w / cover_cell), ch = ceil(h / cover_cell); edge j is in cell ((int)x / cover_cell,
+ *   (int)y / cover_cell) by grid_cell's rule (x in (-cover_cell, cw cover_cell), likewise y; NaN and +-inf are in no cell).
+ *   cell_edges[c] counts the edges of E0 in cell c = cy cw + cx, cell_explained[c] the explained ones.  n_cells_cur: cells
+ *   with cell_edges >= min_cell_edges; n_cells_covered: those of them with cell_explained >= min_cell_explained.
+ * n_kf = 0 or n0 = 0 launches nothing: the record is zero except n_kf, n_edges, cw, ch, with disp_median_bin = -1; flags 0,
+ *   assoc -1, disp NaN, explained and both cell planes 0.
+ * Everything in the record is an integer: no launch geometry or arrival order enters anything. */
+#define EBVO_COVER_DEAD 1u
+#define EBVO_COVER_IN_FRAME 2u
+#define EBVO_COVER_ASSOCIATED 4u
+#define EBVO_COVER_INLIER 8u
+#define EBVO_COVER_BINS 64
+typedef struct ebvo_cover_params
+{
+    double radius;         /* 4.0 px: the alignment's value and rule */
+    double orient_thr_deg; /* 10: the alignment's */
+    double img_margin;     /* 10: the alignment's */
+    double inlier_px;      /* 1.0 (>= 0, +inf allowed) */
+    double bin_px;         /* 1.0 px per displacement bin (finite, > 0) */
+    int32_t cell_size;     /* 4 px: the alignment's grid */
+    int32_t cover_cell;    /* 32 px: the coarse cells (>= 1, at most 2^26 of them) */
+    int32_t min_cell_edges, min_cell_explained; /* 4, 2 (>= 1 each) */
+    int32_t reserved, pad; /* 0, 0 */
+} ebvo_cover_params;
+typedef struct ebvo_keyframe_cover
+{
+    int32_t n_kf, n_dead, n_in_frame, n_assoc, n_inliers;
+    int32_t n_edges, n_explained;
+    int32_t cw, ch, n_cells_cur, n_cells_covered;
+    int32_t disp_median_bin;
+    int32_t hist[EBVO_COVER_BINS];
+} ebvo_keyframe_cover;
+void ebvo_cover_default_params(ebvo_cover_params *p);
+/* On host arrays.  flags (uint8) / assoc (int32) / disp (double): n_kf values each; explained (uint8): n0; cell_edges /
+ * cell_explained (int32): cw ch each; every one of the six may be NULL.  Accepted: radius finite and > 0, cell_size >= 1
+ * with ceil(radius / cell_size) <= 8, orient_thr_deg >= 0, img_margin >= 0, inlier_px >= 0 (+inf allowed), bin_px finite and
+ * > 0, cover_cell >= 1, min_cell_edges >= 1, min_cell_explained >= 1, reserved and pad 0, no NaN, R and t finite, img_w,
+ * img_h >= 1 with at most 2^26 cells in either grid; anything else: EBVO_ERR_ARG, nothing touched.  Runs on slot 0's stream
+ * under the state rules of ebvo_pose_align_edges; the inputs are copied before the call returns. */
+int ebvo_keyframe_cover_edges(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *kf_right, const double *lambda, int n_kf,
+                              const ebvo_edge *cf_edges_left, int n0, int img_w, int img_h, const ebvo_stereo_calib *cal,
+                              const ebvo_cover_params *params, const double R[9], const double t[3], ebvo_keyframe_cover *out,
+                              uint8_t *flags, int32_t *assoc, double *disp, uint8_t *explained, int32_t *cell_edges,
+                              int32_t *cell_explained);
+/* The same on the context's keyframe and the slot's resident kept left edge list, with the keyframe's current lambda iff
+ * ebvo_temporal_use_depth is on (a keyframe at the prior: NULL, the same bits).  State rules: ebvo_temporal_align_pose's.
+ * The slot's pair, final mates, quads, prior, ground-truth state, the depth state and the rand() stream are unchanged. */
+int ebvo_temporal_keyframe_cover(ebvo_ctx *ctx, int slot, const ebvo_stereo_calib *cal, const ebvo_cover_params *params,
+                                 const double R[9], const double t[3], ebvo_keyframe_cover *out, uint8_t *flags, int32_t *assoc,
+                                 double *disp, uint8_t *explained, int32_t *cell_edges, int32_t *cell_explained);
+/* The sizes of that call's arrays: n_kf mates, n0 kept left edges, cw x ch coarse cells (params: cover_cell >= 1 is read). */
+int ebvo_temporal_cover_size(ebvo_ctx *ctx, int slot, const ebvo_cover_params *params, int32_t *n_kf, int32_t *n0, int32_t *cw,
+                             int32_t *ch);
+
+/* The policy: a pure host function of the record's integers.  Each reason is the stated comparison, the share products
+ * formed as (double)a < share * (double)b:
+ *   EBVO_KF_LOST         n_assoc < min_assoc
+ *   EBVO_KF_LOW_OVERLAP  n_in_frame < min_in_frame_share (n_kf - n_dead)
+ *   EBVO_KF_LOW_ASSOC    n_assoc < min_assoc_share n_in_frame
+ *   EBVO_KF_NEW_CONTENT  n_cells_covered < min_cell_cover n_cells_cur
+ *   EBVO_KF_PARALLAX     disp_median_bin >= max_disp_bins
+ * Returns 2 (lost) if EBVO_KF_LOST is set, else 1 (switch) if any other bit is set, else 0 (keep); EBVO_ERR_ARG for a NULL
+ * record or policy.  *reasons (may be NULL) receives the bits.  The defaults are design choices, not measurements. */
+#define EBVO_KF_LOST 1u
+#define EBVO_KF_LOW_OVERLAP 2u
+#define EBVO_KF_LOW_ASSOC 4u
+#define EBVO_KF_NEW_CONTENT 8u
+#define EBVO_KF_PARALLAX 16u
+typedef struct ebvo_keyframe_policy
+{
+    int32_t min_assoc;         /* 50 */
+    int32_t max_disp_bins;     /* 30 */
+    double min_in_frame_share; /* 0.7 */
+    double min_assoc_share;    /* 0.5 */
+    double min_cell_cover;     /* 0.6 */
+} ebvo_keyframe_policy;
+void ebvo_keyframe_policy_default(ebvo_keyframe_policy *p);
+int ebvo_keyframe_decide(const ebvo_keyframe_cover *cover, const ebvo_keyframe_policy *policy, uint32_t *reasons);
+
+/* The keyframe's pose in the sequence frame, (Rk, tk) with X_kf = Rk X_seq + tk: host state of the context.
+ * ebvo_temporal_set_keyframe puts it to the identity (the sequence frame is the last keyframe that was SET rather than
+ * promoted); every successful ebvo_temporal_promote_keyframe under (R, t) makes Rk <- R Rk and tk <- mv3(R, tk) + t.  Every
+ * entry of the 3 x 3 product is (R_i0 Rk_0j + R_i1 Rk_1j) + R_i2 Rk_2j, one rounding per operation, no FMA: mv3's order per
+ * column.  EBVO_ERR_STATE without a keyframe. */
+int ebvo_temporal_keyframe_pose(ebvo_ctx *ctx, double R[9], double t[3]);
+
+/* The frame step on a slot whose ebvo_stereo_wait has returned, from the public calls in this order:
+ *   (a) ebvo_temporal_align_pose from (R0, t0); a status != 0 ends the step: tracked = 0, decision 2;
+ *   (b) with refine_depth, ebvo_temporal_refine_depth under the aligned pose;
+ *   (c) ebvo_temporal_keyframe_cover under the aligned pose; (d) ebvo_keyframe_decide;
+ *   (e) on decision 1 only: ebvo_stereo_finalize of the slot (with the calibration), then ebvo_temporal_promote_keyframe
+ *       under the aligned pose; switched = 1.
+ * R_seq = R Rk, t_seq = mv3(R, tk) + t with (R, t) the aligned pose and (Rk, tk) as they were before any switch: the frame's
+ * pose in the sequence frame.  A refusal at any stage returns that stage's status and names the stage in failed_stage
+ * (EBVO_TRACK_STAGE_*); a failed promotion leaves the old keyframe in place. */
+enum
+{
+    EBVO_TRACK_STAGE_NONE = 0,
+    EBVO_TRACK_STAGE_ALIGN = 1,
+    EBVO_TRACK_STAGE_DEPTH = 2,
+    EBVO_TRACK_STAGE_COVER = 3,
+    EBVO_TRACK_STAGE_FINALIZE = 4,
+    EBVO_TRACK_STAGE_PROMOTE = 5
+};
+typedef struct ebvo_track_params
+{
+    ebvo_align_params align;
+    ebvo_depth_params depth;
+    ebvo_cover_params cover;
+    ebvo_depth_carry_params carry;
+    ebvo_finalize_params finalize;
+    ebvo_keyframe_policy policy;
+    int32_t refine_depth; /* 1 */
+    int32_t reserved;     /* 0 */
+} ebvo_track_params;
+typedef struct ebvo_tracked_frame
+{
+    ebvo_aligned_pose pose;
+    ebvo_depth_refined depth;
+    ebvo_keyframe_cover cover;
+    ebvo_depth_carried carried;
+    ebvo_finalize_counts finalized;
+    double R_seq[9], t_seq[3];
+    uint32_t reasons;
+    int32_t decision, switched, tracked, failed_stage, pad;
+} ebvo_tracked_frame;
+void ebvo_track_default_params(ebvo_track_params *p);
+int ebvo_temporal_track_frame(ebvo_ctx *ctx, int slot, const ebvo_stereo_calib *cal, const ebvo_track_params *params,
+                              const double R0[9], const double t0[3], ebvo_tracked_frame *out);
 
 /* ---- ground-truth evaluation from a disparity map (the reference's has_gt() == true branch, is_left = true) ------- */
 /* Find_Stereo_GT_Locations (src/Stereo_Matches.cpp:133-200), get_Stereo_Edge_GT_Pairs (:202-268) and
