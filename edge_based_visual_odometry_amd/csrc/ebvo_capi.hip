@@ -29,7 +29,7 @@ int ebvo_fail_hip(ebvo_ctx *ctx, hipError_t e, const char *what, const char *fil
     return EBVO_ERR_HIP;
 }
 
-int ebvo_grow(ebvo_ctx *ctx, Slot &s, GrowBuf &b, size_t bytes)
+int ebvo_grow(ebvo_ctx *ctx, Slot &s, GrowBuf &b, size_t bytes, bool bump_generation)
 {
     if (bytes <= b.bytes && b.p)
         return EBVO_OK;
@@ -40,7 +40,8 @@ int ebvo_grow(ebvo_ctx *ctx, Slot &s, GrowBuf &b, size_t bytes)
     b.p = nullptr;
     b.bytes = 0;
     const size_t want = bytes + bytes / 4 + 256;
-    ++s.buf_gen; // a captured chain of this slot may hold the old address
+    if (bump_generation)
+        ++s.buf_gen; // a captured chain of this slot may hold the old address
     hipError_t e = hipMalloc(&b.p, want);
     if (e != hipSuccess)
     {
@@ -175,10 +176,10 @@ static void slot_destroy(Slot *s)
                        &s->keep,         &s->patches_raw,  &s->patches_norm,   &s->patches_flag,   &s->patches_norm_r,
                        &s->patches_flag_r, &s->pair_left,  &s->sincos,         &s->scratch_b,      &s->scratch_c,
                        &s->scratch_d,    &s->fetch_pack,   &s->pose_in,        &s->pose_geom,      &s->pose_order,
-                       &s->pose_draw,    &s->pose_hyp,       &s->pose_sel,       &s->pose_casc,       &s->pose_refit,     &s->align_up,       &s->align_ws,       &s->depth_up,       &s->depth_ws,       &s->carry_up,       &s->carry_ws,       &s->cover_up,       &s->cover_ws,       &s->gt_disp,        &s->gt_geom,        &s->gt_flags,
+                       &s->pose_draw,    &s->pose_hyp,       &s->pose_sel,       &s->pose_casc,       &s->pose_refit,     &s->host_up,        &s->align_ws,       &s->depth_ws,       &s->carry_ws,       &s->cover_ws,       &s->gt_disp,       &s->gt_geom,        &s->gt_flags,
                        &s->gt_boxes,     &s->gt_pool_i32,  &s->gt_pool_idx,    &s->gt_rows,        &s->gt_tot,
-                       &s->gt_up,        &s->tgt_geom,     &s->tgt_i32,        &s->tgt_idx,        &s->tgt_u8,
-                       &s->tgt_rows,     &s->tgt_flags,    &s->tgt_tot,        &s->tgt_up,
+                       &s->tgt_geom,     &s->tgt_i32,      &s->tgt_idx,        &s->tgt_u8,
+                       &s->tgt_rows,     &s->tgt_flags,    &s->tgt_tot,
                        &s->tq_prior_geom, &s->tq_prior_live};
     for (GrowBuf *b : bufs)
         free_buf(*b);
@@ -2018,8 +2019,6 @@ static int pinned_grow(ebvo_ctx *ctx, PinnedBuf &b, size_t bytes)
     return EBVO_OK;
 }
 
-static size_t align64(size_t v) { return (v + 63) & ~(size_t)63; }
-
 // Host-to-device copy of caller memory through the context's page-locked staging (`off` bytes into sw_up, which the caller
 // has sized).  The caller's buffers are ordinary pageable memory (a cv::Mat, a std::vector) that it frees or reuses right
 // after the call: copying out of them directly makes the runtime lock their pages for the transfer, and unmapping locked
@@ -2111,7 +2110,7 @@ extern "C" int ebvo_toed_resident(ebvo_ctx *ctx, int which, const uint8_t *img, 
         ctx->last_error = "internal edge capacity exceeded";
         return EBVO_ERR_CAPACITY;
     }
-    const size_t eb = align64(sizeof(ebvo_edge) * (size_t)ws.n_kept), ab = want_all4 ? sizeof(double) * 4 * (size_t)ws.n_total : 0;
+    const size_t eb = round_up64(sizeof(ebvo_edge) * (size_t)ws.n_kept), ab = want_all4 ? sizeof(double) * 4 * (size_t)ws.n_total : 0;
     PinnedBuf &pb = ctx->sw_toed[which];
     if ((rc = pinned_grow(ctx, pb, eb + ab + 64)))
         return rc;
@@ -2165,7 +2164,7 @@ extern "C" int ebvo_epi_candidates_resident(ebvo_ctx *ctx, uint64_t tag_left, ui
     const int nL = s.im[iL].n_kept, nR = s.im[iR].n_kept;
     if (nL > 0 && !lines)
         return EBVO_ERR_ARG;
-    const size_t rb = align64(sizeof(int32_t) * ((size_t)nL + 1));
+    const size_t rb = round_up64(sizeof(int32_t) * ((size_t)nL + 1));
     if ((rc = pinned_grow(ctx, ctx->sw_cand, rb + 64)))
         return rc;
     view->row_ptr = (const int32_t *)ctx->sw_cand.p;
@@ -2216,7 +2215,7 @@ extern "C" int ebvo_epi_candidates_resident(ebvo_ctx *ctx, uint64_t tag_left, ui
     }
     // arena: row_ptr | col_idx | flags | row_ptr_final | col_idx_final (the final list is a sub-list: np bounds it)
     const bool staged = want_orient_flags != 0;
-    const size_t cb = align64(sizeof(int32_t) * (size_t)np), fb = staged ? align64((size_t)np) : 0;
+    const size_t cb = round_up64(sizeof(int32_t) * (size_t)np), fb = staged ? round_up64((size_t)np) : 0;
     const size_t rb2 = staged ? rb : 0, cb2 = staged ? cb : 0;
     {
         // growing the arena moves it: the row offsets already copied are kept
@@ -2337,8 +2336,8 @@ extern "C" int ebvo_ncc_pairs_resident(ebvo_ctx *ctx, uint64_t tag_left, uint64_
         return EBVO_OK;
     // the lists go through page-locked staging and are validated on the way: the kernels index the right patch bank with
     // col_idx and walk the pair arrays with row_ptr
-    const size_t rb = align64(sizeof(int32_t) * ((size_t)nL + 1)), cb = align64(sizeof(int32_t) * (size_t)np);
-    const size_t ib = align64((size_t)h * w);
+    const size_t rb = round_up64(sizeof(int32_t) * ((size_t)nL + 1)), cb = round_up64(sizeof(int32_t) * (size_t)np);
+    const size_t ib = round_up64((size_t)h * w);
     if ((rc = pinned_grow(ctx, ctx->sw_up, rb + cb + 2 * ib + 64)))
         return rc;
     int32_t *h_rp = (int32_t *)ctx->sw_up.p, *h_ci = (int32_t *)((char *)ctx->sw_up.p + rb);
@@ -2371,9 +2370,9 @@ extern "C" int ebvo_ncc_pairs_resident(ebvo_ctx *ctx, uint64_t tag_left, uint64_
         return rc;
     if ((rc = ebvo_grow(ctx, s, s.row_ptr, sizeof(int32_t) * ((size_t)ctx->cap_edges + 1))))
         return rc;
-    const size_t lb = (want & EBVO_NCC_WANT_LEFT_PATCHES) ? align64(sizeof(float) * 98 * (size_t)nL) : 0;
-    const size_t sb = (want & EBVO_NCC_WANT_SIMS) ? align64(sizeof(double) * 4 * (size_t)np) : 0;
-    const size_t bb = align64(sizeof(double) * (size_t)np), kb = align64((size_t)np);
+    const size_t lb = (want & EBVO_NCC_WANT_LEFT_PATCHES) ? round_up64(sizeof(float) * 98 * (size_t)nL) : 0;
+    const size_t sb = (want & EBVO_NCC_WANT_SIMS) ? round_up64(sizeof(double) * 4 * (size_t)np) : 0;
+    const size_t bb = round_up64(sizeof(double) * (size_t)np), kb = round_up64((size_t)np);
     if ((rc = pinned_grow(ctx, ctx->sw_ncc, lb + sb + bb + kb + 64)))
         return rc;
     // the images the NCC samples are the RAW ones the caller passes (src/Stereo_Matches.cpp:562-563); they replace the
@@ -4082,6 +4081,105 @@ static bool pose_cascade_args_ok(const ebvo_pose_params *p, int n_runs, const eb
 
 // Host quads of a GT call, checked, counted and uploaded into slot 0's own pose buffer.  n_listed / n_sel: listed rows and
 // selected quads, counted here; upload = false: only check and count.
+// ---- host-array calls: copies between a caller's arrays and a carved device buffer ----------------------------------------
+// Nothing is copied for an empty array or a null host pointer (an optional argument the caller left out).
+static int copy_up(ebvo_ctx *ctx, hipStream_t st, void *dst_dev, const void *src_host, size_t bytes)
+{
+    if (bytes && src_host)
+        EBVO_HIP(ctx, hipMemcpyAsync(dst_dev, src_host, bytes, hipMemcpyHostToDevice, st));
+    return EBVO_OK;
+}
+
+static int copy_down(ebvo_ctx *ctx, hipStream_t st, void *dst_host, const void *src_dev, size_t bytes)
+{
+    if (bytes && dst_host)
+        EBVO_HIP(ctx, hipMemcpyAsync(dst_host, src_dev, bytes, hipMemcpyDeviceToHost, st));
+    return EBVO_OK;
+}
+
+// The host-array calls run on slot 0's stream with a buffer of their own (host_up): the slot's pair, its results and its
+// armed state stay as they are (unlike host_slot(), whose callers reuse the pair's buffers).
+static int gt_host_slot(ebvo_ctx *ctx, Slot **out)
+{
+    Slot &s = *ctx->slots[0];
+    if (s.in_flight || s.fin_in_flight || s.tq_in_flight)
+    {
+        ctx->last_error = "slot 0 has submitted work in flight; call ebvo_stereo_wait / ebvo_stereo_finalize_wait / ebvo_temporal_match_wait first";
+        return EBVO_ERR_STATE;
+    }
+    *out = &s;
+    return EBVO_OK;
+}
+
+// One host-array call.  It takes slot 0, carves the slot's staging buffer and copies on the slot's stream.  The copies read and
+// write the caller's arrays and the function's locals, so none of them may outlive the call: finish() waits for them, and the
+// destructor does on every return that did not get there.  A local that down() writes into is declared before this object.
+struct HostCall
+{
+    ebvo_ctx *ctx;
+    Slot *s = nullptr;
+    int rc;               // the slot's state first, then the first failure of stage() or of a copy; every helper returns it
+    bool pending = false; // copies were enqueued since the last finish()
+
+    explicit HostCall(ebvo_ctx *c) : ctx(c), rc(gt_host_slot(c, &s)) {}
+    HostCall(const HostCall &) = delete;
+    HostCall &operator=(const HostCall &) = delete;
+    ~HostCall()
+    {
+        if (pending)
+            (void)hipStreamSynchronize(s->stream);
+    }
+
+    Slot &slot() const { return *s; }
+    // the staging buffer holds L.total() bytes; at<T>(offset) is an array of it
+    int stage(const Carve &L)
+    {
+        if (rc)
+            return rc;
+        const hipError_t e = hipSetDevice(ctx->device);
+        if (e != hipSuccess)
+            return rc = ebvo_fail_hip(ctx, e, "hipSetDevice(ctx->device)", __FILE__, __LINE__);
+        return rc = ebvo_grow(ctx, *s, s->host_up, L.total(), false);
+    }
+    template <class T> T *at(size_t offset) const { return (T *)((char *)s->host_up.p + offset); }
+
+    int up(void *dst_dev, const void *src_host, size_t bytes)
+    {
+        pending = true;
+        return rc ? rc : (rc = copy_up(ctx, s->stream, dst_dev, src_host, bytes));
+    }
+    // `rows` rows of row_bytes each, src_pitch bytes apart on the host, packed on the device
+    int up_rows(void *dst_dev, const void *src_host, size_t row_bytes, size_t src_pitch, size_t rows)
+    {
+        pending = true;
+        if (rc)
+            return rc;
+        const hipError_t e = hipMemcpy2DAsync(dst_dev, row_bytes, src_host, src_pitch, row_bytes, rows, hipMemcpyHostToDevice, s->stream);
+        return e == hipSuccess ? rc : (rc = ebvo_fail_hip(ctx, e, "hipMemcpy2DAsync(dst_dev, src_host)", __FILE__, __LINE__));
+    }
+    int down(void *dst_host, const void *src_dev, size_t bytes)
+    {
+        pending = true;
+        return rc ? rc : (rc = copy_down(ctx, s->stream, dst_host, src_dev, bytes));
+    }
+    int fill(void *dst_dev, int byte, size_t bytes)
+    {
+        if (rc || !bytes)
+            return rc;
+        const hipError_t e = hipMemsetAsync(dst_dev, byte, bytes, s->stream);
+        return e == hipSuccess ? rc : (rc = ebvo_fail_hip(ctx, e, "hipMemsetAsync(dst_dev, byte, bytes, stream)", __FILE__, __LINE__));
+    }
+    // wait for the stream whatever happened before; an earlier failure comes before the wait's own
+    int finish()
+    {
+        pending = false;
+        const hipError_t e = hipStreamSynchronize(s->stream);
+        if (!rc && e != hipSuccess)
+            rc = ebvo_fail_hip(ctx, e, "hipStreamSynchronize(stream)", __FILE__, __LINE__);
+        return rc;
+    }
+};
+
 struct PoseHostQuads
 {
     const ebvo_edge *kfL = nullptr, *kfR = nullptr, *cfL = nullptr, *cfR = nullptr;
@@ -4126,30 +4224,33 @@ static int pose_host_quads_upload(ebvo_ctx *ctx, Slot &s, const ebvo_edge *kf_le
 {
     const size_t kz = (size_t)n_kf, nz = (size_t)q->n;
     const size_t ek = sizeof(ebvo_edge) * kz, eq = sizeof(ebvo_edge) * nz, rb = sizeof(int32_t) * (kz + 1);
-    if (int rc = ebvo_grow(ctx, s, s.pose_in, 2 * ek + 2 * eq + rb + kz + nz))
+    Carve L;
+    const size_t o_kfL = L.take(ek), o_kfR = L.take(ek), o_cfL = L.take(eq), o_cfR = L.take(eq), o_rp = L.take(rb), o_on = L.take(kz),
+                 o_tp = L.take(nz);
+    int rc = ebvo_grow(ctx, s, s.pose_in, L.total());
+    if (rc)
         return rc;
-    uint8_t *base = (uint8_t *)s.pose_in.p;
-    q->kfL = (ebvo_edge *)base;
-    q->kfR = (ebvo_edge *)(base + ek);
-    q->cfL = (ebvo_edge *)(base + 2 * ek);
-    q->cfR = (ebvo_edge *)(base + 2 * ek + eq);
-    q->rp = (int32_t *)(base + 2 * ek + 2 * eq);
-    uint8_t *d_on = base + 2 * ek + 2 * eq + rb, *d_tp = d_on + kz;
-    q->on = d_on;
-    q->tp = quad_is_tp ? d_tp : nullptr;
+    char *base = (char *)s.pose_in.p;
+    q->kfL = (ebvo_edge *)(base + o_kfL);
+    q->kfR = (ebvo_edge *)(base + o_kfR);
+    q->cfL = (ebvo_edge *)(base + o_cfL);
+    q->cfR = (ebvo_edge *)(base + o_cfR);
+    q->rp = (int32_t *)(base + o_rp);
+    q->on = (uint8_t *)(base + o_on);
+    q->tp = quad_is_tp ? (uint8_t *)(base + o_tp) : nullptr;
     std::vector<uint8_t> on(kz);
     for (size_t i = 0; i < kz; ++i)
         on[i] = (!row_listed || row_listed[i]) && (!kf_is_tp || kf_is_tp[i]);
     hipStream_t st = s.stream;
-    EBVO_HIP(ctx, hipMemcpyAsync((void *)q->kfL, kf_left, ek, hipMemcpyHostToDevice, st));
-    EBVO_HIP(ctx, hipMemcpyAsync((void *)q->kfR, kf_right, ek, hipMemcpyHostToDevice, st));
-    EBVO_HIP(ctx, hipMemcpyAsync((void *)q->cfL, cf_left, eq, hipMemcpyHostToDevice, st));
-    EBVO_HIP(ctx, hipMemcpyAsync((void *)q->cfR, cf_right, eq, hipMemcpyHostToDevice, st));
-    EBVO_HIP(ctx, hipMemcpyAsync((void *)q->rp, row_ptr, rb, hipMemcpyHostToDevice, st));
-    EBVO_HIP(ctx, hipMemcpyAsync(d_on, on.data(), kz, hipMemcpyHostToDevice, st));
-    if (quad_is_tp)
-        EBVO_HIP(ctx, hipMemcpyAsync(d_tp, quad_is_tp, nz, hipMemcpyHostToDevice, st));
-    EBVO_HIP(ctx, hipStreamSynchronize(st)); // `on` is a local
+    (rc = copy_up(ctx, st, base + o_kfL, kf_left, ek)) || (rc = copy_up(ctx, st, base + o_kfR, kf_right, ek)) ||
+        (rc = copy_up(ctx, st, base + o_cfL, cf_left, eq)) || (rc = copy_up(ctx, st, base + o_cfR, cf_right, eq)) ||
+        (rc = copy_up(ctx, st, base + o_rp, row_ptr, rb)) || (rc = copy_up(ctx, st, base + o_on, on.data(), kz)) ||
+        (rc = copy_up(ctx, st, base + o_tp, quad_is_tp, nz));
+    // `on` is a local and the other sources are the caller's; the pose kernels read the buffer after this returns
+    const hipError_t e = hipStreamSynchronize(st);
+    if (rc)
+        return rc;
+    EBVO_HIP(ctx, e);
     return EBVO_OK;
 }
 
@@ -4356,7 +4457,6 @@ extern "C" int ebvo_temporal_refine_pose(ebvo_ctx *ctx, int slot, const ebvo_ste
 }
 
 // ---- alignment of the pose to the current frame's TOED edges (align_kernels.hip) ---------------------------------------
-static int gt_grow(ebvo_ctx *ctx, Slot &s, GrowBuf &b, size_t bytes); // defined with the ground-truth calls below
 static int gt_host_slot(ebvo_ctx *ctx, Slot **out);
 extern "C" void ebvo_align_default_params(ebvo_align_params *p)
 {
@@ -4450,43 +4550,34 @@ static int align_edges_host(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_
         n1 = 0;
     else if (n1 < 0 || (n1 > 0 && !cf_edges_right))
         return EBVO_ERR_ARG;
-    int rc;
-    Slot *sp;
-    if ((rc = gt_host_slot(ctx, &sp)))
-        return rc;
-    Slot &s = *sp;
+    AlignResult r;
+    HostCall hc(ctx);
+    if (hc.rc)
+        return hc.rc;
     if (n_kf == 0 || n0 + (int64_t)n1 == 0)
     {
         align_nothing(R0, t0, n_kf, out, assoc_left, assoc_right);
         return EBVO_OK;
     }
-    EBVO_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t nz = (size_t)n_kf, o_kfR = sizeof(ebvo_edge) * nz, o_E0 = 2 * o_kfR, o_E1 = o_E0 + sizeof(ebvo_edge) * (size_t)n0,
-                 o_lam = (o_E1 + sizeof(ebvo_edge) * (size_t)n1 + 63) & ~(size_t)63, total = o_lam + (lambda ? sizeof(double) * nz : 0) + 64;
-    if ((rc = gt_grow(ctx, s, s.align_up, total)))
-        return rc;
-    char *base = (char *)s.align_up.p;
-    ebvo_edge *kfL = (ebvo_edge *)base, *kfR = (ebvo_edge *)(base + o_kfR), *E0 = (ebvo_edge *)(base + o_E0), *E1 = (ebvo_edge *)(base + o_E1);
-    hipStream_t st = s.stream;
-    EBVO_HIP(ctx, hipMemcpyAsync(kfL, kf_left, sizeof(ebvo_edge) * nz, hipMemcpyHostToDevice, st));
-    EBVO_HIP(ctx, hipMemcpyAsync(kfR, kf_right, sizeof(ebvo_edge) * nz, hipMemcpyHostToDevice, st));
-    if (n0)
-        EBVO_HIP(ctx, hipMemcpyAsync(E0, cf_edges_left, sizeof(ebvo_edge) * (size_t)n0, hipMemcpyHostToDevice, st));
-    if (n1)
-        EBVO_HIP(ctx, hipMemcpyAsync(E1, cf_edges_right, sizeof(ebvo_edge) * (size_t)n1, hipMemcpyHostToDevice, st));
-    double *d_lam = lambda ? (double *)(base + o_lam) : nullptr;
-    if (lambda)
-        EBVO_HIP(ctx, hipMemcpyAsync(d_lam, lambda, sizeof(double) * nz, hipMemcpyHostToDevice, st));
-    AlignResult r;
+    const size_t nz = (size_t)n_kf, eb = sizeof(ebvo_edge);
+    Carve L;
+    const size_t o_kfL = L.take(eb * nz), o_kfR = L.take(eb * nz), o_E0 = L.take(eb * (size_t)n0), o_E1 = L.take(eb * (size_t)n1),
+                 o_lam = L.take(lambda ? 8 * nz : 0);
+    if (hc.stage(L))
+        return hc.rc;
+    ebvo_edge *kfL = hc.at<ebvo_edge>(o_kfL), *kfR = hc.at<ebvo_edge>(o_kfR), *E0 = hc.at<ebvo_edge>(o_E0), *E1 = hc.at<ebvo_edge>(o_E1);
+    double *d_lam = lambda ? hc.at<double>(o_lam) : nullptr;
+    if (hc.up(kfL, kf_left, eb * nz) || hc.up(kfR, kf_right, eb * nz) || hc.up(E0, cf_edges_left, eb * (size_t)n0) ||
+        hc.up(E1, cf_edges_right, eb * (size_t)n1) || hc.up(d_lam, lambda, 8 * nz))
+        return hc.rc;
     {
-        const TemporalGridScope grid_scope(ctx, s);
-        rc = align_run(ctx, s, kfL, kfR, n_kf, E0, n0, E1, n1, img_w, img_h, cal, params, R0, t0, d_lam, &r, assoc_left, assoc_right);
+        const TemporalGridScope grid_scope(ctx, hc.slot());
+        if (int rc = align_run(ctx, hc.slot(), kfL, kfR, n_kf, E0, n0, E1, n1, img_w, img_h, cal, params, R0, t0, d_lam, &r, assoc_left,
+                               assoc_right))
+            return rc;
     }
-    if (rc)
-    {
-        (void)hipStreamSynchronize(st); // the uploads read the caller's arrays: none of them outlives the call
-        return rc;
-    }
+    if (hc.finish())
+        return hc.rc;
     align_publish(r, n_kf, out);
     return EBVO_OK;
 }
@@ -4642,66 +4733,44 @@ extern "C" int ebvo_depth_refine_edges(ebvo_ctx *ctx, const ebvo_edge *kf_left, 
         n1 = 0;
     else if (n1 < 0 || (n1 > 0 && !cf_edges_right))
         return EBVO_ERR_ARG;
-    int rc;
-    Slot *sp;
-    if ((rc = gt_host_slot(ctx, &sp)))
-        return rc;
-    Slot &s = *sp;
+    DepthRecord r;
+    HostCall hc(ctx);
+    if (hc.rc)
+        return hc.rc;
     if (n_kf == 0)
     {
         memset(out, 0, sizeof *out);
         return EBVO_OK;
     }
-    EBVO_HIP(ctx, hipSetDevice(ctx->device));
     const size_t nz = (size_t)n_kf, eb = sizeof(ebvo_edge);
-    auto up64 = [](size_t v) { return (v + 63) & ~(size_t)63; };
-    // kf_left, kf_right, E0, E1, assoc x 2, lambda, info, n_obs, flags
-    const size_t o_kfR = up64(eb * nz), o_E0 = o_kfR + up64(eb * nz), o_E1 = o_E0 + up64(eb * (size_t)n0), o_a0 = o_E1 + up64(eb * (size_t)n1),
-                 o_a1 = o_a0 + up64(4 * nz), o_lam = o_a1 + up64(4 * nz), o_info = o_lam + up64(8 * nz), o_nobs = o_info + up64(8 * nz),
-                 o_fl = o_nobs + up64(4 * nz), total = o_fl + up64(nz);
-    if ((rc = gt_grow(ctx, s, s.depth_up, total)))
-        return rc;
-    char *base = (char *)s.depth_up.p;
-    ebvo_edge *kfL = (ebvo_edge *)base, *kfR = (ebvo_edge *)(base + o_kfR), *E0 = (ebvo_edge *)(base + o_E0), *E1 = (ebvo_edge *)(base + o_E1);
-    int32_t *a0 = (int32_t *)(base + o_a0), *a1 = (int32_t *)(base + o_a1), *d_nobs = (int32_t *)(base + o_nobs);
-    double *d_lam = (double *)(base + o_lam), *d_info = (double *)(base + o_info);
-    uint8_t *d_fl = (uint8_t *)(base + o_fl);
-    hipStream_t st = s.stream;
-    const bool right = params->cameras > 1 && assoc_right;
-    DepthRecord r;
-    auto enqueue = [&]() -> int {
-        EBVO_HIP(ctx, hipMemcpyAsync(kfL, kf_left, eb * nz, hipMemcpyHostToDevice, st));
-        EBVO_HIP(ctx, hipMemcpyAsync(kfR, kf_right, eb * nz, hipMemcpyHostToDevice, st));
-        if (n0)
-            EBVO_HIP(ctx, hipMemcpyAsync(E0, cf_edges_left, eb * (size_t)n0, hipMemcpyHostToDevice, st));
-        if (n1)
-            EBVO_HIP(ctx, hipMemcpyAsync(E1, cf_edges_right, eb * (size_t)n1, hipMemcpyHostToDevice, st));
-        if (assoc_left)
-            EBVO_HIP(ctx, hipMemcpyAsync(a0, assoc_left, 4 * nz, hipMemcpyHostToDevice, st));
-        if (right)
-            EBVO_HIP(ctx, hipMemcpyAsync(a1, assoc_right, 4 * nz, hipMemcpyHostToDevice, st));
-        if (have_in)
-        {
-            EBVO_HIP(ctx, hipMemcpyAsync(d_lam, lambda_in, 8 * nz, hipMemcpyHostToDevice, st));
-            EBVO_HIP(ctx, hipMemcpyAsync(d_info, info_in, 8 * nz, hipMemcpyHostToDevice, st));
-            EBVO_HIP(ctx, hipMemcpyAsync(d_nobs, n_obs_in, 4 * nz, hipMemcpyHostToDevice, st));
-        }
-        const TemporalGridScope grid_scope(ctx, s);
-        if (int rc2 = depth_run(ctx, s, kfL, kfR, n_kf, E0, n0, E1, n1, assoc_left ? a0 : nullptr, right ? a1 : nullptr, img_w, img_h, cal, params,
-                                R, t, have_in ? d_lam : nullptr, have_in ? d_info : nullptr, have_in ? d_nobs : nullptr, d_lam, d_info,
-                                d_nobs, d_fl, &r))
-            return rc2;
-        EBVO_HIP(ctx, hipMemcpyAsync(lambda, d_lam, 8 * nz, hipMemcpyDeviceToHost, st));
-        EBVO_HIP(ctx, hipMemcpyAsync(info, d_info, 8 * nz, hipMemcpyDeviceToHost, st));
-        EBVO_HIP(ctx, hipMemcpyAsync(n_obs, d_nobs, 4 * nz, hipMemcpyDeviceToHost, st));
-        EBVO_HIP(ctx, hipMemcpyAsync(flags, d_fl, nz, hipMemcpyDeviceToHost, st));
-        return EBVO_OK;
-    };
-    rc = enqueue();
-    const hipError_t e = hipStreamSynchronize(st); // the copies read and write the caller's arrays: none of them outlives the call
-    if (rc)
-        return rc;
-    EBVO_HIP(ctx, e);
+    Carve L;
+    const size_t o_kfL = L.take(eb * nz), o_kfR = L.take(eb * nz), o_E0 = L.take(eb * (size_t)n0), o_E1 = L.take(eb * (size_t)n1),
+                 o_a0 = L.take(4 * nz), o_a1 = L.take(4 * nz), o_lam = L.take(8 * nz), o_info = L.take(8 * nz), o_nobs = L.take(4 * nz),
+                 o_fl = L.take(nz);
+    if (hc.stage(L))
+        return hc.rc;
+    ebvo_edge *kfL = hc.at<ebvo_edge>(o_kfL), *kfR = hc.at<ebvo_edge>(o_kfR), *E0 = hc.at<ebvo_edge>(o_E0), *E1 = hc.at<ebvo_edge>(o_E1);
+    int32_t *a0 = assoc_left ? hc.at<int32_t>(o_a0) : nullptr, *a1 = params->cameras > 1 && assoc_right ? hc.at<int32_t>(o_a1) : nullptr;
+    int32_t *d_nobs = hc.at<int32_t>(o_nobs);
+    double *d_lam = hc.at<double>(o_lam), *d_info = hc.at<double>(o_info);
+    uint8_t *d_fl = hc.at<uint8_t>(o_fl);
+    if (hc.up(kfL, kf_left, eb * nz) || hc.up(kfR, kf_right, eb * nz) || hc.up(E0, cf_edges_left, eb * (size_t)n0) ||
+        hc.up(E1, cf_edges_right, eb * (size_t)n1) || hc.up(a0, assoc_left, 4 * nz) || hc.up(a1, assoc_right, a1 ? 4 * nz : 0) ||
+        hc.up(d_lam, lambda_in, 8 * nz) || hc.up(d_info, info_in, 8 * nz) || hc.up(d_nobs, n_obs_in, 4 * nz))
+        return hc.rc;
+    {
+        const TemporalGridScope grid_scope(ctx, hc.slot());
+        if (int rc = depth_run(ctx, hc.slot(), kfL, kfR, n_kf, E0, n0, E1, n1, a0, a1, img_w, img_h, cal, params, R, t,
+                               have_in ? d_lam : nullptr, have_in ? d_info : nullptr, have_in ? d_nobs : nullptr, d_lam, d_info, d_nobs, d_fl,
+                               &r))
+            return rc;
+    }
+    hc.down(lambda, d_lam, 8 * nz);
+    hc.down(info, d_info, 8 * nz);
+    hc.down(n_obs, d_nobs, 4 * nz);
+    hc.down(flags, d_fl, nz);
+    if (hc.finish())
+        return hc.rc;
     depth_publish(r, n_kf, out);
     return EBVO_OK;
 }
@@ -4907,60 +4976,44 @@ extern "C" int ebvo_depth_carry(ebvo_ctx *ctx, const ebvo_edge *kf_left, const e
     const int have_in = (lambda_in ? 1 : 0) + (info_in ? 1 : 0) + (n_obs_in ? 1 : 0);
     if (have_in != 0 && have_in != 3)
         return EBVO_ERR_ARG;
-    int rc;
-    Slot *sp;
-    if ((rc = gt_host_slot(ctx, &sp)))
-        return rc;
-    Slot &s = *sp;
     int32_t counts[CARRY_COUNTS] = {0, 0, 0, 0, 0, 0};
+    HostCall hc(ctx);
+    if (hc.rc)
+        return hc.rc;
     if (n_new == 0)
     {
         carry_publish(counts, n_old, n_new, out);
         return EBVO_OK;
     }
-    EBVO_HIP(ctx, hipSetDevice(ctx->device));
     const bool assoc = have_in && n_old > 0;
     const size_t no = assoc ? (size_t)n_old : 0, nn = (size_t)n_new, eb = sizeof(ebvo_edge);
-    auto up64 = [](size_t v) { return (v + 63) & ~(size_t)63; };
     // old mates and their state, new mates, the outgoing state
-    const size_t o_oR = up64(eb * no), o_li = o_oR + up64(eb * no), o_ii = o_li + up64(8 * no), o_ni = o_ii + up64(8 * no),
-                 o_nL = o_ni + up64(4 * no), o_nR = o_nL + up64(eb * nn), o_lam = o_nR + up64(eb * nn), o_info = o_lam + up64(8 * nn),
-                 o_nobs = o_info + up64(8 * nn), o_src = o_nobs + up64(4 * nn), o_fl = o_src + up64(4 * nn), total = o_fl + up64(nn);
-    if ((rc = gt_grow(ctx, s, s.carry_up, total)))
-        return rc;
-    char *base = (char *)s.carry_up.p;
-    ebvo_edge *oL = (ebvo_edge *)base, *oR = (ebvo_edge *)(base + o_oR), *nL = (ebvo_edge *)(base + o_nL), *nR = (ebvo_edge *)(base + o_nR);
-    double *d_li = (double *)(base + o_li), *d_ii = (double *)(base + o_ii), *d_lam = (double *)(base + o_lam), *d_info = (double *)(base + o_info);
-    int32_t *d_ni = (int32_t *)(base + o_ni), *d_nobs = (int32_t *)(base + o_nobs), *d_src = (int32_t *)(base + o_src);
-    uint8_t *d_fl = (uint8_t *)(base + o_fl);
-    hipStream_t st = s.stream;
-    auto enqueue = [&]() -> int {
-        if (assoc)
-        {
-            EBVO_HIP(ctx, hipMemcpyAsync(oL, kf_left, eb * no, hipMemcpyHostToDevice, st));
-            EBVO_HIP(ctx, hipMemcpyAsync(oR, kf_right, eb * no, hipMemcpyHostToDevice, st));
-            EBVO_HIP(ctx, hipMemcpyAsync(d_li, lambda_in, 8 * no, hipMemcpyHostToDevice, st));
-            EBVO_HIP(ctx, hipMemcpyAsync(d_ii, info_in, 8 * no, hipMemcpyHostToDevice, st));
-            EBVO_HIP(ctx, hipMemcpyAsync(d_ni, n_obs_in, 4 * no, hipMemcpyHostToDevice, st));
-        }
-        EBVO_HIP(ctx, hipMemcpyAsync(nL, new_left, eb * nn, hipMemcpyHostToDevice, st));
-        EBVO_HIP(ctx, hipMemcpyAsync(nR, new_right, eb * nn, hipMemcpyHostToDevice, st));
-        const TemporalGridScope grid_scope(ctx, s);
-        if (int rc2 = carry_run(ctx, s, oL, oR, n_old, assoc ? d_li : nullptr, assoc ? d_ii : nullptr, assoc ? d_ni : nullptr, nL, nR, n_new, img_w,
-                                img_h, cal, params, R, t, d_lam, d_info, d_nobs, d_fl, d_src, counts))
-            return rc2;
-        EBVO_HIP(ctx, hipMemcpyAsync(lambda, d_lam, 8 * nn, hipMemcpyDeviceToHost, st));
-        EBVO_HIP(ctx, hipMemcpyAsync(info, d_info, 8 * nn, hipMemcpyDeviceToHost, st));
-        EBVO_HIP(ctx, hipMemcpyAsync(n_obs, d_nobs, 4 * nn, hipMemcpyDeviceToHost, st));
-        EBVO_HIP(ctx, hipMemcpyAsync(flags, d_fl, nn, hipMemcpyDeviceToHost, st));
-        EBVO_HIP(ctx, hipMemcpyAsync(src_index, d_src, 4 * nn, hipMemcpyDeviceToHost, st));
-        return EBVO_OK;
-    };
-    rc = enqueue();
-    const hipError_t e = hipStreamSynchronize(st); // the copies read and write the caller's arrays: none of them outlives the call
-    if (rc)
-        return rc;
-    EBVO_HIP(ctx, e);
+    Carve L;
+    const size_t o_oL = L.take(eb * no), o_oR = L.take(eb * no), o_li = L.take(8 * no), o_ii = L.take(8 * no), o_ni = L.take(4 * no),
+                 o_nL = L.take(eb * nn), o_nR = L.take(eb * nn), o_lam = L.take(8 * nn), o_info = L.take(8 * nn), o_nobs = L.take(4 * nn),
+                 o_src = L.take(4 * nn), o_fl = L.take(nn);
+    if (hc.stage(L))
+        return hc.rc;
+    ebvo_edge *oL = hc.at<ebvo_edge>(o_oL), *oR = hc.at<ebvo_edge>(o_oR), *nL = hc.at<ebvo_edge>(o_nL), *nR = hc.at<ebvo_edge>(o_nR);
+    double *d_li = hc.at<double>(o_li), *d_ii = hc.at<double>(o_ii), *d_lam = hc.at<double>(o_lam), *d_info = hc.at<double>(o_info);
+    int32_t *d_ni = hc.at<int32_t>(o_ni), *d_nobs = hc.at<int32_t>(o_nobs), *d_src = hc.at<int32_t>(o_src);
+    uint8_t *d_fl = hc.at<uint8_t>(o_fl);
+    if (hc.up(oL, kf_left, eb * no) || hc.up(oR, kf_right, eb * no) || hc.up(d_li, lambda_in, 8 * no) || hc.up(d_ii, info_in, 8 * no) ||
+        hc.up(d_ni, n_obs_in, 4 * no) || hc.up(nL, new_left, eb * nn) || hc.up(nR, new_right, eb * nn))
+        return hc.rc;
+    {
+        const TemporalGridScope grid_scope(ctx, hc.slot());
+        if (int rc = carry_run(ctx, hc.slot(), oL, oR, n_old, assoc ? d_li : nullptr, assoc ? d_ii : nullptr, assoc ? d_ni : nullptr, nL, nR,
+                               n_new, img_w, img_h, cal, params, R, t, d_lam, d_info, d_nobs, d_fl, d_src, counts))
+            return rc;
+    }
+    hc.down(lambda, d_lam, 8 * nn);
+    hc.down(info, d_info, 8 * nn);
+    hc.down(n_obs, d_nobs, 4 * nn);
+    hc.down(flags, d_fl, nn);
+    hc.down(src_index, d_src, 4 * nn);
+    if (hc.finish())
+        return hc.rc;
     carry_publish(counts, n_old, n_new, out);
     return EBVO_OK;
 }
@@ -5172,42 +5225,33 @@ extern "C" int ebvo_keyframe_cover_edges(ebvo_ctx *ctx, const ebvo_edge *kf_left
     if (!ctx || !cover_args_ok(cal, params, R, t, out, img_w, img_h) || n_kf < 0 || n0 < 0 || (n_kf > 0 && (!kf_left || !kf_right)) ||
         (n0 > 0 && !cf_edges_left))
         return EBVO_ERR_ARG;
-    int rc;
-    Slot *sp;
-    if ((rc = gt_host_slot(ctx, &sp)))
-        return rc;
-    Slot &s = *sp;
+    ebvo_keyframe_cover rec;
+    HostCall hc(ctx);
+    if (hc.rc)
+        return hc.rc;
     if (n_kf == 0 || n0 == 0)
     {
         cover_nothing(params, n_kf, n0, img_w, img_h, out, flags, assoc, disp, explained, cell_edges, cell_explained);
         return EBVO_OK;
     }
-    EBVO_HIP(ctx, hipSetDevice(ctx->device));
     const size_t nz = (size_t)n_kf, eb = sizeof(ebvo_edge);
-    auto up64 = [](size_t v) { return (v + 63) & ~(size_t)63; };
-    const size_t o_kfR = up64(eb * nz), o_E0 = o_kfR + up64(eb * nz), o_lam = o_E0 + up64(eb * (size_t)n0), total = o_lam + up64(8 * nz);
-    if ((rc = gt_grow(ctx, s, s.cover_up, total)))
-        return rc;
-    char *base = (char *)s.cover_up.p;
-    ebvo_edge *kfL = (ebvo_edge *)base, *kfR = (ebvo_edge *)(base + o_kfR), *E0 = (ebvo_edge *)(base + o_E0);
-    double *d_lam = lambda ? (double *)(base + o_lam) : nullptr;
-    hipStream_t st = s.stream;
-    ebvo_keyframe_cover rec;
-    auto enqueue = [&]() -> int {
-        EBVO_HIP(ctx, hipMemcpyAsync(kfL, kf_left, eb * nz, hipMemcpyHostToDevice, st));
-        EBVO_HIP(ctx, hipMemcpyAsync(kfR, kf_right, eb * nz, hipMemcpyHostToDevice, st));
-        EBVO_HIP(ctx, hipMemcpyAsync(E0, cf_edges_left, eb * (size_t)n0, hipMemcpyHostToDevice, st));
-        if (lambda)
-            EBVO_HIP(ctx, hipMemcpyAsync(d_lam, lambda, 8 * nz, hipMemcpyHostToDevice, st));
-        const TemporalGridScope grid_scope(ctx, s);
-        return cover_run(ctx, s, kfL, kfR, n_kf, d_lam, E0, n0, img_w, img_h, cal, params, R, t, &rec, flags, assoc, disp, explained, cell_edges,
-                         cell_explained);
-    };
-    rc = enqueue();
-    const hipError_t e = hipStreamSynchronize(st); // the copies read and write the caller's arrays: none of them outlives the call
-    if (rc)
-        return rc;
-    EBVO_HIP(ctx, e);
+    Carve L;
+    const size_t o_kfL = L.take(eb * nz), o_kfR = L.take(eb * nz), o_E0 = L.take(eb * (size_t)n0), o_lam = L.take(8 * nz);
+    if (hc.stage(L))
+        return hc.rc;
+    ebvo_edge *kfL = hc.at<ebvo_edge>(o_kfL), *kfR = hc.at<ebvo_edge>(o_kfR), *E0 = hc.at<ebvo_edge>(o_E0);
+    double *d_lam = lambda ? hc.at<double>(o_lam) : nullptr;
+    if (hc.up(kfL, kf_left, eb * nz) || hc.up(kfR, kf_right, eb * nz) || hc.up(E0, cf_edges_left, eb * (size_t)n0) ||
+        hc.up(d_lam, lambda, 8 * nz))
+        return hc.rc;
+    {
+        const TemporalGridScope grid_scope(ctx, hc.slot());
+        if (int rc = cover_run(ctx, hc.slot(), kfL, kfR, n_kf, d_lam, E0, n0, img_w, img_h, cal, params, R, t, &rec, flags, assoc, disp,
+                               explained, cell_edges, cell_explained))
+            return rc;
+    }
+    if (hc.finish())
+        return hc.rc;
     *out = rec;
     return EBVO_OK;
 }
@@ -5738,27 +5782,6 @@ static bool gt_params_ok(const ebvo_gt_params *p)
     return p->orient_gate_deg >= 0 && p->pool_epi_thr >= 0 && p->pool_dist >= 0 && p->pool_orient_deg >= 0 && p->tp_dist >= 0; // (false for NaN)
 }
 
-// ebvo_grow without the generation bump: no captured pair chain ever holds a ground-truth buffer
-static int gt_grow(ebvo_ctx *ctx, Slot &s, GrowBuf &b, size_t bytes)
-{
-    if (bytes <= b.bytes && b.p)
-        return EBVO_OK;
-    EBVO_HIP(ctx, hipStreamSynchronize(s.stream));
-    if (b.p)
-        (void)hipFree(b.p);
-    b.p = nullptr;
-    b.bytes = 0;
-    const size_t want = bytes + bytes / 4 + 256;
-    if (hipMalloc(&b.p, want) != hipSuccess)
-    {
-        (void)hipGetLastError();
-        ctx->last_error = "hipMalloc failed (out of device memory)";
-        return EBVO_ERR_NOMEM;
-    }
-    b.bytes = want;
-    return EBVO_OK;
-}
-
 // The four doubles of a stage (:365-368) from the per-row (n, tp): plain sequential sums in row order, as std::accumulate
 // forms them.  drop_empty: the rows of remove_empty_clusters (:1526).  The integer fields are filled too (host values).
 static void gt_stage_doubles(const int32_t *rows, const uint8_t *focused, int nL, bool drop_empty, ebvo_gt_stage *st)
@@ -5825,11 +5848,11 @@ extern "C" int ebvo_stereo_set_gt(ebvo_ctx *ctx, int slot, const float *disp, in
     const size_t nLz = (size_t)nL;
     s.gt_armed = false;
     s.gt_fin_enq = s.gt_fin_done = false;
-    if ((rc = gt_grow(ctx, s, s.gt_disp, sizeof(float) * (size_t)h * w)) || (rc = gt_grow(ctx, s, s.gt_geom, sizeof(double) * 8 * (nLz + 1))) ||
-        (rc = gt_grow(ctx, s, s.gt_flags, 2 * (nLz + 1))) || (rc = gt_grow(ctx, s, s.gt_boxes, gt_boxes_bytes(nR))) ||
-        (rc = gt_grow(ctx, s, s.gt_pool_i32, sizeof(int32_t) * 2 * (nLz + 1))) ||
-        (rc = gt_grow(ctx, s, s.gt_rows, sizeof(int32_t) * 2 * (nLz + 1) * EBVO_GT_NUM_STAGES)) ||
-        (rc = gt_grow(ctx, s, s.gt_tot, sizeof(unsigned long long) * 8 * EBVO_GT_NUM_STAGES)))
+    if ((rc = ebvo_grow(ctx, s, s.gt_disp, sizeof(float) * (size_t)h * w, false)) || (rc = ebvo_grow(ctx, s, s.gt_geom, sizeof(double) * 8 * (nLz + 1), false)) ||
+        (rc = ebvo_grow(ctx, s, s.gt_flags, 2 * (nLz + 1), false)) || (rc = ebvo_grow(ctx, s, s.gt_boxes, gt_boxes_bytes(nR), false)) ||
+        (rc = ebvo_grow(ctx, s, s.gt_pool_i32, sizeof(int32_t) * 2 * (nLz + 1), false)) ||
+        (rc = ebvo_grow(ctx, s, s.gt_rows, sizeof(int32_t) * 2 * (nLz + 1) * EBVO_GT_NUM_STAGES, false)) ||
+        (rc = ebvo_grow(ctx, s, s.gt_tot, sizeof(unsigned long long) * 8 * EBVO_GT_NUM_STAGES, false)))
         return rc;
     hipStream_t st = s.stream;
     s.gt_nL = nL;
@@ -5859,7 +5882,7 @@ extern "C" int ebvo_stereo_set_gt(ebvo_ctx *ctx, int slot, const float *disp, in
         EBVO_HIP(ctx, hipMemcpyAsync(h_valid.data(), valid, nLz, hipMemcpyDeviceToHost, st));
         EBVO_HIP(ctx, hipStreamSynchronize(st));
         const int64_t n_pool = s.gt_h_pool_rp[nLz];
-        if ((rc = gt_grow(ctx, s, s.gt_pool_idx, sizeof(int32_t) * ((size_t)n_pool + 1))))
+        if ((rc = ebvo_grow(ctx, s, s.gt_pool_idx, sizeof(int32_t) * ((size_t)n_pool + 1), false)))
             return rc;
         if ((rc = gt_pool_enqueue(ctx, s, true, s.im[0].edges, nL, s.im[1].edges, nR, (const double *)s.lines.p, gt_xy, valid,
                                   s.gt_boxes.p, &P, cnt, prp, (int32_t *)s.gt_pool_idx.p, focused)) ||
@@ -6039,20 +6062,6 @@ extern "C" int ebvo_stereo_gt_metrics(ebvo_ctx *ctx, int slot, ebvo_gt_stage *st
     return EBVO_GT_NUM_STAGES;
 }
 
-// The host-array calls run on slot 0's stream with a buffer of their own (gt_up): the slot's pair, its results and its
-// armed state stay as they are (unlike host_slot(), whose callers reuse the pair's buffers).
-static int gt_host_slot(ebvo_ctx *ctx, Slot **out)
-{
-    Slot &s = *ctx->slots[0];
-    if (s.in_flight || s.fin_in_flight || s.tq_in_flight)
-    {
-        ctx->last_error = "slot 0 has submitted work in flight; call ebvo_stereo_wait / ebvo_stereo_finalize_wait / ebvo_temporal_match_wait first";
-        return EBVO_ERR_STATE;
-    }
-    *out = &s;
-    return EBVO_OK;
-}
-
 extern "C" int ebvo_gt_locate(ebvo_ctx *ctx, const ebvo_edge *edges, int n, const float *disp, int h, int w, ptrdiff_t stride_elems,
                               const ebvo_stereo_calib *calib, const ebvo_gt_params *params, uint8_t *valid, double *gt_xy,
                               double *gamma_left, double *gamma_right)
@@ -6063,39 +6072,36 @@ extern "C" int ebvo_gt_locate(ebvo_ctx *ctx, const ebvo_edge *edges, int n, cons
         P = *params;
     if (!ctx || n < 0 || !disp || !calib || h <= 0 || w <= 0 || stride_elems < w || !gt_params_ok(&P) || (n > 0 && (!edges || !valid)))
         return EBVO_ERR_ARG;
-    EBVO_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
-    Slot *sp;
-    if ((rc = gt_host_slot(ctx, &sp)))
-        return rc;
-    Slot &s = *sp;
+    HostCall hc(ctx);
+    if (hc.rc)
+        return hc.rc;
     if (n == 0)
         return EBVO_OK;
     const size_t nz = (size_t)n;
-    // one buffer of the call's own: edges, the eight doubles per edge, the map, the valid flags
-    const size_t o_geom = sizeof(ebvo_edge) * nz, o_disp = o_geom + sizeof(double) * 8 * nz,
-                 o_valid = o_disp + sizeof(float) * (size_t)h * w;
-    if ((rc = gt_grow(ctx, s, s.gt_up, o_valid + nz)))
+    // edges, the eight doubles per edge, the map, the valid flags
+    Carve L;
+    const size_t o_e = L.take(sizeof(ebvo_edge) * nz), o_xy = L.take(sizeof(double) * 2 * nz), o_gl = L.take(sizeof(double) * 3 * nz),
+                 o_gr = L.take(sizeof(double) * 3 * nz), o_disp = L.take(sizeof(float) * (size_t)h * w), o_valid = L.take(nz);
+    if (hc.stage(L))
+        return hc.rc;
+    ebvo_edge *d_e = hc.at<ebvo_edge>(o_e);
+    double *d_xy = hc.at<double>(o_xy), *d_gl = hc.at<double>(o_gl), *d_gr = hc.at<double>(o_gr);
+    float *d_disp = hc.at<float>(o_disp);
+    uint8_t *d_valid = hc.at<uint8_t>(o_valid);
+    if (hc.up_rows(d_disp, disp, sizeof(float) * (size_t)w, sizeof(float) * (size_t)stride_elems, (size_t)h) ||
+        hc.up(d_e, edges, sizeof(ebvo_edge) * nz))
+        return hc.rc;
+    if (int rc = gt_locate_enqueue(ctx, hc.slot(), d_e, n, d_disp, h, w, w, calib, P.orient_gate_deg, d_valid, d_xy, d_gl, d_gr))
         return rc;
-    hipStream_t st = s.stream;
-    char *base = (char *)s.gt_up.p;
-    double *d_xy = (double *)(base + o_geom), *d_gl = d_xy + 2 * nz, *d_gr = d_gl + 3 * nz;
-    EBVO_HIP(ctx, hipMemcpy2DAsync(base + o_disp, sizeof(float) * (size_t)w, disp, sizeof(float) * (size_t)stride_elems,
-                                   sizeof(float) * (size_t)w, (size_t)h, hipMemcpyHostToDevice, st));
-    EBVO_HIP(ctx, hipMemcpyAsync(base, edges, sizeof(ebvo_edge) * nz, hipMemcpyHostToDevice, st));
-    if ((rc = gt_locate_enqueue(ctx, s, (const ebvo_edge *)base, n, (const float *)(base + o_disp), h, w, w, calib, P.orient_gate_deg,
-                                (uint8_t *)(base + o_valid), d_xy, d_gl, d_gr)))
-        return rc;
-    EBVO_HIP(ctx, hipMemcpyAsync(valid, base + o_valid, nz, hipMemcpyDeviceToHost, st));
-    if (gt_xy)
-        EBVO_HIP(ctx, hipMemcpyAsync(gt_xy, d_xy, sizeof(double) * 2 * nz, hipMemcpyDeviceToHost, st));
-    if (gamma_left)
-        EBVO_HIP(ctx, hipMemcpyAsync(gamma_left, d_gl, sizeof(double) * 3 * nz, hipMemcpyDeviceToHost, st));
-    if (gamma_right)
-        EBVO_HIP(ctx, hipMemcpyAsync(gamma_right, d_gr, sizeof(double) * 3 * nz, hipMemcpyDeviceToHost, st));
-    EBVO_HIP(ctx, hipStreamSynchronize(st));
-    return EBVO_OK;
+    hc.down(valid, d_valid, nz);
+    hc.down(gt_xy, d_xy, sizeof(double) * 2 * nz);
+    hc.down(gamma_left, d_gl, sizeof(double) * 3 * nz);
+    hc.down(gamma_right, d_gr, sizeof(double) * 3 * nz);
+    return hc.finish();
 }
+
+static int host_stage_tail(HostCall &hc, const int32_t *d_rows, const unsigned long long *d_tot, int n, const uint8_t *on, bool temporal,
+                           int32_t *n_tp, ebvo_gt_stage *stage_out); // defined with the temporal stages below
 
 extern "C" int ebvo_gt_evaluate_rows(ebvo_ctx *ctx, const int32_t *row_ptr, const ebvo_edge *cand_edges, int nL, const uint8_t *focused,
                                      const double *gt_xy, double tp_dist, int32_t *n_tp, ebvo_gt_stage *stage_out)
@@ -6103,48 +6109,31 @@ extern "C" int ebvo_gt_evaluate_rows(ebvo_ctx *ctx, const int32_t *row_ptr, cons
     int64_t np = 0;
     if (!ctx || !stage_out || !(tp_dist >= 0) || check_csr(row_ptr, nL, &np) || (nL > 0 && (!focused || !gt_xy)) || (np > 0 && !cand_edges))
         return EBVO_ERR_ARG;
-    EBVO_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
-    Slot *sp;
-    if ((rc = gt_host_slot(ctx, &sp)))
-        return rc;
-    Slot &s = *sp;
+    HostCall hc(ctx);
+    if (hc.rc)
+        return hc.rc;
     memset(stage_out, 0, sizeof *stage_out);
     stage_out->present = 1;
     const size_t nLz = (size_t)nL, npz = (size_t)np;
-    // one buffer of the call's own: candidates, gt_xy, the five totals, the (n, tp) rows, row_ptr, focused
-    const size_t o_xy = sizeof(ebvo_edge) * (npz + 1), o_tot = o_xy + sizeof(double) * 2 * (nLz + 1),
-                 o_rows = o_tot + sizeof(unsigned long long) * 8, o_rp = o_rows + sizeof(int32_t) * 2 * (nLz + 1),
-                 o_f = o_rp + sizeof(int32_t) * (nLz + 2), total = o_f + nLz + 8;
-    if ((rc = gt_grow(ctx, s, s.gt_up, total)))
+    // candidates, gt_xy, the five totals, the (n, tp) rows, row_ptr, focused
+    Carve L;
+    const size_t o_cand = L.take(sizeof(ebvo_edge) * (npz + 1)), o_xy = L.take(sizeof(double) * 2 * (nLz + 1)),
+                 o_tot = L.take(sizeof(unsigned long long) * 8), o_rows = L.take(sizeof(int32_t) * 2 * (nLz + 1)),
+                 o_rp = L.take(sizeof(int32_t) * (nLz + 2)), o_f = L.take(nLz);
+    if (hc.stage(L))
+        return hc.rc;
+    ebvo_edge *d_cand = hc.at<ebvo_edge>(o_cand);
+    double *d_xy = hc.at<double>(o_xy);
+    unsigned long long *d_tot = hc.at<unsigned long long>(o_tot);
+    int32_t *d_rows = hc.at<int32_t>(o_rows), *d_rp = hc.at<int32_t>(o_rp);
+    uint8_t *d_f = hc.at<uint8_t>(o_f);
+    // without rows nothing below writes the totals
+    if (hc.fill(d_tot, 0, sizeof(unsigned long long) * 8) || hc.up(d_cand, cand_edges, sizeof(ebvo_edge) * npz) ||
+        hc.up(d_rp, row_ptr, sizeof(int32_t) * (nLz + 1)) || hc.up(d_xy, gt_xy, sizeof(double) * 2 * nLz) || hc.up(d_f, focused, nLz))
+        return hc.rc;
+    if (int rc = gt_rows_enqueue(ctx, hc.slot(), d_rp, d_cand, nullptr, nullptr, nullptr, d_xy, d_f, nL, tp_dist, d_rows, d_tot))
         return rc;
-    hipStream_t st = s.stream;
-    char *base = (char *)s.gt_up.p;
-    int32_t *d_rows = (int32_t *)(base + o_rows);
-    unsigned long long *d_tot = (unsigned long long *)(base + o_tot);
-    if (np)
-        EBVO_HIP(ctx, hipMemcpyAsync(base, cand_edges, sizeof(ebvo_edge) * npz, hipMemcpyHostToDevice, st));
-    EBVO_HIP(ctx, hipMemcpyAsync(base + o_rp, row_ptr, sizeof(int32_t) * (nLz + 1), hipMemcpyHostToDevice, st));
-    if (nL)
-    {
-        EBVO_HIP(ctx, hipMemcpyAsync(base + o_xy, gt_xy, sizeof(double) * 2 * nLz, hipMemcpyHostToDevice, st));
-        EBVO_HIP(ctx, hipMemcpyAsync(base + o_f, focused, nLz, hipMemcpyHostToDevice, st));
-    }
-    if ((rc = gt_rows_enqueue(ctx, s, (const int32_t *)(base + o_rp), (const ebvo_edge *)base, nullptr, nullptr, nullptr,
-                              (const double *)(base + o_xy), (const uint8_t *)(base + o_f), nL, tp_dist, d_rows, d_tot)))
-        return rc;
-    std::vector<int32_t> rows(2 * nLz + 1);
-    unsigned long long tot[5] = {0, 0, 0, 0, 0};
-    if (nL)
-        EBVO_HIP(ctx, hipMemcpyAsync(rows.data(), d_rows, sizeof(int32_t) * 2 * nLz, hipMemcpyDeviceToHost, st));
-    EBVO_HIP(ctx, hipMemcpyAsync(tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, st));
-    EBVO_HIP(ctx, hipStreamSynchronize(st));
-    gt_stage_doubles(rows.data(), focused, nL, false, stage_out);
-    if ((rc = gt_totals_agree(ctx, *stage_out, tot, false)))
-        return rc;
-    if (n_tp && nL)
-        memcpy(n_tp, rows.data(), sizeof(int32_t) * 2 * nLz);
-    return EBVO_OK;
+    return host_stage_tail(hc, d_rows, d_tot, nL, focused, /*temporal=*/false, n_tp, stage_out);
 }
 
 // ---- temporal ground truth from a relative pose (tgt_kernels.hip) -------------------------------------------------------
@@ -6324,10 +6313,10 @@ extern "C" int ebvo_temporal_set_gt(ebvo_ctx *ctx, int slot, const double R[9], 
     }
     const size_t n_flags = s.tgt_flag_off[EBVO_TGT_REFINE] + (size_t)s.tgt_flag_n[EBVO_TGT_REFINE];
     int rc;
-    if ((rc = gt_grow(ctx, s, s.tgt_geom, sizeof(double) * 9 * nz + 64)) || (rc = gt_grow(ctx, s, s.tgt_u8, 3 * nz + 64)) ||
-        (rc = gt_grow(ctx, s, s.tgt_i32, sizeof(int32_t) * 2 * (nz + 1))) ||
-        (rc = gt_grow(ctx, s, s.tgt_rows, sizeof(int32_t) * 2 * npos * nz + 64)) || (rc = gt_grow(ctx, s, s.tgt_flags, n_flags + 64)) ||
-        (rc = gt_grow(ctx, s, s.tgt_tot, sizeof(unsigned long long) * 8 * npos)))
+    if ((rc = ebvo_grow(ctx, s, s.tgt_geom, sizeof(double) * 9 * nz + 64, false)) || (rc = ebvo_grow(ctx, s, s.tgt_u8, 3 * nz + 64, false)) ||
+        (rc = ebvo_grow(ctx, s, s.tgt_i32, sizeof(int32_t) * 2 * (nz + 1), false)) ||
+        (rc = ebvo_grow(ctx, s, s.tgt_rows, sizeof(int32_t) * 2 * npos * nz + 64, false)) || (rc = ebvo_grow(ctx, s, s.tgt_flags, n_flags + 64, false)) ||
+        (rc = ebvo_grow(ctx, s, s.tgt_tot, sizeof(unsigned long long) * 8 * npos, false)))
         return rc;
     hipStream_t st = s.stream;
     double *pl = (double *)s.tgt_geom.p, *pr = pl + 2 * nz, *ol = pr + 2 * nz, *orr = ol + nz, *gamma = orr + nz;
@@ -6371,7 +6360,7 @@ extern "C" int ebvo_temporal_set_gt(ebvo_ctx *ctx, int slot, const double R[9], 
         return EBVO_ERR_CAPACITY;
     }
     const int64_t n_ver = h_rp[n_kf];
-    if ((rc = gt_grow(ctx, s, s.tgt_idx, sizeof(int32_t) * (size_t)(n_ver + 1))))
+    if ((rc = ebvo_grow(ctx, s, s.tgt_idx, sizeof(int32_t) * (size_t)(n_ver + 1), false)))
         return rc;
     s.tgt_h_on.assign(nz, 0);
     if (walk) // otherwise the offsets are the zeros written above; h_rp outlives the copy through the synchronise below
@@ -6497,6 +6486,30 @@ static int tgt_totals_agree(ebvo_ctx *ctx, const ebvo_gt_stage &g, const unsigne
         return EBVO_OK;
     ctx->last_error = "temporal ground-truth stage " + std::to_string(g.stage) + ": the device totals differ from the per-row counts";
     return EBVO_ERR_HIP;
+}
+
+// The tail of a host-array stage call: the (n, tp) rows and the five totals come back, the call ends, the stage's doubles are
+// formed from the rows (the stereo stage's or the temporal one's, over the rows that `on` keeps) and checked against the
+// totals.  The locals the copies write into are safe here: finish() waits on every path before they go.
+static int host_stage_tail(HostCall &hc, const int32_t *d_rows, const unsigned long long *d_tot, int n, const uint8_t *on, bool temporal,
+                           int32_t *n_tp, ebvo_gt_stage *stage_out)
+{
+    const size_t nz = (size_t)n;
+    std::vector<int32_t> rows(2 * nz + 1);
+    unsigned long long tot[5] = {0, 0, 0, 0, 0};
+    hc.down(rows.data(), d_rows, sizeof(int32_t) * 2 * nz);
+    hc.down(tot, d_tot, sizeof tot);
+    if (hc.finish())
+        return hc.rc;
+    if (temporal)
+        tgt_stage_doubles(rows.data(), on, n, stage_out);
+    else
+        gt_stage_doubles(rows.data(), on, n, false, stage_out);
+    if (int rc = temporal ? tgt_totals_agree(hc.ctx, *stage_out, tot) : gt_totals_agree(hc.ctx, *stage_out, tot, false))
+        return rc;
+    if (n_tp && n)
+        memcpy(n_tp, rows.data(), sizeof(int32_t) * 2 * nz);
+    return EBVO_OK;
 }
 
 extern "C" int ebvo_temporal_gt_metrics(ebvo_ctx *ctx, int slot, ebvo_gt_stage *stages)
@@ -6706,67 +6719,75 @@ extern "C" int ebvo_tgt_grid_rows(ebvo_ctx *ctx, const ebvo_edge *kf_left, const
     const int64_t gw64 = ((int64_t)img_w + cell_size - 1) / cell_size, gh64 = ((int64_t)img_h + cell_size - 1) / cell_size;
     if (gw64 * gh64 > (1 << 26) || gw64 > 30000 || gh64 > 30000) // the cells of a mate are 16-bit
         return EBVO_ERR_ARG;
-    EBVO_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
-    Slot *sp;
-    if ((rc = gt_host_slot(ctx, &sp)))
-        return rc;
-    Slot &s = *sp;
+    HostCall hc(ctx);
+    if (hc.rc)
+        return hc.rc;
     memset(stage_out, 0, sizeof *stage_out);
     stage_out->stage = EBVO_TGT_GRID;
     stage_out->present = 1;
     const int gw = (int)gw64, gh = (int)gh64;
-    const size_t nz = (size_t)n_kf, ncz = (size_t)n_cf;
-    // one buffer of the call's own: the four mate lists, both projections, the totals, the (n, tp) rows, row_on, the grid
-    const size_t o_kfR = sizeof(ebvo_edge) * nz, o_cfL = 2 * sizeof(ebvo_edge) * nz, o_cfR = o_cfL + sizeof(ebvo_edge) * ncz,
-                 o_pl = o_cfR + sizeof(ebvo_edge) * ncz, o_pr = o_pl + sizeof(double) * 2 * nz, o_tot = o_pr + sizeof(double) * 2 * nz,
-                 o_rows = o_tot + sizeof(unsigned long long) * 8, o_on = o_rows + sizeof(int32_t) * 2 * (nz + 1),
-                 o_grid = (o_on + nz + 63) & ~(size_t)63, total = o_grid + match_temporal_grid_bytes(n_cf, gw * gh) + 64;
-    if ((rc = gt_grow(ctx, s, s.tgt_up, total)))
-        return rc;
-    hipStream_t st = s.stream;
-    char *base = (char *)s.tgt_up.p;
-    ebvo_edge *kfL = (ebvo_edge *)base, *kfR = (ebvo_edge *)(base + o_kfR), *cfL = (ebvo_edge *)(base + o_cfL), *cfR = (ebvo_edge *)(base + o_cfR);
-    double *pl = (double *)(base + o_pl), *pr = (double *)(base + o_pr);
-    unsigned long long *d_tot = (unsigned long long *)(base + o_tot);
-    int32_t *d_rows = (int32_t *)(base + o_rows);
-    uint8_t *on = (uint8_t *)(base + o_on);
-    EBVO_HIP(ctx, hipMemsetAsync(d_tot, 0, sizeof(unsigned long long) * 8, st));
-    if (n_kf)
-    {
-        EBVO_HIP(ctx, hipMemcpyAsync(kfL, kf_left, sizeof(ebvo_edge) * nz, hipMemcpyHostToDevice, st));
-        EBVO_HIP(ctx, hipMemcpyAsync(kfR, kf_right, sizeof(ebvo_edge) * nz, hipMemcpyHostToDevice, st));
-        EBVO_HIP(ctx, hipMemcpyAsync(pl, proj_left, sizeof(double) * 2 * nz, hipMemcpyHostToDevice, st));
-        EBVO_HIP(ctx, hipMemcpyAsync(pr, proj_right, sizeof(double) * 2 * nz, hipMemcpyHostToDevice, st));
-        if (row_on)
-            EBVO_HIP(ctx, hipMemcpyAsync(on, row_on, nz, hipMemcpyHostToDevice, st));
-        else
-            EBVO_HIP(ctx, hipMemsetAsync(on, 1, nz, st));
-        EBVO_HIP(ctx, hipMemsetAsync(d_rows, 0, sizeof(int32_t) * 2 * nz, st));
-    }
+    const size_t nz = (size_t)n_kf, ncz = (size_t)n_cf, eb = sizeof(ebvo_edge);
+    // the four mate lists, both projections, the totals, the (n, tp) rows, row_on, the grid
+    Carve L;
+    const size_t o_kfL = L.take(eb * nz), o_kfR = L.take(eb * nz), o_cfL = L.take(eb * ncz), o_cfR = L.take(eb * ncz),
+                 o_pl = L.take(sizeof(double) * 2 * nz), o_pr = L.take(sizeof(double) * 2 * nz), o_tot = L.take(sizeof(unsigned long long) * 8),
+                 o_rows = L.take(sizeof(int32_t) * 2 * (nz + 1)), o_on = L.take(nz), o_grid = L.take(match_temporal_grid_bytes(n_cf, gw * gh));
+    if (hc.stage(L))
+        return hc.rc;
+    Slot &s = hc.slot();
+    ebvo_edge *kfL = hc.at<ebvo_edge>(o_kfL), *kfR = hc.at<ebvo_edge>(o_kfR), *cfL = hc.at<ebvo_edge>(o_cfL), *cfR = hc.at<ebvo_edge>(o_cfR);
+    double *pl = hc.at<double>(o_pl), *pr = hc.at<double>(o_pr);
+    unsigned long long *d_tot = hc.at<unsigned long long>(o_tot);
+    int32_t *d_rows = hc.at<int32_t>(o_rows);
+    uint8_t *on = hc.at<uint8_t>(o_on);
+    void *grid = hc.at<char>(o_grid);
+    if (hc.fill(d_tot, 0, sizeof(unsigned long long) * 8) || hc.up(kfL, kf_left, eb * nz) || hc.up(kfR, kf_right, eb * nz) ||
+        hc.up(pl, proj_left, sizeof(double) * 2 * nz) || hc.up(pr, proj_right, sizeof(double) * 2 * nz) ||
+        (row_on ? hc.up(on, row_on, nz) : hc.fill(on, 1, nz)) || hc.fill(d_rows, 0, sizeof(int32_t) * 2 * nz))
+        return hc.rc;
+    int rc;
     if (n_kf > 0 && n_cf > 0)
     {
-        EBVO_HIP(ctx, hipMemcpyAsync(cfL, cf_left, sizeof(ebvo_edge) * ncz, hipMemcpyHostToDevice, st));
-        EBVO_HIP(ctx, hipMemcpyAsync(cfR, cf_right, sizeof(ebvo_edge) * ncz, hipMemcpyHostToDevice, st));
-        if ((rc = match_temporal_cells_enqueue(ctx, s, cfL, cfR, n_cf, cell_size, gw, gh, base + o_grid)) ||
-            (rc = tgt_grid_rows_enqueue(ctx, s, kfL, kfR, n_kf, cfL, cfR, base + o_grid, n_cf, cell_size, tgt_cell_radius(grid_radius, cell_size),
-                                        gw, gh, on, pl, pr, tp_dist, d_rows, d_tot)))
+        if (hc.up(cfL, cf_left, eb * ncz) || hc.up(cfR, cf_right, eb * ncz))
+            return hc.rc;
+        if ((rc = match_temporal_cells_enqueue(ctx, s, cfL, cfR, n_cf, cell_size, gw, gh, grid)) ||
+            (rc = tgt_grid_rows_enqueue(ctx, s, kfL, kfR, n_kf, cfL, cfR, grid, n_cf, cell_size, tgt_cell_radius(grid_radius, cell_size), gw, gh,
+                                        on, pl, pr, tp_dist, d_rows, d_tot)))
             return rc;
     }
     else if ((rc = gt_totals_enqueue(ctx, s, d_rows, on, n_kf, d_tot))) // no current-frame mates: the rows that are on are empty
         return rc;
-    std::vector<int32_t> rows(2 * nz + 1);
-    unsigned long long tot[5] = {0, 0, 0, 0, 0};
-    if (n_kf)
-        EBVO_HIP(ctx, hipMemcpyAsync(rows.data(), d_rows, sizeof(int32_t) * 2 * nz, hipMemcpyDeviceToHost, st));
-    EBVO_HIP(ctx, hipMemcpyAsync(tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, st));
-    EBVO_HIP(ctx, hipStreamSynchronize(st));
-    tgt_stage_doubles(rows.data(), row_on, n_kf, stage_out);
-    if ((rc = tgt_totals_agree(ctx, *stage_out, tot)))
-        return rc;
-    if (n_tp && n_kf)
-        memcpy(n_tp, rows.data(), sizeof(int32_t) * 2 * nz);
-    return EBVO_OK;
+    return host_stage_tail(hc, d_rows, d_tot, n_kf, row_on, /*temporal=*/true, n_tp, stage_out);
+}
+
+// The middle of a two-pass call: the per-row counts of the first pass come back (d_cnt null: nothing was counted, every row
+// is empty), the call's copies end, and the row offsets are formed.  EBVO_ERR_CAPACITY: more than a 32-bit offset holds.
+static int host_row_offsets(HostCall &hc, const int32_t *d_cnt, int n_kf, std::vector<int32_t> &h_rp)
+{
+    std::vector<int32_t> h_cnt((size_t)n_kf + 1, 0);
+    int32_t n_rows = 0;
+    hc.down(h_cnt.data(), d_cnt, d_cnt ? sizeof(int32_t) * (size_t)n_kf : 0);
+    if (hc.finish()) // on every path, before h_cnt goes
+        return hc.rc;
+    return tgt_row_offsets(h_cnt, n_kf, h_rp, &n_rows) ? EBVO_OK : EBVO_ERR_CAPACITY;
+}
+
+// the per-mate arrays of a two-pass call: in the image (or live), both projections, both orientations
+struct MateArrays
+{
+    uint8_t *flag;
+    double *pl, *pr, *ol, *orr;
+};
+
+// The end of a two-pass call: the per-mate outputs the caller asked for, and the wait.
+static int host_mate_outputs(HostCall &hc, size_t nz, const MateArrays &host, const MateArrays &dev)
+{
+    hc.down(host.flag, dev.flag, nz);
+    hc.down(host.pl, dev.pl, sizeof(double) * 2 * nz);
+    hc.down(host.pr, dev.pr, sizeof(double) * 2 * nz);
+    hc.down(host.ol, dev.ol, sizeof(double) * nz);
+    hc.down(host.orr, dev.orr, sizeof(double) * nz);
+    return hc.finish();
 }
 
 extern "C" int ebvo_tgt_veridical(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *kf_right, const double *kf_gamma, int n_kf,
@@ -6785,57 +6806,49 @@ extern "C" int ebvo_tgt_veridical(ebvo_ctx *ctx, const ebvo_edge *kf_left, const
     const int64_t gw64 = ((int64_t)img_w + cell_size - 1) / cell_size, gh64 = ((int64_t)img_h + cell_size - 1) / cell_size;
     if (gw64 * gh64 > (1 << 26) || gw64 > 30000 || gh64 > 30000) // the cells of a mate are 16-bit
         return EBVO_ERR_ARG;
-    EBVO_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
-    Slot *sp;
-    if ((rc = gt_host_slot(ctx, &sp)))
-        return rc;
-    Slot &s = *sp;
+    std::vector<int32_t> h_rp;
+    HostCall hc(ctx);
+    if (hc.rc)
+        return hc.rc;
     if (n_veridical)
         *n_veridical = 0;
     const int gw = (int)gw64, gh = (int)gh64;
     const size_t nz = (size_t)n_kf, ncz = (size_t)n_cf;
-    // pass 1 buffer (the call's own): mates, gamma, the six doubles per keyframe mate, counts and offsets, flags, the grid
-    const size_t o_kfR = sizeof(ebvo_edge) * nz, o_cfL = 2 * sizeof(ebvo_edge) * nz, o_cfR = o_cfL + sizeof(ebvo_edge) * ncz,
-                 o_geom = o_cfR + sizeof(ebvo_edge) * ncz, o_i32 = o_geom + sizeof(double) * 9 * nz,
-                 o_u8 = o_i32 + sizeof(int32_t) * 2 * (nz + 1), o_grid = (o_u8 + 2 * nz + 63) & ~(size_t)63,
-                 o_idx = (o_grid + match_temporal_grid_bytes(n_cf, gw * gh) + 63) & ~(size_t)63;
-    const size_t idx_room = sizeof(int32_t) * (size_t)((cap < (int64_t)nz * ncz ? cap : (int64_t)nz * ncz) + 1);
-    if ((rc = gt_grow(ctx, s, s.tgt_up, o_idx + idx_room)))
+    // mates, gamma, the six doubles per keyframe mate, counts and offsets, flags, the grid, the list
+    const size_t eb = sizeof(ebvo_edge), idx_room = sizeof(int32_t) * (size_t)((cap < (int64_t)nz * ncz ? cap : (int64_t)nz * ncz) + 1);
+    Carve L;
+    const size_t o_kfL = L.take(eb * nz), o_kfR = L.take(eb * nz), o_cfL = L.take(eb * ncz), o_cfR = L.take(eb * ncz),
+                 o_pl = L.take(sizeof(double) * 2 * nz), o_pr = L.take(sizeof(double) * 2 * nz), o_ol = L.take(sizeof(double) * nz),
+                 o_or = L.take(sizeof(double) * nz), o_gamma = L.take(sizeof(double) * 3 * nz), o_cnt = L.take(sizeof(int32_t) * (nz + 1)),
+                 o_rp = L.take(sizeof(int32_t) * (nz + 1)), o_in = L.take(nz), o_on = L.take(nz),
+                 o_grid = L.take(match_temporal_grid_bytes(n_cf, gw * gh)), o_idx = L.take(idx_room);
+    if (hc.stage(L))
+        return hc.rc;
+    Slot &s = hc.slot();
+    ebvo_edge *kfL = hc.at<ebvo_edge>(o_kfL), *kfR = hc.at<ebvo_edge>(o_kfR), *cfL = hc.at<ebvo_edge>(o_cfL), *cfR = hc.at<ebvo_edge>(o_cfR);
+    double *pl = hc.at<double>(o_pl), *pr = hc.at<double>(o_pr), *ol = hc.at<double>(o_ol), *orr = hc.at<double>(o_or);
+    double *gamma = kf_gamma ? hc.at<double>(o_gamma) : nullptr;
+    int32_t *cnt = hc.at<int32_t>(o_cnt), *rp = hc.at<int32_t>(o_rp), *idx = hc.at<int32_t>(o_idx);
+    uint8_t *in = hc.at<uint8_t>(o_in), *on = hc.at<uint8_t>(o_on);
+    void *grid = hc.at<char>(o_grid);
+    if (hc.up(kfL, kf_left, eb * nz) || hc.up(kfR, kf_right, eb * nz) || hc.up(gamma, kf_gamma, sizeof(double) * 3 * nz))
+        return hc.rc;
+    int rc;
+    if ((rc = tgt_project_enqueue(ctx, s, kfL, kfR, gamma, n_kf, R, t, calib, P.img_margin, img_w, img_h, in, pl, pr, ol, orr)))
         return rc;
-    hipStream_t st = s.stream;
-    char *base = (char *)s.tgt_up.p;
-    ebvo_edge *kfL = (ebvo_edge *)base, *kfR = (ebvo_edge *)(base + o_kfR), *cfL = (ebvo_edge *)(base + o_cfL), *cfR = (ebvo_edge *)(base + o_cfR);
-    double *pl = (double *)(base + o_geom), *pr = pl + 2 * nz, *ol = pr + 2 * nz, *orr = ol + nz, *gamma = orr + nz;
-    int32_t *cnt = (int32_t *)(base + o_i32), *rp = cnt + nz + 1;
-    uint8_t *in = (uint8_t *)(base + o_u8), *on = in + nz;
-    std::vector<int32_t> h_cnt(nz + 1, 0), h_rp;
-    int32_t n_rows = 0;
-    if (n_kf)
-    {
-        EBVO_HIP(ctx, hipMemcpyAsync(kfL, kf_left, sizeof(ebvo_edge) * nz, hipMemcpyHostToDevice, st));
-        EBVO_HIP(ctx, hipMemcpyAsync(kfR, kf_right, sizeof(ebvo_edge) * nz, hipMemcpyHostToDevice, st));
-        if (kf_gamma)
-            EBVO_HIP(ctx, hipMemcpyAsync(gamma, kf_gamma, sizeof(double) * 3 * nz, hipMemcpyHostToDevice, st));
-        if ((rc = tgt_project_enqueue(ctx, s, kfL, kfR, kf_gamma ? gamma : nullptr, n_kf, R, t, calib, P.img_margin, img_w, img_h, in, pl,
-                                      pr, ol, orr)))
-            return rc;
-    }
     const bool walk = n_kf > 0 && n_cf > 0;
     const int sr = tgt_cell_radius(P.search_radius, cell_size);
     if (walk)
     {
-        EBVO_HIP(ctx, hipMemcpyAsync(cfL, cf_left, sizeof(ebvo_edge) * ncz, hipMemcpyHostToDevice, st));
-        EBVO_HIP(ctx, hipMemcpyAsync(cfR, cf_right, sizeof(ebvo_edge) * ncz, hipMemcpyHostToDevice, st));
-        if ((rc = match_temporal_cells_enqueue(ctx, s, cfL, cfR, n_cf, cell_size, gw, gh, base + o_grid)) ||
-            (rc = tgt_veridical_enqueue(ctx, s, n_kf, in, pl, pr, ol, orr, cfL, cfR, base + o_grid, n_cf, cell_size, sr, gw, gh, P.tp_dist,
+        if (hc.up(cfL, cf_left, eb * ncz) || hc.up(cfR, cf_right, eb * ncz))
+            return hc.rc;
+        if ((rc = match_temporal_cells_enqueue(ctx, s, cfL, cfR, n_cf, cell_size, gw, gh, grid)) ||
+            (rc = tgt_veridical_enqueue(ctx, s, n_kf, in, pl, pr, ol, orr, cfL, cfR, grid, n_cf, cell_size, sr, gw, gh, P.tp_dist,
                                         P.orient_thr_deg, nullptr, cnt, nullptr, nullptr, 0, nullptr)))
             return rc;
-        EBVO_HIP(ctx, hipMemcpyAsync(h_cnt.data(), cnt, sizeof(int32_t) * nz, hipMemcpyDeviceToHost, st));
     }
-    EBVO_HIP(ctx, hipStreamSynchronize(st));
-    if (!tgt_row_offsets(h_cnt, n_kf, h_rp, &n_rows))
-        return EBVO_ERR_CAPACITY;
+    if ((rc = host_row_offsets(hc, walk ? cnt : nullptr, n_kf, h_rp)))
+        return rc;
     const int64_t n_ver = h_rp[n_kf];
     if (n_veridical)
         *n_veridical = n_ver;
@@ -6843,26 +6856,15 @@ extern "C" int ebvo_tgt_veridical(ebvo_ctx *ctx, const ebvo_edge *kf_left, const
         return EBVO_ERR_CAPACITY;
     if (walk && ver_idx && n_ver > 0)
     {
-        EBVO_HIP(ctx, hipMemcpyAsync(rp, h_rp.data(), sizeof(int32_t) * (nz + 1), hipMemcpyHostToDevice, st));
-        if ((rc = tgt_veridical_enqueue(ctx, s, n_kf, in, pl, pr, ol, orr, cfL, cfR, base + o_grid, n_cf, cell_size, sr, gw, gh, P.tp_dist,
-                                        P.orient_thr_deg, nullptr, nullptr, rp, (int32_t *)(base + o_idx), n_ver, on)))
+        if (hc.up(rp, h_rp.data(), sizeof(int32_t) * (nz + 1)))
+            return hc.rc;
+        if ((rc = tgt_veridical_enqueue(ctx, s, n_kf, in, pl, pr, ol, orr, cfL, cfR, grid, n_cf, cell_size, sr, gw, gh, P.tp_dist,
+                                        P.orient_thr_deg, nullptr, nullptr, rp, idx, n_ver, on)))
             return rc;
-        EBVO_HIP(ctx, hipMemcpyAsync(ver_idx, base + o_idx, sizeof(int32_t) * (size_t)n_ver, hipMemcpyDeviceToHost, st));
+        hc.down(ver_idx, idx, sizeof(int32_t) * (size_t)n_ver);
     }
-    if (nz)
-    {
-        const struct
-        {
-            void *dst;
-            const void *src;
-            size_t bytes;
-        } copies[] = {{in_image, in, nz}, {proj_left, pl, sizeof(double) * 2 * nz}, {proj_right, pr, sizeof(double) * 2 * nz},
-                      {orient_left, ol, sizeof(double) * nz}, {orient_right, orr, sizeof(double) * nz}};
-        for (const auto &c : copies)
-            if (c.dst)
-                EBVO_HIP(ctx, hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, st));
-    }
-    EBVO_HIP(ctx, hipStreamSynchronize(st));
+    if (host_mate_outputs(hc, nz, {in_image, proj_left, proj_right, orient_left, orient_right}, {in, pl, pr, ol, orr}))
+        return hc.rc;
     if (ver_row_ptr)
         memcpy(ver_row_ptr, h_rp.data(), sizeof(int32_t) * (nz + 1));
     return EBVO_OK;
@@ -6979,60 +6981,54 @@ extern "C" int ebvo_tprior_candidates(ebvo_ctx *ctx, const ebvo_edge *kf_left, c
     const int64_t gw64 = ((int64_t)img_w + cell_size - 1) / cell_size, gh64 = ((int64_t)img_h + cell_size - 1) / cell_size;
     if (gw64 * gh64 > (1 << 26) || gw64 > 30000 || gh64 > 30000) // the cells of a mate are 16-bit
         return EBVO_ERR_ARG;
-    EBVO_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
-    Slot *sp;
-    if ((rc = gt_host_slot(ctx, &sp)))
-        return rc;
-    Slot &s = *sp;
+    std::vector<int32_t> h_rp;
+    HostCall hc(ctx);
+    if (hc.rc)
+        return hc.rc;
     if (n_candidates)
         *n_candidates = 0;
     const int gw = (int)gw64, gh = (int)gh64;
     const size_t nz = (size_t)n_kf, ncz = (size_t)n_cf;
-    // one buffer of the call's own: mates, the six doubles per keyframe mate, counts and offsets, live, the grid, the list
-    const size_t o_kfR = sizeof(ebvo_edge) * nz, o_cfL = 2 * sizeof(ebvo_edge) * nz, o_cfR = o_cfL + sizeof(ebvo_edge) * ncz,
-                 o_geom = o_cfR + sizeof(ebvo_edge) * ncz, o_i32 = o_geom + sizeof(double) * 6 * nz,
-                 o_u8 = o_i32 + sizeof(int32_t) * 2 * (nz + 1), o_grid = (o_u8 + nz + 63) & ~(size_t)63,
-                 o_idx = (o_grid + match_temporal_grid_bytes(n_cf, gw * gh) + 63) & ~(size_t)63;
-    const size_t idx_room = sizeof(int32_t) * (size_t)((cap < (int64_t)nz * ncz ? cap : (int64_t)nz * ncz) + 1);
-    if ((rc = gt_grow(ctx, s, s.tgt_up, o_idx + idx_room)))
-        return rc;
-    hipStream_t st = s.stream;
-    char *base = (char *)s.tgt_up.p;
-    ebvo_edge *kfL = (ebvo_edge *)base, *kfR = (ebvo_edge *)(base + o_kfR), *cfL = (ebvo_edge *)(base + o_cfL), *cfR = (ebvo_edge *)(base + o_cfR);
-    double *pl = (double *)(base + o_geom), *pr = pl + 2 * nz, *ol = pr + 2 * nz, *orr = ol + nz;
-    int32_t *cnt = (int32_t *)(base + o_i32), *rp = cnt + nz + 1;
-    uint8_t *lv = (uint8_t *)(base + o_u8);
+    // mates, the six doubles per keyframe mate, counts and offsets, live, the grid, the list
+    const size_t eb = sizeof(ebvo_edge), idx_room = sizeof(int32_t) * (size_t)((cap < (int64_t)nz * ncz ? cap : (int64_t)nz * ncz) + 1);
+    Carve L;
+    const size_t o_kfL = L.take(eb * nz), o_kfR = L.take(eb * nz), o_cfL = L.take(eb * ncz), o_cfR = L.take(eb * ncz),
+                 o_pl = L.take(sizeof(double) * 2 * nz), o_pr = L.take(sizeof(double) * 2 * nz), o_ol = L.take(sizeof(double) * nz),
+                 o_or = L.take(sizeof(double) * nz), o_cnt = L.take(sizeof(int32_t) * (nz + 1)), o_rp = L.take(sizeof(int32_t) * (nz + 1)),
+                 o_lv = L.take(nz), o_grid = L.take(match_temporal_grid_bytes(n_cf, gw * gh)), o_idx = L.take(idx_room);
+    if (hc.stage(L))
+        return hc.rc;
+    Slot &s = hc.slot();
+    ebvo_edge *kfL = hc.at<ebvo_edge>(o_kfL), *kfR = hc.at<ebvo_edge>(o_kfR), *cfL = hc.at<ebvo_edge>(o_cfL), *cfR = hc.at<ebvo_edge>(o_cfR);
+    double *pl = hc.at<double>(o_pl), *pr = hc.at<double>(o_pr), *ol = hc.at<double>(o_ol), *orr = hc.at<double>(o_or);
+    int32_t *cnt = hc.at<int32_t>(o_cnt), *rp = hc.at<int32_t>(o_rp), *idx = hc.at<int32_t>(o_idx);
+    uint8_t *lv = hc.at<uint8_t>(o_lv);
+    void *grid = hc.at<char>(o_grid);
     TemporalPrior Q;
     Q.live = lv; Q.pl = pl; Q.pr = pr; Q.ol = ol; Q.orr = orr;
     Q.use_orientation = P.use_orientation != 0;
-    std::vector<int32_t> h_cnt(nz + 1, 0), h_rp;
-    int32_t n_rows = 0;
-    EBVO_HIP(ctx, hipMemsetAsync(cnt, 0, sizeof(int32_t) * 2 * (nz + 1), st));
-    if (n_kf)
-    {
-        EBVO_HIP(ctx, hipMemcpyAsync(kfL, kf_left, sizeof(ebvo_edge) * nz, hipMemcpyHostToDevice, st));
-        EBVO_HIP(ctx, hipMemcpyAsync(kfR, kf_right, sizeof(ebvo_edge) * nz, hipMemcpyHostToDevice, st));
-        if ((rc = tprior_project_enqueue(ctx, s, kfL, kfR, n_kf, R, t, calib, P.img_margin, img_w, img_h, lv, pl, pr, ol, orr)))
-            return rc;
-    }
+    if (hc.fill(cnt, 0, sizeof(int32_t) * (nz + 1)) || hc.fill(rp, 0, sizeof(int32_t) * (nz + 1)) || hc.up(kfL, kf_left, eb * nz) ||
+        hc.up(kfR, kf_right, eb * nz))
+        return hc.rc;
+    int rc;
+    if ((rc = tprior_project_enqueue(ctx, s, kfL, kfR, n_kf, R, t, calib, P.img_margin, img_w, img_h, lv, pl, pr, ol, orr)))
+        return rc;
     const bool walk = n_kf > 0 && n_cf > 0;
     const int sr = tgt_cell_radius(grid_radius, cell_size);
     if (walk)
     {
-        EBVO_HIP(ctx, hipMemcpyAsync(cfL, cf_left, sizeof(ebvo_edge) * ncz, hipMemcpyHostToDevice, st));
-        EBVO_HIP(ctx, hipMemcpyAsync(cfR, cf_right, sizeof(ebvo_edge) * ncz, hipMemcpyHostToDevice, st));
-        if ((rc = match_temporal_cells_enqueue(ctx, s, cfL, cfR, n_cf, cell_size, gw, gh, base + o_grid)) ||
-            (rc = match_temporal_candidates_enqueue(ctx, s, kfL, kfR, n_kf, cfL, cfR, base + o_grid, n_cf, cell_size, sr, gw, gh,
-                                                    orient_thr_deg, cnt, nullptr, nullptr, 0, &Q)))
+        if (hc.up(cfL, cf_left, eb * ncz) || hc.up(cfR, cf_right, eb * ncz))
+            return hc.rc;
+        if ((rc = match_temporal_cells_enqueue(ctx, s, cfL, cfR, n_cf, cell_size, gw, gh, grid)) ||
+            (rc = match_temporal_candidates_enqueue(ctx, s, kfL, kfR, n_kf, cfL, cfR, grid, n_cf, cell_size, sr, gw, gh, orient_thr_deg, cnt,
+                                                    nullptr, nullptr, 0, &Q)))
             return rc;
-        EBVO_HIP(ctx, hipMemcpyAsync(h_cnt.data(), cnt, sizeof(int32_t) * nz, hipMemcpyDeviceToHost, st));
     }
-    EBVO_HIP(ctx, hipStreamSynchronize(st));
-    if (!tgt_row_offsets(h_cnt, n_kf, h_rp, &n_rows))
+    if ((rc = host_row_offsets(hc, walk ? cnt : nullptr, n_kf, h_rp)))
     {
-        ctx->last_error = "more candidate quads than a 32-bit row offset holds";
-        return EBVO_ERR_CAPACITY;
+        if (rc == EBVO_ERR_CAPACITY)
+            ctx->last_error = "more candidate quads than a 32-bit row offset holds";
+        return rc;
     }
     const int64_t n_cand = h_rp[n_kf];
     if (n_candidates)
@@ -7044,26 +7040,15 @@ extern "C" int ebvo_tprior_candidates(ebvo_ctx *ctx, const ebvo_edge *kf_left, c
     }
     if (walk && col_idx && n_cand > 0)
     {
-        EBVO_HIP(ctx, hipMemcpyAsync(rp, h_rp.data(), sizeof(int32_t) * (nz + 1), hipMemcpyHostToDevice, st));
-        if ((rc = match_temporal_candidates_enqueue(ctx, s, kfL, kfR, n_kf, cfL, cfR, base + o_grid, n_cf, cell_size, sr, gw, gh,
-                                                    orient_thr_deg, nullptr, rp, (int32_t *)(base + o_idx), n_cand, &Q)))
+        if (hc.up(rp, h_rp.data(), sizeof(int32_t) * (nz + 1)))
+            return hc.rc;
+        if ((rc = match_temporal_candidates_enqueue(ctx, s, kfL, kfR, n_kf, cfL, cfR, grid, n_cf, cell_size, sr, gw, gh, orient_thr_deg,
+                                                    nullptr, rp, idx, n_cand, &Q)))
             return rc;
-        EBVO_HIP(ctx, hipMemcpyAsync(col_idx, base + o_idx, sizeof(int32_t) * (size_t)n_cand, hipMemcpyDeviceToHost, st));
+        hc.down(col_idx, idx, sizeof(int32_t) * (size_t)n_cand);
     }
-    if (nz)
-    {
-        const struct
-        {
-            void *dst;
-            const void *src;
-            size_t bytes;
-        } copies[] = {{live, lv, nz}, {proj_left, pl, sizeof(double) * 2 * nz}, {proj_right, pr, sizeof(double) * 2 * nz},
-                      {orient_left, ol, sizeof(double) * nz}, {orient_right, orr, sizeof(double) * nz}};
-        for (const auto &c : copies)
-            if (c.dst)
-                EBVO_HIP(ctx, hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, st));
-    }
-    EBVO_HIP(ctx, hipStreamSynchronize(st));
+    if (host_mate_outputs(hc, nz, {live, proj_left, proj_right, orient_left, orient_right}, {lv, pl, pr, ol, orr}))
+        return hc.rc;
     if (row_ptr)
         memcpy(row_ptr, h_rp.data(), sizeof(int32_t) * (nz + 1));
     return EBVO_OK;
@@ -7077,60 +7062,35 @@ extern "C" int ebvo_tgt_evaluate_rows(ebvo_ctx *ctx, const int32_t *row_ptr, con
     if (!ctx || !stage_out || !(tp_dist >= 0) || check_csr(row_ptr, n_kf, &np) || (n_kf > 0 && (!proj_left || !proj_right)) ||
         (np > 0 && (!left_centres || !right_centres)))
         return EBVO_ERR_ARG;
-    EBVO_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
-    Slot *sp;
-    if ((rc = gt_host_slot(ctx, &sp)))
-        return rc;
-    Slot &s = *sp;
+    HostCall hc(ctx);
+    if (hc.rc)
+        return hc.rc;
     memset(stage_out, 0, sizeof *stage_out);
     stage_out->present = 1;
     const size_t nz = (size_t)n_kf, npz = (size_t)np;
-    // one buffer of the call's own: both centre lists, both projections, the totals, the (n, tp) rows, row_ptr, row_on, is_tp
-    const size_t o_R = sizeof(ebvo_edge) * (npz + 1), o_pl = 2 * o_R, o_pr = o_pl + sizeof(double) * 2 * (nz + 1),
-                 o_tot = o_pr + sizeof(double) * 2 * (nz + 1), o_rows = o_tot + sizeof(unsigned long long) * 8,
-                 o_rp = o_rows + sizeof(int32_t) * 2 * (nz + 1), o_on = o_rp + sizeof(int32_t) * (nz + 2), o_tp = o_on + nz + 8,
-                 total = o_tp + npz + 8;
-    if ((rc = gt_grow(ctx, s, s.tgt_up, total)))
+    // both centre lists, both projections, the totals, the (n, tp) rows, row_ptr, row_on, is_tp
+    Carve L;
+    const size_t o_cL = L.take(sizeof(ebvo_edge) * (npz + 1)), o_cR = L.take(sizeof(ebvo_edge) * (npz + 1)),
+                 o_pl = L.take(sizeof(double) * 2 * (nz + 1)), o_pr = L.take(sizeof(double) * 2 * (nz + 1)),
+                 o_tot = L.take(sizeof(unsigned long long) * 8), o_rows = L.take(sizeof(int32_t) * 2 * (nz + 1)),
+                 o_rp = L.take(sizeof(int32_t) * (nz + 2)), o_on = L.take(nz), o_tp = L.take(npz);
+    if (hc.stage(L))
+        return hc.rc;
+    ebvo_edge *cL = hc.at<ebvo_edge>(o_cL), *cR = hc.at<ebvo_edge>(o_cR);
+    double *pl = hc.at<double>(o_pl), *pr = hc.at<double>(o_pr);
+    unsigned long long *d_tot = hc.at<unsigned long long>(o_tot);
+    int32_t *d_rows = hc.at<int32_t>(o_rows), *d_rp = hc.at<int32_t>(o_rp);
+    uint8_t *on = hc.at<uint8_t>(o_on), *d_tp = hc.at<uint8_t>(o_tp);
+    if (hc.up(cL, left_centres, sizeof(ebvo_edge) * npz) || hc.up(cR, right_centres, sizeof(ebvo_edge) * npz) ||
+        hc.up(d_rp, row_ptr, sizeof(int32_t) * (nz + 1)) || hc.up(pl, proj_left, sizeof(double) * 2 * nz) ||
+        hc.up(pr, proj_right, sizeof(double) * 2 * nz) || (row_on ? hc.up(on, row_on, nz) : hc.fill(on, 1, nz)) ||
+        hc.fill(d_rows, 0, sizeof(int32_t) * 2 * nz))
+        return hc.rc;
+    if (int rc = tgt_rows_enqueue(ctx, hc.slot(), d_rp, cL, cR, nullptr, nullptr, nullptr, nullptr, pl, pr, on, n_kf, np, tp_dist, d_rows, d_tp,
+                                  d_tot))
         return rc;
-    hipStream_t st = s.stream;
-    char *base = (char *)s.tgt_up.p;
-    int32_t *d_rows = (int32_t *)(base + o_rows);
-    unsigned long long *d_tot = (unsigned long long *)(base + o_tot);
-    if (np)
-    {
-        EBVO_HIP(ctx, hipMemcpyAsync(base, left_centres, sizeof(ebvo_edge) * npz, hipMemcpyHostToDevice, st));
-        EBVO_HIP(ctx, hipMemcpyAsync(base + o_R, right_centres, sizeof(ebvo_edge) * npz, hipMemcpyHostToDevice, st));
-    }
-    EBVO_HIP(ctx, hipMemcpyAsync(base + o_rp, row_ptr, sizeof(int32_t) * (nz + 1), hipMemcpyHostToDevice, st));
-    if (n_kf)
-    {
-        EBVO_HIP(ctx, hipMemcpyAsync(base + o_pl, proj_left, sizeof(double) * 2 * nz, hipMemcpyHostToDevice, st));
-        EBVO_HIP(ctx, hipMemcpyAsync(base + o_pr, proj_right, sizeof(double) * 2 * nz, hipMemcpyHostToDevice, st));
-        if (row_on)
-            EBVO_HIP(ctx, hipMemcpyAsync(base + o_on, row_on, nz, hipMemcpyHostToDevice, st));
-        else
-            EBVO_HIP(ctx, hipMemsetAsync(base + o_on, 1, nz, st));
-        EBVO_HIP(ctx, hipMemsetAsync(d_rows, 0, sizeof(int32_t) * 2 * nz, st));
-    }
-    if ((rc = tgt_rows_enqueue(ctx, s, (const int32_t *)(base + o_rp), (const ebvo_edge *)base, (const ebvo_edge *)(base + o_R), nullptr,
-                               nullptr, nullptr, nullptr, (const double *)(base + o_pl), (const double *)(base + o_pr),
-                               (const uint8_t *)(base + o_on), n_kf, np, tp_dist, d_rows, (uint8_t *)(base + o_tp), d_tot)))
-        return rc;
-    std::vector<int32_t> rows(2 * nz + 1);
-    unsigned long long tot[5] = {0, 0, 0, 0, 0};
-    if (n_kf)
-        EBVO_HIP(ctx, hipMemcpyAsync(rows.data(), d_rows, sizeof(int32_t) * 2 * nz, hipMemcpyDeviceToHost, st));
-    if (is_tp && np)
-        EBVO_HIP(ctx, hipMemcpyAsync(is_tp, base + o_tp, npz, hipMemcpyDeviceToHost, st));
-    EBVO_HIP(ctx, hipMemcpyAsync(tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, st));
-    EBVO_HIP(ctx, hipStreamSynchronize(st));
-    tgt_stage_doubles(rows.data(), row_on, n_kf, stage_out);
-    if ((rc = tgt_totals_agree(ctx, *stage_out, tot)))
-        return rc;
-    if (n_tp && n_kf)
-        memcpy(n_tp, rows.data(), sizeof(int32_t) * 2 * nz);
-    return EBVO_OK;
+    hc.down(is_tp, d_tp, npz);
+    return host_stage_tail(hc, d_rows, d_tot, n_kf, row_on, /*temporal=*/true, n_tp, stage_out);
 }
 
 // the values each developer key accepts; anything else is refused before the context changes at all

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/ebvo_hip.h"
+#include "ebvo_carve.h"
 
 enum KernelId
 {
@@ -184,18 +185,17 @@ struct Slot
                                                                  // order, one batch of draws, its hypotheses
     GrowBuf pose_sel, pose_casc; // ground-truth rows: the compacted selection and what is scattered back; the cascade's draws,
                                  // counters and stage bytes
-    GrowBuf align_up, align_ws;  // edge alignment (align_kernels.hip): the uploaded lists of the host-array call; the state, tile sums,
-                                 // planes and both edge grids of either call
-    GrowBuf depth_up, depth_ws;  // inverse-depth filter (depth_kernels.hip): the uploaded arrays of the host-array call; Gamma and T1,
-                                 // the tile sums and the record of either call
-    GrowBuf carry_up, carry_ws;  // handover of the depths on promotion (carry_kernels.hip): the uploaded arrays and the outgoing state
-                                 // of the host-array call; the counters, the old mates' projections, their planes and grid of either call
-    GrowBuf cover_up, cover_ws;  // keyframe coverage (cover_kernels.hip): the uploaded arrays of the host-array call; the record, the
-                                 // counters, the bins, the cell planes and the per-mate and per-edge outputs of either call
+    GrowBuf host_up;   // the uploaded arrays and the outputs of every host-array call that leaves the slot's state alone (the *_edges
+                       // calls, ebvo_depth_carry, ebvo_gt_* and ebvo_tgt_* / ebvo_tprior_*): one at a time, each ends synchronised
+    GrowBuf align_ws;  // edge alignment (align_kernels.hip): the state, tile sums, planes and both edge grids
+    GrowBuf depth_ws;  // inverse-depth filter (depth_kernels.hip): Gamma and T1, the tile sums and the record
+    GrowBuf carry_ws;  // handover of the depths on promotion (carry_kernels.hip): the counters, the old mates' projections, their
+                       // planes and grid
+    GrowBuf cover_ws;  // keyframe coverage (cover_kernels.hip): the record, the counters, the bins, the cell planes and the per-mate
+                       // and per-edge outputs
     GrowBuf pose_refit;          // inlier refit (pose_refit_kernels.hip): seven planes per quad, the fit set, the mask, the result
     // ground-truth evaluation (gt_kernels.hip, ebvo_stereo_set_gt): armed = the buffers below describe the resident pair
     GrowBuf gt_disp, gt_geom, gt_flags, gt_boxes, gt_pool_i32, gt_pool_idx, gt_rows, gt_tot;
-    GrowBuf gt_up; // everything ebvo_gt_locate / ebvo_gt_evaluate_rows need (host-array calls: they touch nothing else of slot 0)
     bool gt_armed = false;
     bool gt_fin_enq = false, gt_fin_done = false, gt_fin_sift = false; // the finalisation chain ran (with SIFT) while armed
     int gt_nL = 0;
@@ -206,7 +206,6 @@ struct Slot
     std::vector<int32_t> gt_h_pool_rp;  // host copy of the pool's row_ptr
     // temporal ground truth (tgt_kernels.hip, ebvo_temporal_set_gt): armed = the buffers below describe the slot's temporal match
     GrowBuf tgt_geom, tgt_i32, tgt_idx, tgt_u8, tgt_rows, tgt_flags, tgt_tot;
-    GrowBuf tgt_up; // everything ebvo_tgt_veridical / ebvo_tgt_evaluate_rows need (host-array calls: they touch nothing else of slot 0)
     bool tgt_armed = false;
     int tgt_n_kf = 0;
     int32_t tgt_n_rows = 0;      // keyframe mates with a veridical quad
@@ -460,11 +459,9 @@ __device__ inline int64_t devcount(const DevCount &c)
             return ebvo_fail_hip((ctx), e_, #call, __FILE__, __LINE__);  \
     } while (0)
 
-// the next multiple of 64 bytes: where the next array of a carved workspace starts
-inline size_t round_up64(size_t v) { return (v + 63) & ~(size_t)63; }
-
-// grow a slot buffer (synchronises the slot's stream before freeing the old allocation)
-int ebvo_grow(ebvo_ctx *ctx, Slot &s, GrowBuf &b, size_t bytes);
+// grow a slot buffer (synchronises the slot's stream before freeing the old allocation).  bump_generation: a captured chain of
+// the slot may hold the old address; false for the buffers no captured chain ever holds (ground truth, host-array staging)
+int ebvo_grow(ebvo_ctx *ctx, Slot &s, GrowBuf &b, size_t bytes, bool bump_generation = true);
 
 // profiling brackets around kernel launches on a slot's stream
 bool ebvo_prof_begin(ebvo_ctx *ctx, Slot &s, int kid); // false: nothing was recorded (profiler off, or another stage selected)
