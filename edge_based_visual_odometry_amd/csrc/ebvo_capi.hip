@@ -507,6 +507,141 @@ static int host_slot(ebvo_ctx *ctx, Slot **out)
     return EBVO_OK;
 }
 
+// ---- host-array calls: copies between a caller's arrays and a carved device buffer ----------------------------------------
+// Nothing is copied for an empty array or a null host pointer (an optional argument the caller left out).
+static int copy_up(ebvo_ctx *ctx, hipStream_t st, void *dst_dev, const void *src_host, size_t bytes)
+{
+    if (bytes && src_host)
+        EBVO_HIP(ctx, hipMemcpyAsync(dst_dev, src_host, bytes, hipMemcpyHostToDevice, st));
+    return EBVO_OK;
+}
+
+static int copy_down(ebvo_ctx *ctx, hipStream_t st, void *dst_host, const void *src_dev, size_t bytes)
+{
+    if (bytes && dst_host)
+        EBVO_HIP(ctx, hipMemcpyAsync(dst_host, src_dev, bytes, hipMemcpyDeviceToHost, st));
+    return EBVO_OK;
+}
+
+// The host-array calls run on slot 0's stream with a buffer of their own (host_up): the slot's pair, its results and its
+// armed state stay as they are (unlike host_slot(), whose callers reuse the pair's buffers).
+static int gt_host_slot(ebvo_ctx *ctx, Slot **out)
+{
+    Slot &s = *ctx->slots[0];
+    if (s.in_flight || s.fin_in_flight || s.tq_in_flight)
+    {
+        ctx->last_error = "slot 0 has submitted work in flight; call ebvo_stereo_wait / ebvo_stereo_finalize_wait / ebvo_temporal_match_wait first";
+        return EBVO_ERR_STATE;
+    }
+    *out = &s;
+    return EBVO_OK;
+}
+
+// One host-array call.  It sets the device, takes slot 0 and copies on the slot's stream.  The copies read and write the
+// caller's arrays and the function's locals, so none of them may outlive the call: finish() waits for them, and the
+// destructor does on every return that did not get there.  A local that down() writes into is declared before this object.
+// Two kinds: STAGED leaves the slot's pair alone (gt_host_slot) and works in the carved staging buffer, stage() / at();
+// PAIR_BUFFERS gives the pair up (host_slot) and works in the pair's named buffers, grow() / image(), because the stage
+// enqueues it calls write into slot-owned buffers.
+namespace
+{
+struct HostCall
+{
+    enum Kind { STAGED, PAIR_BUFFERS };
+    ebvo_ctx *ctx;
+    Slot *s = nullptr;
+    int rc;               // the device and the slot's state first, then the first failure of a helper; every helper returns it
+    bool pending = false; // copies were enqueued since the last finish()
+
+    explicit HostCall(ebvo_ctx *c, Kind kind = STAGED) : ctx(c)
+    {
+        const hipError_t e = hipSetDevice(c->device);
+        rc = e != hipSuccess      ? ebvo_fail_hip(c, e, "hipSetDevice(ctx->device)", __FILE__, __LINE__)
+             : kind == PAIR_BUFFERS ? host_slot(c, &s)
+                                    : gt_host_slot(c, &s);
+    }
+    HostCall(const HostCall &) = delete;
+    HostCall &operator=(const HostCall &) = delete;
+    ~HostCall()
+    {
+        if (pending)
+            (void)hipStreamSynchronize(s->stream);
+    }
+
+    Slot &slot() const { return *s; }
+    // the staging buffer holds L.total() bytes; at<T>(offset) is an array of it
+    int stage(const Carve &L) { return rc ? rc : (rc = ebvo_grow(ctx, *s, s->host_up, L.total(), false)); }
+    template <class T> T *at(size_t offset) const { return (T *)((char *)s->host_up.p + offset); }
+    // a named buffer of the pair (a captured chain may hold its old address: the generation is bumped)
+    int grow(GrowBuf &b, size_t bytes) { return rc ? rc : (rc = ebvo_grow(ctx, *s, b, bytes)); }
+
+    int up(void *dst_dev, const void *src_host, size_t bytes)
+    {
+        pending = true;
+        return rc ? rc : (rc = copy_up(ctx, s->stream, dst_dev, src_host, bytes));
+    }
+    // `rows` rows of row_bytes each, src_pitch bytes apart on the host, packed on the device
+    int up_rows(void *dst_dev, const void *src_host, size_t row_bytes, size_t src_pitch, size_t rows)
+    {
+        pending = true;
+        if (rc)
+            return rc;
+        const hipError_t e = hipMemcpy2DAsync(dst_dev, row_bytes, src_host, src_pitch, row_bytes, rows, hipMemcpyHostToDevice, s->stream);
+        return e == hipSuccess ? rc : (rc = ebvo_fail_hip(ctx, e, "hipMemcpy2DAsync(dst_dev, src_host)", __FILE__, __LINE__));
+    }
+    // image k of the slot (upload_image: one linear copy for a packed image)
+    int image(int k, const uint8_t *img, int h, int w, ptrdiff_t stride)
+    {
+        pending = true;
+        return rc ? rc : (rc = upload_image(ctx, *s, k, img, h, w, stride));
+    }
+    int down(void *dst_host, const void *src_dev, size_t bytes)
+    {
+        pending = true;
+        return rc ? rc : (rc = copy_down(ctx, s->stream, dst_host, src_dev, bytes));
+    }
+    // `rows` packed rows of row_bytes each on the device, dst_pitch bytes apart on the host (one linear copy if that is packed too)
+    int down_rows(void *dst_host, size_t dst_pitch, const void *src_dev, size_t row_bytes, size_t rows)
+    {
+        if (dst_pitch == row_bytes)
+            return down(dst_host, src_dev, row_bytes * rows);
+        pending = true;
+        if (rc)
+            return rc;
+        const hipError_t e = hipMemcpy2DAsync(dst_host, dst_pitch, src_dev, row_bytes, row_bytes, rows, hipMemcpyDeviceToHost, s->stream);
+        return e == hipSuccess ? rc : (rc = ebvo_fail_hip(ctx, e, "hipMemcpy2DAsync(dst_host, src_dev)", __FILE__, __LINE__));
+    }
+    int fill(void *dst_dev, int byte, size_t bytes)
+    {
+        if (rc || !bytes)
+            return rc;
+        const hipError_t e = hipMemsetAsync(dst_dev, byte, bytes, s->stream);
+        return e == hipSuccess ? rc : (rc = ebvo_fail_hip(ctx, e, "hipMemsetAsync(dst_dev, byte, bytes, stream)", __FILE__, __LINE__));
+    }
+    // wait for the stream whatever happened before; an earlier failure comes before the wait's own
+    int finish()
+    {
+        pending = false;
+        const hipError_t e = hipStreamSynchronize(s->stream);
+        if (!rc && e != hipSuccess)
+            rc = ebvo_fail_hip(ctx, e, "hipStreamSynchronize(stream)", __FILE__, __LINE__);
+        return rc;
+    }
+};
+} // namespace
+
+// a CSR row_ptr of nL rows: starts at 0 and never decreases; *np: the listed total
+static int check_csr(const int32_t *row_ptr, int nL, int64_t *np)
+{
+    if (nL < 0 || !row_ptr || row_ptr[0] != 0)
+        return EBVO_ERR_ARG;
+    for (int i = 0; i < nL; ++i)
+        if (row_ptr[i + 1] < row_ptr[i])
+            return EBVO_ERR_ARG;
+    *np = row_ptr[nL];
+    return EBVO_OK;
+}
+
 // run TOED on n_img resident images of the slot and read the counts back (synchronises)
 namespace
 {
@@ -581,18 +716,18 @@ extern "C" int ebvo_toed(ebvo_ctx *ctx, const uint8_t *img, int h, int w, ptrdif
 {
     if (!ctx || !img || !n_kept || !n_total || cap < 0 || cap_all < 0 || (cap > 0 && !out))
         return EBVO_ERR_ARG;
-    EBVO_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
-    Slot *sp;
-    if ((rc = check_size(ctx, h, w)) || (rc = host_slot(ctx, &sp)))
+    if (int rc = check_size(ctx, h, w))
         return rc;
-    Slot &s = *sp;
+    HostCall hc(ctx, HostCall::PAIR_BUFFERS);
+    if (hc.rc)
+        return hc.rc;
+    Slot &s = hc.slot();
     ctx->sw_tag[0] = ctx->sw_tag[1] = 0; // the edge lists of the resident stage-wise calls live in these workspaces
-    if ((rc = upload_image(ctx, s, 0, img, h, w, stride)))
-        return rc;
+    if (hc.image(0, img, h, w, stride))
+        return hc.rc;
     float ms_c = 0, ms_n = 0;
     const bool timed = t_conv || t_nms;
-    if ((rc = toed_sync(ctx, s, 1, h, w, timed ? &ms_c : nullptr, timed ? &ms_n : nullptr)))
+    if (int rc = toed_sync(ctx, s, 1, h, w, timed ? &ms_c : nullptr, timed ? &ms_n : nullptr))
         return rc;
     const ImageWS &ws = s.im[0];
     *n_kept = ws.n_kept;
@@ -606,14 +741,9 @@ extern "C" int ebvo_toed(ebvo_ctx *ctx, const uint8_t *img, int h, int w, ptrdif
     }
     if ((out && ws.n_kept > cap) || (all4 && ws.n_total > cap_all))
         return EBVO_ERR_CAPACITY;
-    if (out && ws.n_kept)
-        EBVO_HIP(ctx, hipMemcpyAsync(out, ws.edges, sizeof(ebvo_edge) * (size_t)ws.n_kept, hipMemcpyDeviceToHost,
-                                     s.stream));
-    if (all4 && ws.n_total)
-        EBVO_HIP(ctx, hipMemcpyAsync(all4, ws.all4, sizeof(double) * 4 * (size_t)ws.n_total, hipMemcpyDeviceToHost,
-                                     s.stream));
-    EBVO_HIP(ctx, hipStreamSynchronize(s.stream));
-    return EBVO_OK;
+    hc.down(out, ws.edges, sizeof(ebvo_edge) * (size_t)ws.n_kept);
+    hc.down(all4, ws.all4, sizeof(double) * 4 * (size_t)ws.n_total);
+    return hc.finish();
 }
 
 extern "C" int ebvo_toed_screen_audit(ebvo_ctx *ctx, const uint8_t *img, int h, int w, ptrdiff_t stride, ebvo_screen_audit *out)
@@ -671,18 +801,16 @@ extern "C" int ebvo_toed_pair(ebvo_ctx *ctx, const uint8_t *img_left, const uint
 {
     if (!ctx || !img_left || !img_right || !n_kept || !n_total || cap < 0)
         return EBVO_ERR_ARG;
-    EBVO_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
-    Slot *sp;
-    if ((rc = check_size(ctx, h, w)) || (rc = host_slot(ctx, &sp)))
+    if (int rc = check_size(ctx, h, w))
         return rc;
-    Slot &s = *sp;
+    HostCall hc(ctx, HostCall::PAIR_BUFFERS);
+    if (hc.rc)
+        return hc.rc;
+    Slot &s = hc.slot();
     ctx->sw_tag[0] = ctx->sw_tag[1] = 0;
-    if ((rc = upload_image(ctx, s, 0, img_left, h, w, stride_left)))
-        return rc;
-    if ((rc = upload_image(ctx, s, 1, img_right, h, w, stride_right)))
-        return rc;
-    if ((rc = toed_sync(ctx, s, 2, h, w, nullptr, nullptr)))
+    if (hc.image(0, img_left, h, w, stride_left) || hc.image(1, img_right, h, w, stride_right))
+        return hc.rc;
+    if (int rc = toed_sync(ctx, s, 2, h, w, nullptr, nullptr))
         return rc;
     ebvo_edge *outs[2] = {out_left, out_right};
     bool too_small = false;
@@ -698,11 +826,8 @@ extern "C" int ebvo_toed_pair(ebvo_ctx *ctx, const uint8_t *img_left, const uint
     if (too_small)
         return EBVO_ERR_CAPACITY;
     for (int k = 0; k < 2; ++k)
-        if (outs[k] && s.im[k].n_kept)
-            EBVO_HIP(ctx, hipMemcpyAsync(outs[k], s.im[k].edges, sizeof(ebvo_edge) * (size_t)s.im[k].n_kept,
-                                         hipMemcpyDeviceToHost, s.stream));
-    EBVO_HIP(ctx, hipStreamSynchronize(s.stream));
-    return EBVO_OK;
+        hc.down(outs[k], s.im[k].edges, sizeof(ebvo_edge) * (size_t)s.im[k].n_kept);
+    return hc.finish();
 }
 
 extern "C" int ebvo_epipolar_lines(const double F[9], const ebvo_edge *edges, int n, double *lines)
@@ -755,44 +880,30 @@ static int epi_candidates_impl(ebvo_ctx *ctx, const ebvo_edge *L, int nL, const 
         (nL > 0 && (!L || !lines)) || (nR > 0 && !R) || (stage_mask & ~EBVO_STAGE_ALL) || stage_mask == 0 ||
         !stereo_thresholds_ok(epi_thr, max_disp, orient_thr_deg, 0.0))
         return EBVO_ERR_ARG;
-    EBVO_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
-    Slot *sp;
-    if ((rc = host_slot(ctx, &sp)))
-        return rc;
-    Slot &s = *sp;
+    HostCall hc(ctx, HostCall::PAIR_BUFFERS);
+    if (hc.rc)
+        return hc.rc;
+    Slot &s = hc.slot();
     *n_pairs = 0;
     if (nL == 0 || nR == 0)
     {
         memset(row_ptr, 0, sizeof(int32_t) * ((size_t)nL + 1));
         return EBVO_OK;
     }
-    if ((rc = ebvo_grow(ctx, s, s.scratch_b, sizeof(ebvo_edge) * (size_t)nL)))
-        return rc;
-    if ((rc = ebvo_grow(ctx, s, s.scratch_c, sizeof(ebvo_edge) * (size_t)nR)))
-        return rc;
-    if ((rc = ebvo_grow(ctx, s, s.lines, sizeof(double) * 3 * (size_t)nL)))
-        return rc;
-    EBVO_HIP(ctx, hipMemcpyAsync(s.scratch_b.p, L, sizeof(ebvo_edge) * (size_t)nL, hipMemcpyHostToDevice, s.stream));
-    EBVO_HIP(ctx, hipMemcpyAsync(s.lines.p, lines, sizeof(double) * 3 * (size_t)nL, hipMemcpyHostToDevice, s.stream));
-    EBVO_HIP(ctx, hipMemcpyAsync(s.scratch_c.p, R, sizeof(ebvo_edge) * (size_t)nR, hipMemcpyHostToDevice, s.stream));
+    if (hc.grow(s.scratch_b, sizeof(ebvo_edge) * (size_t)nL) || hc.grow(s.scratch_c, sizeof(ebvo_edge) * (size_t)nR) ||
+        hc.grow(s.lines, sizeof(double) * 3 * (size_t)nL) || hc.up(s.scratch_b.p, L, sizeof(ebvo_edge) * (size_t)nL) ||
+        hc.up(s.lines.p, lines, sizeof(double) * 3 * (size_t)nL) || hc.up(s.scratch_c.p, R, sizeof(ebvo_edge) * (size_t)nR))
+        return hc.rc;
     const ebvo_edge *dL = (const ebvo_edge *)s.scratch_b.p, *dR = (const ebvo_edge *)s.scratch_c.p;
-    if ((rc = match_candidates_enqueue(ctx, s, dL, nL, nullptr, dR, nR, nullptr, 0, (const double *)s.lines.p, epi_thr,
-                                       max_disp, orient_thr_deg, stage_mask, false)))
+    if (int rc = match_candidates_enqueue(ctx, s, dL, nL, nullptr, dR, nR, nullptr, 0, (const double *)s.lines.p, epi_thr,
+                                          max_disp, orient_thr_deg, stage_mask, false))
         return rc;
-    // the total lands in the slot's pinned record (not in this stack frame); on any failure the stream is drained
-    // before returning so that no copy into the caller's row_ptr stays in flight
+    // the total lands in the slot's pinned record (not in this stack frame)
     unsigned long long *h_total_p = reinterpret_cast<unsigned long long *>(s.h_result);
-    {
-        hipError_t e1 = hipMemcpyAsync(h_total_p, s.d_total, sizeof(*h_total_p), hipMemcpyDeviceToHost, s.stream);
-        hipError_t e2 = e1 == hipSuccess ? hipMemcpyAsync(row_ptr, s.row_ptr.p, sizeof(int32_t) * ((size_t)nL + 1),
-                                                          hipMemcpyDeviceToHost, s.stream)
-                                         : hipSuccess;
-        hipError_t e3 = hipStreamSynchronize(s.stream);
-        if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess)
-            return ebvo_fail_hip(ctx, e1 != hipSuccess ? e1 : (e2 != hipSuccess ? e2 : e3), "candidate total read-back",
-                                 __FILE__, __LINE__);
-    }
+    hc.down(h_total_p, s.d_total, sizeof(*h_total_p));
+    hc.down(row_ptr, s.row_ptr.p, sizeof(int32_t) * ((size_t)nL + 1));
+    if (hc.finish())
+        return hc.rc;
     const unsigned long long h_total = *h_total_p;
     if (h_total > 0x7fffffffull)
     {
@@ -805,34 +916,25 @@ static int epi_candidates_impl(ebvo_ctx *ctx, const ebvo_edge *L, int nL, const 
         return (col_idx || cap > 0) ? EBVO_ERR_CAPACITY : EBVO_OK;
     if (np == 0 || !col_idx)
         return EBVO_OK;
-    if ((rc = ebvo_grow(ctx, s, s.col_idx, sizeof(int32_t) * (size_t)np)))
-        return rc;
+    if (hc.grow(s.col_idx, sizeof(int32_t) * (size_t)np))
+        return hc.rc;
     s.cap_pairs = np;
-    if ((rc = match_candidates_fill_enqueue(ctx, s, dL, nL, nullptr, dR, nR, nullptr, 0, (const double *)s.lines.p,
-                                            epi_thr, max_disp, orient_thr_deg, stage_mask)))
+    if (int rc = match_candidates_fill_enqueue(ctx, s, dL, nL, nullptr, dR, nR, nullptr, 0, (const double *)s.lines.p,
+                                               epi_thr, max_disp, orient_thr_deg, stage_mask))
         return rc;
-    // from here on copies into caller-owned memory are in flight: whatever fails, the stream is drained before returning
-    rc = [&]() -> int {
-        int r;
-        if (orient_ok)
-        {
-            // the third reference stage (apply_orientation_filter, src/Stereo_Matches.cpp:863-915) as one flag per listed pair
-            if ((r = ebvo_grow(ctx, s, s.keep, (size_t)np)) ||
-                (r = match_orient_flags_enqueue(ctx, s, dL, nL, dR, (const int32_t *)s.row_ptr.p, (const int32_t *)s.col_idx.p,
-                                                np, orient_thr_deg, (uint8_t *)s.keep.p)))
-                return r;
-        }
-        EBVO_HIP(ctx, hipMemcpyAsync(col_idx, s.col_idx.p, sizeof(int32_t) * (size_t)np, hipMemcpyDeviceToHost, s.stream));
-        if (orient_ok)
-            EBVO_HIP(ctx, hipMemcpyAsync(orient_ok, s.keep.p, (size_t)np, hipMemcpyDeviceToHost, s.stream));
-        return EBVO_OK;
-    }();
-    if (rc)
+    if (orient_ok)
     {
-        (void)hipStreamSynchronize(s.stream);
-        return rc;
+        // the third reference stage (apply_orientation_filter, src/Stereo_Matches.cpp:863-915) as one flag per listed pair
+        if (hc.grow(s.keep, (size_t)np))
+            return hc.rc;
+        if (int rc = match_orient_flags_enqueue(ctx, s, dL, nL, dR, (const int32_t *)s.row_ptr.p, (const int32_t *)s.col_idx.p,
+                                                np, orient_thr_deg, (uint8_t *)s.keep.p))
+            return rc;
     }
-    EBVO_HIP(ctx, hipStreamSynchronize(s.stream));
+    hc.down(col_idx, s.col_idx.p, sizeof(int32_t) * (size_t)np);
+    hc.down(orient_ok, s.keep.p, (size_t)np);
+    if (hc.finish())
+        return hc.rc;
     s.cap_pairs = 0; // the pipeline re-establishes its own capacity
     return EBVO_OK;
 }
@@ -851,22 +953,20 @@ extern "C" int ebvo_sobel_gradients(ebvo_ctx *ctx, const uint8_t *img, int h, in
 {
     if (!ctx || !img || !gx || !gy)
         return EBVO_ERR_ARG;
-    EBVO_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
-    Slot *sp;
-    if ((rc = check_size(ctx, h, w)) || (rc = host_slot(ctx, &sp)))
+    if (int rc = check_size(ctx, h, w))
         return rc;
-    Slot &s = *sp;
+    HostCall hc(ctx, HostCall::PAIR_BUFFERS);
+    if (hc.rc)
+        return hc.rc;
+    Slot &s = hc.slot();
     const size_t bytes = sizeof(float) * (size_t)h * w;
-    if ((rc = upload_image(ctx, s, 0, img, h, w, stride)) || (rc = ebvo_grow(ctx, s, s.grad_x, bytes)) ||
-        (rc = ebvo_grow(ctx, s, s.grad_y, bytes)))
+    if (hc.image(0, img, h, w, stride) || hc.grow(s.grad_x, bytes) || hc.grow(s.grad_y, bytes))
+        return hc.rc;
+    if (int rc = refine_sobel_enqueue(ctx, s, s.im[0].img, h, w, w, (float *)s.grad_x.p, (float *)s.grad_y.p, nullptr))
         return rc;
-    if ((rc = refine_sobel_enqueue(ctx, s, s.im[0].img, h, w, w, (float *)s.grad_x.p, (float *)s.grad_y.p, nullptr)))
-        return rc;
-    EBVO_HIP(ctx, hipMemcpyAsync(gx, s.grad_x.p, bytes, hipMemcpyDeviceToHost, s.stream));
-    EBVO_HIP(ctx, hipMemcpyAsync(gy, s.grad_y.p, bytes, hipMemcpyDeviceToHost, s.stream));
-    EBVO_HIP(ctx, hipStreamSynchronize(s.stream));
-    return EBVO_OK;
+    hc.down(gx, s.grad_x.p, bytes);
+    hc.down(gy, s.grad_y.p, bytes);
+    return hc.finish();
 }
 
 extern "C" int ebvo_gn_refine_stereo(ebvo_ctx *ctx, const uint8_t *imgL, const uint8_t *imgR, int h, int w,
@@ -878,37 +978,29 @@ extern "C" int ebvo_gn_refine_stereo(ebvo_ctx *ctx, const uint8_t *imgL, const u
     if (!ctx || !imgL || !imgR || nL < 0 || !row_ptr || !params || (nL > 0 && (!L || !lines)) || params->max_iter < 1 ||
         !(params->tol >= 0) || !(params->huber_delta > 0))
         return EBVO_ERR_ARG;
-    EBVO_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
-    Slot *sp;
-    if ((rc = check_size(ctx, h, w)) || (rc = host_slot(ctx, &sp)))
+    if (int rc = check_size(ctx, h, w))
         return rc;
-    Slot &s = *sp;
-    if (row_ptr[0] != 0)
+    HostCall hc(ctx, HostCall::PAIR_BUFFERS);
+    if (hc.rc)
+        return hc.rc;
+    Slot &s = hc.slot();
+    int64_t np = 0;
+    if (check_csr(row_ptr, nL, &np))
         return EBVO_ERR_ARG;
-    for (int i = 0; i < nL; ++i)
-        if (row_ptr[i + 1] < row_ptr[i])
-            return EBVO_ERR_ARG;
-    const int64_t np = row_ptr[nL];
     if (np == 0)
         return EBVO_OK;
     if (!cand_xy || !alpha || !score || !confidence || !validity || !iters || !refined_xy)
         return EBVO_ERR_ARG;
     const size_t npz = (size_t)np;
-    if ((rc = upload_image(ctx, s, 0, imgL, h, w, strideL)) || (rc = upload_image(ctx, s, 1, imgR, h, w, strideR)) ||
-        (rc = ebvo_grow(ctx, s, s.scratch_b, sizeof(ebvo_edge) * (size_t)nL)) ||
-        (rc = ebvo_grow(ctx, s, s.lines, sizeof(double) * 3 * (size_t)nL)) ||
-        (rc = ebvo_grow(ctx, s, s.row_ptr, sizeof(int32_t) * ((size_t)nL + 1))) ||
-        (rc = ebvo_grow(ctx, s, s.pair_left, sizeof(int32_t) * npz)) || (rc = ebvo_grow(ctx, s, s.gn_xy, sizeof(double) * 2 * npz)) ||
-        (rc = ebvo_grow(ctx, s, s.gn_out, sizeof(double) * 5 * npz)) || (rc = ebvo_grow(ctx, s, s.gn_valid, npz)) ||
-        (rc = ebvo_grow(ctx, s, s.gn_iters, sizeof(int32_t) * npz)))
-        return rc;
-    hipStream_t st = s.stream;
-    EBVO_HIP(ctx, hipMemcpyAsync(s.scratch_b.p, L, sizeof(ebvo_edge) * (size_t)nL, hipMemcpyHostToDevice, st));
-    EBVO_HIP(ctx, hipMemcpyAsync(s.lines.p, lines, sizeof(double) * 3 * (size_t)nL, hipMemcpyHostToDevice, st));
-    EBVO_HIP(ctx, hipMemcpyAsync(s.row_ptr.p, row_ptr, sizeof(int32_t) * ((size_t)nL + 1), hipMemcpyHostToDevice, st));
-    EBVO_HIP(ctx, hipMemcpyAsync(s.gn_xy.p, cand_xy, sizeof(double) * 2 * npz, hipMemcpyHostToDevice, st));
+    if (hc.image(0, imgL, h, w, strideL) || hc.image(1, imgR, h, w, strideR) || hc.grow(s.scratch_b, sizeof(ebvo_edge) * (size_t)nL) ||
+        hc.grow(s.lines, sizeof(double) * 3 * (size_t)nL) || hc.grow(s.row_ptr, sizeof(int32_t) * ((size_t)nL + 1)) ||
+        hc.grow(s.pair_left, sizeof(int32_t) * npz) || hc.grow(s.gn_xy, sizeof(double) * 2 * npz) ||
+        hc.grow(s.gn_out, sizeof(double) * 5 * npz) || hc.grow(s.gn_valid, npz) || hc.grow(s.gn_iters, sizeof(int32_t) * npz) ||
+        hc.up(s.scratch_b.p, L, sizeof(ebvo_edge) * (size_t)nL) || hc.up(s.lines.p, lines, sizeof(double) * 3 * (size_t)nL) ||
+        hc.up(s.row_ptr.p, row_ptr, sizeof(int32_t) * ((size_t)nL + 1)) || hc.up(s.gn_xy.p, cand_xy, sizeof(double) * 2 * npz))
+        return hc.rc;
     double *out = (double *)s.gn_out.p;
+    int rc;
     if ((rc = match_expand_rows_enqueue(ctx, s, (const int32_t *)s.row_ptr.p, nL, np, (int32_t *)s.pair_left.p)) ||
         (rc = refine_gn_stereo_enqueue(ctx, s, s.im[0].img, s.im[1].img, nullptr, h, w, (const ebvo_edge *)s.scratch_b.p, nL,
                                        (const double *)s.lines.p, (const int32_t *)s.pair_left.p,
@@ -917,14 +1009,13 @@ extern "C" int ebvo_gn_refine_stereo(ebvo_ctx *ctx, const uint8_t *imgL, const u
                                        out, out + npz, out + 2 * npz, (uint8_t *)s.gn_valid.p, (int32_t *)s.gn_iters.p,
                                        out + 3 * npz)))
         return rc;
-    EBVO_HIP(ctx, hipMemcpyAsync(alpha, out, sizeof(double) * npz, hipMemcpyDeviceToHost, st));
-    EBVO_HIP(ctx, hipMemcpyAsync(score, out + npz, sizeof(double) * npz, hipMemcpyDeviceToHost, st));
-    EBVO_HIP(ctx, hipMemcpyAsync(confidence, out + 2 * npz, sizeof(double) * npz, hipMemcpyDeviceToHost, st));
-    EBVO_HIP(ctx, hipMemcpyAsync(refined_xy, out + 3 * npz, sizeof(double) * 2 * npz, hipMemcpyDeviceToHost, st));
-    EBVO_HIP(ctx, hipMemcpyAsync(validity, s.gn_valid.p, npz, hipMemcpyDeviceToHost, st));
-    EBVO_HIP(ctx, hipMemcpyAsync(iters, s.gn_iters.p, sizeof(int32_t) * npz, hipMemcpyDeviceToHost, st));
-    EBVO_HIP(ctx, hipStreamSynchronize(st));
-    return EBVO_OK;
+    hc.down(alpha, out, sizeof(double) * npz);
+    hc.down(score, out + npz, sizeof(double) * npz);
+    hc.down(confidence, out + 2 * npz, sizeof(double) * npz);
+    hc.down(refined_xy, out + 3 * npz, sizeof(double) * 2 * npz);
+    hc.down(validity, s.gn_valid.p, npz);
+    hc.down(iters, s.gn_iters.p, sizeof(int32_t) * npz);
+    return hc.finish();
 }
 
 extern "C" int ebvo_edge_patches(ebvo_ctx *ctx, const uint8_t *img, int h, int w, ptrdiff_t stride,
@@ -932,28 +1023,22 @@ extern "C" int ebvo_edge_patches(ebvo_ctx *ctx, const uint8_t *img, int h, int w
 {
     if (!ctx || !img || n < 0 || (n > 0 && (!edges || !patches)))
         return EBVO_ERR_ARG;
-    EBVO_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
-    Slot *sp;
-    if ((rc = check_size(ctx, h, w)) || (rc = host_slot(ctx, &sp)))
+    if (int rc = check_size(ctx, h, w))
         return rc;
-    Slot &s = *sp;
+    HostCall hc(ctx, HostCall::PAIR_BUFFERS);
+    if (hc.rc)
+        return hc.rc;
+    Slot &s = hc.slot();
     if (n == 0)
         return EBVO_OK;
-    if ((rc = upload_image(ctx, s, 0, img, h, w, stride)))
+    if (hc.image(0, img, h, w, stride) || hc.grow(s.scratch_b, sizeof(ebvo_edge) * (size_t)n) ||
+        hc.grow(s.patches_raw, sizeof(float) * 98 * (size_t)n) || hc.up(s.scratch_b.p, edges, sizeof(ebvo_edge) * (size_t)n))
+        return hc.rc;
+    if (int rc = match_patches_enqueue(ctx, s, s.im[0].img, h, w, w, (const ebvo_edge *)s.scratch_b.p, n, nullptr, 0,
+                                       (float *)s.patches_raw.p, nullptr, nullptr))
         return rc;
-    if ((rc = ebvo_grow(ctx, s, s.scratch_b, sizeof(ebvo_edge) * (size_t)n)))
-        return rc;
-    if ((rc = ebvo_grow(ctx, s, s.patches_raw, sizeof(float) * 98 * (size_t)n)))
-        return rc;
-    EBVO_HIP(ctx, hipMemcpyAsync(s.scratch_b.p, edges, sizeof(ebvo_edge) * (size_t)n, hipMemcpyHostToDevice, s.stream));
-    if ((rc = match_patches_enqueue(ctx, s, s.im[0].img, h, w, w, (const ebvo_edge *)s.scratch_b.p, n, nullptr, 0,
-                                    (float *)s.patches_raw.p, nullptr, nullptr)))
-        return rc;
-    EBVO_HIP(ctx, hipMemcpyAsync(patches, s.patches_raw.p, sizeof(float) * 98 * (size_t)n, hipMemcpyDeviceToHost,
-                                 s.stream));
-    EBVO_HIP(ctx, hipStreamSynchronize(s.stream));
-    return EBVO_OK;
+    hc.down(patches, s.patches_raw.p, sizeof(float) * 98 * (size_t)n);
+    return hc.finish();
 }
 
 extern "C" int ebvo_ncc_pairs(ebvo_ctx *ctx, const uint8_t *imgL, const uint8_t *imgR, int h, int w,
@@ -963,100 +1048,59 @@ extern "C" int ebvo_ncc_pairs(ebvo_ctx *ctx, const uint8_t *imgL, const uint8_t 
 {
     if (!ctx || !imgL || !imgR || nL < 0 || !row_ptr || (nL > 0 && !L))
         return EBVO_ERR_ARG;
-    EBVO_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
-    Slot *sp;
-    if ((rc = check_size(ctx, h, w)) || (rc = host_slot(ctx, &sp)))
+    if (int rc = check_size(ctx, h, w))
         return rc;
-    Slot &s = *sp;
-    if (row_ptr[0] != 0)
-        return EBVO_ERR_ARG;
-    for (int i = 0; i < nL; ++i)
-        if (row_ptr[i + 1] < row_ptr[i])
-            return EBVO_ERR_ARG;
-    const int64_t np = row_ptr[nL];
-    if (np > 0 && !Rc)
+    HostCall hc(ctx, HostCall::PAIR_BUFFERS);
+    if (hc.rc)
+        return hc.rc;
+    Slot &s = hc.slot();
+    int64_t np = 0;
+    if (check_csr(row_ptr, nL, &np) || (np > 0 && !Rc))
         return EBVO_ERR_ARG;
     if (nL == 0)
         return EBVO_OK;
-    if ((rc = upload_image(ctx, s, 0, imgL, h, w, strideL)))
-        return rc;
-    if ((rc = upload_image(ctx, s, 1, imgR, h, w, strideR)))
-        return rc;
-    if ((rc = ebvo_grow(ctx, s, s.scratch_b, sizeof(ebvo_edge) * (size_t)nL)))
-        return rc;
-    if ((rc = ebvo_grow(ctx, s, s.rc_edges, sizeof(ebvo_edge) * ((size_t)np + 1))))
-        return rc;
-    if ((rc = ebvo_grow(ctx, s, s.row_ptr, sizeof(int32_t) * ((size_t)nL + 1))))
-        return rc;
-    if ((rc = ebvo_grow(ctx, s, s.patches_raw, sizeof(float) * 98 * (size_t)nL)))
-        return rc;
-    if ((rc = ebvo_grow(ctx, s, s.patches_norm, sizeof(float) * 98 * (size_t)nL)))
-        return rc;
-    if ((rc = ebvo_grow(ctx, s, s.patches_flag, 2 * (size_t)nL)))
-        return rc;
-    if (sims && (rc = ebvo_grow(ctx, s, s.sims, sizeof(double) * 4 * ((size_t)np + 1))))
-        return rc;
-    if ((rc = ebvo_grow(ctx, s, s.best, sizeof(double) * ((size_t)np + 1))))
-        return rc;
-    if ((rc = ebvo_grow(ctx, s, s.keep, (size_t)np + 1)))
-        return rc;
-    EBVO_HIP(ctx, hipMemcpyAsync(s.scratch_b.p, L, sizeof(ebvo_edge) * (size_t)nL, hipMemcpyHostToDevice, s.stream));
-    if (np)
-        EBVO_HIP(ctx, hipMemcpyAsync(s.rc_edges.p, Rc, sizeof(ebvo_edge) * (size_t)np, hipMemcpyHostToDevice, s.stream));
-    EBVO_HIP(ctx, hipMemcpyAsync(s.row_ptr.p, row_ptr, sizeof(int32_t) * ((size_t)nL + 1), hipMemcpyHostToDevice,
-                                 s.stream));
+    const size_t nLz = (size_t)nL, npz = (size_t)np;
+    if (hc.image(0, imgL, h, w, strideL) || hc.image(1, imgR, h, w, strideR) || hc.grow(s.scratch_b, sizeof(ebvo_edge) * nLz) ||
+        hc.grow(s.rc_edges, sizeof(ebvo_edge) * (npz + 1)) || hc.grow(s.row_ptr, sizeof(int32_t) * (nLz + 1)) ||
+        hc.grow(s.patches_raw, sizeof(float) * 98 * nLz) || hc.grow(s.patches_norm, sizeof(float) * 98 * nLz) ||
+        hc.grow(s.patches_flag, 2 * nLz) || (sims && hc.grow(s.sims, sizeof(double) * 4 * (npz + 1))) ||
+        hc.grow(s.best, sizeof(double) * (npz + 1)) || hc.grow(s.keep, npz + 1) || hc.up(s.scratch_b.p, L, sizeof(ebvo_edge) * nLz) ||
+        hc.up(s.rc_edges.p, Rc, sizeof(ebvo_edge) * npz) || hc.up(s.row_ptr.p, row_ptr, sizeof(int32_t) * (nLz + 1)))
+        return hc.rc;
+    int rc;
     if ((rc = match_patches_enqueue(ctx, s, s.im[0].img, h, w, w, (const ebvo_edge *)s.scratch_b.p, nL, nullptr, 0,
-                                    (float *)s.patches_raw.p, (float *)s.patches_norm.p, (uint8_t *)s.patches_flag.p)))
-        return rc;
-    if ((rc = match_ncc_pairs_enqueue(ctx, s, s.im[1].img, h, w, w, (const ebvo_edge *)s.rc_edges.p,
+                                    (float *)s.patches_raw.p, (float *)s.patches_norm.p, (uint8_t *)s.patches_flag.p)) ||
+        (rc = match_ncc_pairs_enqueue(ctx, s, s.im[1].img, h, w, w, (const ebvo_edge *)s.rc_edges.p,
                                       (const int32_t *)s.row_ptr.p, nL, np, (const float *)s.patches_norm.p,
                                       (const uint8_t *)s.patches_flag.p, thr, sims ? (double *)s.sims.p : nullptr,
                                       (double *)s.best.p, (uint8_t *)s.keep.p)))
         return rc;
-    if (left_patches)
-        EBVO_HIP(ctx, hipMemcpyAsync(left_patches, s.patches_raw.p, sizeof(float) * 98 * (size_t)nL,
-                                     hipMemcpyDeviceToHost, s.stream));
-    if (np)
-    {
-        if (sims)
-            EBVO_HIP(ctx, hipMemcpyAsync(sims, s.sims.p, sizeof(double) * 4 * (size_t)np, hipMemcpyDeviceToHost, s.stream));
-        if (best)
-            EBVO_HIP(ctx, hipMemcpyAsync(best, s.best.p, sizeof(double) * (size_t)np, hipMemcpyDeviceToHost, s.stream));
-        if (keep)
-            EBVO_HIP(ctx, hipMemcpyAsync(keep, s.keep.p, (size_t)np, hipMemcpyDeviceToHost, s.stream));
-    }
-    EBVO_HIP(ctx, hipStreamSynchronize(s.stream));
-    return EBVO_OK;
+    hc.down(left_patches, s.patches_raw.p, sizeof(float) * 98 * nLz);
+    hc.down(sims, s.sims.p, sizeof(double) * 4 * npz);
+    hc.down(best, s.best.p, sizeof(double) * npz);
+    hc.down(keep, s.keep.p, npz);
+    return hc.finish();
 }
 
 extern "C" int ebvo_ncc_patches(ebvo_ctx *ctx, const float *A, const float *B, int n, double *sim)
 {
     if (!ctx || n < 0 || (n > 0 && (!A || !B || !sim)))
         return EBVO_ERR_ARG;
-    EBVO_HIP(ctx, hipSetDevice(ctx->device));
-    if (n == 0)
+    if (n == 0) // (before the slot is taken: an empty list leaves the pair as it is)
         return EBVO_OK;
-    int rc;
-    Slot *sp;
-    if ((rc = host_slot(ctx, &sp)))
-        return rc;
-    Slot &s = *sp;
+    HostCall hc(ctx, HostCall::PAIR_BUFFERS);
+    if (hc.rc)
+        return hc.rc;
+    Slot &s = hc.slot();
     const size_t pb = sizeof(float) * 49 * (size_t)n;
-    if ((rc = ebvo_grow(ctx, s, s.scratch_b, pb)))
+    if (hc.grow(s.scratch_b, pb) || hc.grow(s.scratch_c, pb) || hc.grow(s.scratch_d, sizeof(double) * (size_t)n) ||
+        hc.up(s.scratch_b.p, A, pb) || hc.up(s.scratch_c.p, B, pb))
+        return hc.rc;
+    if (int rc = match_ncc_stored_enqueue(ctx, s, (const float *)s.scratch_b.p, (const float *)s.scratch_c.p, n,
+                                          (double *)s.scratch_d.p))
         return rc;
-    if ((rc = ebvo_grow(ctx, s, s.scratch_c, pb)))
-        return rc;
-    if ((rc = ebvo_grow(ctx, s, s.scratch_d, sizeof(double) * (size_t)n)))
-        return rc;
-    EBVO_HIP(ctx, hipMemcpyAsync(s.scratch_b.p, A, pb, hipMemcpyHostToDevice, s.stream));
-    EBVO_HIP(ctx, hipMemcpyAsync(s.scratch_c.p, B, pb, hipMemcpyHostToDevice, s.stream));
-    if ((rc = match_ncc_stored_enqueue(ctx, s, (const float *)s.scratch_b.p, (const float *)s.scratch_c.p, n,
-                                       (double *)s.scratch_d.p)))
-        return rc;
-    EBVO_HIP(ctx, hipMemcpyAsync(sim, s.scratch_d.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s.stream));
-    EBVO_HIP(ctx, hipStreamSynchronize(s.stream));
-    return EBVO_OK;
+    hc.down(sim, s.scratch_d.p, sizeof(double) * (size_t)n);
+    return hc.finish();
 }
 
 extern "C" int ebvo_ncc_quads(ebvo_ctx *ctx, const float *kfL, const float *kfR, const float *cfL, const float *cfR,
@@ -2439,91 +2483,63 @@ extern "C" int ebvo_gn_refine_temporal(ebvo_ctx *ctx, const uint8_t *imgKF, cons
     if (!ctx || !imgKF || !imgCF || n < 0 || !params || params->max_iter < 1 || !(params->tol >= 0) ||
         !(params->huber_delta > 0))
         return EBVO_ERR_ARG;
-    EBVO_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
-    Slot *sp;
-    if ((rc = check_size(ctx, h, w)) || (rc = host_slot(ctx, &sp)))
+    if (int rc = check_size(ctx, h, w))
         return rc;
-    Slot &s = *sp;
+    HostCall hc(ctx, HostCall::PAIR_BUFFERS);
+    if (hc.rc)
+        return hc.rc;
+    Slot &s = hc.slot();
     if (n == 0)
         return EBVO_OK;
     if (!kf || !cf || !init_disp || !disp || !score || !validity || !iters)
         return EBVO_ERR_ARG;
     const size_t nz = (size_t)n;
-    if ((rc = upload_image(ctx, s, 0, imgKF, h, w, strideKF)) || (rc = upload_image(ctx, s, 1, imgCF, h, w, strideCF)) ||
-        (rc = ebvo_grow(ctx, s, s.scratch_b, sizeof(ebvo_edge) * nz)) ||
-        (rc = ebvo_grow(ctx, s, s.scratch_c, sizeof(ebvo_edge) * nz)) || (rc = ebvo_grow(ctx, s, s.gn_xy, sizeof(double) * 2 * nz)) ||
-        (rc = ebvo_grow(ctx, s, s.gn_out, sizeof(double) * 3 * nz)) || (rc = ebvo_grow(ctx, s, s.gn_valid, nz)) ||
-        (rc = ebvo_grow(ctx, s, s.gn_iters, sizeof(int32_t) * nz)))
-        return rc;
-    hipStream_t st = s.stream;
-    EBVO_HIP(ctx, hipMemcpyAsync(s.scratch_b.p, kf, sizeof(ebvo_edge) * nz, hipMemcpyHostToDevice, st));
-    EBVO_HIP(ctx, hipMemcpyAsync(s.scratch_c.p, cf, sizeof(ebvo_edge) * nz, hipMemcpyHostToDevice, st));
-    EBVO_HIP(ctx, hipMemcpyAsync(s.gn_xy.p, init_disp, sizeof(double) * 2 * nz, hipMemcpyHostToDevice, st));
+    if (hc.image(0, imgKF, h, w, strideKF) || hc.image(1, imgCF, h, w, strideCF) || hc.grow(s.scratch_b, sizeof(ebvo_edge) * nz) ||
+        hc.grow(s.scratch_c, sizeof(ebvo_edge) * nz) || hc.grow(s.gn_xy, sizeof(double) * 2 * nz) ||
+        hc.grow(s.gn_out, sizeof(double) * 3 * nz) || hc.grow(s.gn_valid, nz) || hc.grow(s.gn_iters, sizeof(int32_t) * nz) ||
+        hc.up(s.scratch_b.p, kf, sizeof(ebvo_edge) * nz) || hc.up(s.scratch_c.p, cf, sizeof(ebvo_edge) * nz) ||
+        hc.up(s.gn_xy.p, init_disp, sizeof(double) * 2 * nz))
+        return hc.rc;
     double *out = (double *)s.gn_out.p;
     // (the refinement packs the current-frame image itself: intensity + Sobel gradients per bilinear cell)
-    if ((rc = refine_gn_temporal_enqueue(ctx, s, s.im[0].img, s.im[1].img, nullptr, h, w,
-                                         (const ebvo_edge *)s.scratch_b.p, (const ebvo_edge *)s.scratch_c.p,
-                                         (const double *)s.gn_xy.p, n, params->max_iter, params->tol, params->huber_delta,
-                                         out, out + 2 * nz, (uint8_t *)s.gn_valid.p, (int32_t *)s.gn_iters.p)))
+    if (int rc = refine_gn_temporal_enqueue(ctx, s, s.im[0].img, s.im[1].img, nullptr, h, w,
+                                            (const ebvo_edge *)s.scratch_b.p, (const ebvo_edge *)s.scratch_c.p,
+                                            (const double *)s.gn_xy.p, n, params->max_iter, params->tol, params->huber_delta,
+                                            out, out + 2 * nz, (uint8_t *)s.gn_valid.p, (int32_t *)s.gn_iters.p))
         return rc;
-    EBVO_HIP(ctx, hipMemcpyAsync(disp, out, sizeof(double) * 2 * nz, hipMemcpyDeviceToHost, st));
-    EBVO_HIP(ctx, hipMemcpyAsync(score, out + 2 * nz, sizeof(double) * nz, hipMemcpyDeviceToHost, st));
-    EBVO_HIP(ctx, hipMemcpyAsync(validity, s.gn_valid.p, nz, hipMemcpyDeviceToHost, st));
-    EBVO_HIP(ctx, hipMemcpyAsync(iters, s.gn_iters.p, sizeof(int32_t) * nz, hipMemcpyDeviceToHost, st));
-    EBVO_HIP(ctx, hipStreamSynchronize(st));
-    return EBVO_OK;
+    hc.down(disp, out, sizeof(double) * 2 * nz);
+    hc.down(score, out + 2 * nz, sizeof(double) * nz);
+    hc.down(validity, s.gn_valid.p, nz);
+    hc.down(iters, s.gn_iters.p, sizeof(int32_t) * nz);
+    return hc.finish();
 }
 
 // ---- stage glue on CSR candidate lists -------------------------------------------------------------------------
-static int check_csr(const int32_t *row_ptr, int nL, int64_t *np)
-{
-    if (nL < 0 || !row_ptr || row_ptr[0] != 0)
-        return EBVO_ERR_ARG;
-    for (int i = 0; i < nL; ++i)
-        if (row_ptr[i + 1] < row_ptr[i])
-            return EBVO_ERR_ARG;
-    *np = row_ptr[nL];
-    return EBVO_OK;
-}
-
 static int row_select(ebvo_ctx *ctx, const int32_t *row_ptr, int nL, const double *scores, double thr, int mode,
                       int32_t *new_count, int32_t *order)
 {
     int64_t np = 0;
     if (!ctx || check_csr(row_ptr, nL, &np) || (nL > 0 && !new_count) || (np > 0 && (!scores || !order)))
         return EBVO_ERR_ARG;
-    EBVO_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
-    Slot *sp;
-    if ((rc = host_slot(ctx, &sp)))
-        return rc;
-    Slot &s = *sp;
+    HostCall hc(ctx, HostCall::PAIR_BUFFERS);
+    if (hc.rc)
+        return hc.rc;
+    Slot &s = hc.slot();
     if (nL == 0)
         return EBVO_OK;
-    const size_t npz = (size_t)np;
-    if ((rc = ebvo_grow(ctx, s, s.row_ptr, sizeof(int32_t) * ((size_t)nL + 1))) ||
-        (rc = ebvo_grow(ctx, s, s.best, sizeof(double) * (npz + 1))) ||
-        (rc = ebvo_grow(ctx, s, s.cand_cnt, sizeof(int32_t) * ((size_t)nL + 1))) ||
-        (rc = ebvo_grow(ctx, s, s.pair_left, sizeof(int32_t) * (npz + 1))))
+    const size_t npz = (size_t)np, nLz = (size_t)nL;
+    if (hc.grow(s.row_ptr, sizeof(int32_t) * (nLz + 1)) || hc.grow(s.best, sizeof(double) * (npz + 1)) ||
+        hc.grow(s.cand_cnt, sizeof(int32_t) * (nLz + 1)) || hc.grow(s.pair_left, sizeof(int32_t) * (npz + 1)) ||
+        hc.up(s.row_ptr.p, row_ptr, sizeof(int32_t) * (nLz + 1)) || hc.up(s.best.p, scores, sizeof(double) * npz))
+        return hc.rc;
+    const int32_t *d_rp = (const int32_t *)s.row_ptr.p;
+    int32_t *d_cnt = (int32_t *)s.cand_cnt.p, *d_order = (int32_t *)s.pair_left.p;
+    if (int rc = mode == 2 ? glue_keep_best_enqueue(ctx, s, d_rp, nL, (const double *)s.best.p, d_cnt, d_order)
+                           : glue_bnb_enqueue(ctx, s, d_rp, nL, (const double *)s.best.p, thr, mode, d_cnt, d_order))
         return rc;
-    hipStream_t st = s.stream;
-    EBVO_HIP(ctx, hipMemcpyAsync(s.row_ptr.p, row_ptr, sizeof(int32_t) * ((size_t)nL + 1), hipMemcpyHostToDevice, st));
-    if (npz)
-        EBVO_HIP(ctx, hipMemcpyAsync(s.best.p, scores, sizeof(double) * npz, hipMemcpyHostToDevice, st));
-    if (mode == 2)
-        rc = glue_keep_best_enqueue(ctx, s, (const int32_t *)s.row_ptr.p, nL, (const double *)s.best.p,
-                                    (int32_t *)s.cand_cnt.p, (int32_t *)s.pair_left.p);
-    else
-        rc = glue_bnb_enqueue(ctx, s, (const int32_t *)s.row_ptr.p, nL, (const double *)s.best.p, thr, mode,
-                              (int32_t *)s.cand_cnt.p, (int32_t *)s.pair_left.p);
-    if (rc)
-        return rc;
-    EBVO_HIP(ctx, hipMemcpyAsync(new_count, s.cand_cnt.p, sizeof(int32_t) * (size_t)nL, hipMemcpyDeviceToHost, st));
-    if (npz)
-        EBVO_HIP(ctx, hipMemcpyAsync(order, s.pair_left.p, sizeof(int32_t) * npz, hipMemcpyDeviceToHost, st));
-    EBVO_HIP(ctx, hipStreamSynchronize(st));
-    return EBVO_OK;
+    hc.down(new_count, d_cnt, sizeof(int32_t) * nLz);
+    hc.down(order, d_order, sizeof(int32_t) * npz);
+    return hc.finish();
 }
 
 extern "C" int ebvo_bnb_test(ebvo_ctx *ctx, const int32_t *row_ptr, int nL, const double *scores, double ratio_thr,
@@ -2544,31 +2560,25 @@ extern "C" int ebvo_epipolar_shift(ebvo_ctx *ctx, const ebvo_edge *cand, const d
     int64_t np = 0;
     if (!ctx || check_csr(row_ptr, nL, &np) || (np > 0 && (!cand || !lines || !shifted)))
         return EBVO_ERR_ARG;
-    EBVO_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
-    Slot *sp;
-    if ((rc = host_slot(ctx, &sp)))
-        return rc;
-    Slot &s = *sp;
+    HostCall hc(ctx, HostCall::PAIR_BUFFERS);
+    if (hc.rc)
+        return hc.rc;
+    Slot &s = hc.slot();
     if (np == 0)
         return EBVO_OK;
-    const size_t npz = (size_t)np;
-    if ((rc = ebvo_grow(ctx, s, s.row_ptr, sizeof(int32_t) * ((size_t)nL + 1))) ||
-        (rc = ebvo_grow(ctx, s, s.lines, sizeof(double) * 3 * (size_t)nL)) ||
-        (rc = ebvo_grow(ctx, s, s.rc_edges, sizeof(ebvo_edge) * npz)) || (rc = ebvo_grow(ctx, s, s.scratch_c, sizeof(ebvo_edge) * npz)) ||
-        (rc = ebvo_grow(ctx, s, s.pair_left, sizeof(int32_t) * npz)))
-        return rc;
-    hipStream_t st = s.stream;
-    EBVO_HIP(ctx, hipMemcpyAsync(s.row_ptr.p, row_ptr, sizeof(int32_t) * ((size_t)nL + 1), hipMemcpyHostToDevice, st));
-    EBVO_HIP(ctx, hipMemcpyAsync(s.lines.p, lines, sizeof(double) * 3 * (size_t)nL, hipMemcpyHostToDevice, st));
-    EBVO_HIP(ctx, hipMemcpyAsync(s.rc_edges.p, cand, sizeof(ebvo_edge) * npz, hipMemcpyHostToDevice, st));
+    const size_t npz = (size_t)np, nLz = (size_t)nL;
+    if (hc.grow(s.row_ptr, sizeof(int32_t) * (nLz + 1)) || hc.grow(s.lines, sizeof(double) * 3 * nLz) ||
+        hc.grow(s.rc_edges, sizeof(ebvo_edge) * npz) || hc.grow(s.scratch_c, sizeof(ebvo_edge) * npz) ||
+        hc.grow(s.pair_left, sizeof(int32_t) * npz) || hc.up(s.row_ptr.p, row_ptr, sizeof(int32_t) * (nLz + 1)) ||
+        hc.up(s.lines.p, lines, sizeof(double) * 3 * nLz) || hc.up(s.rc_edges.p, cand, sizeof(ebvo_edge) * npz))
+        return hc.rc;
+    int rc;
     if ((rc = match_expand_rows_enqueue(ctx, s, (const int32_t *)s.row_ptr.p, nL, np, (int32_t *)s.pair_left.p)) ||
         (rc = glue_shift_enqueue(ctx, s, (const ebvo_edge *)s.rc_edges.p, (const double *)s.lines.p,
                                  (const int32_t *)s.pair_left.p, np, (ebvo_edge *)s.scratch_c.p)))
         return rc;
-    EBVO_HIP(ctx, hipMemcpyAsync(shifted, s.scratch_c.p, sizeof(ebvo_edge) * npz, hipMemcpyDeviceToHost, st));
-    EBVO_HIP(ctx, hipStreamSynchronize(st));
-    return EBVO_OK;
+    hc.down(shifted, s.scratch_c.p, sizeof(ebvo_edge) * npz);
+    return hc.finish();
 }
 
 extern "C" int ebvo_cluster_rows(ebvo_ctx *ctx, const ebvo_edge *cand, const int32_t *row_ptr, int nL, int by_orientation,
@@ -2577,36 +2587,25 @@ extern "C" int ebvo_cluster_rows(ebvo_ctx *ctx, const ebvo_edge *cand, const int
     int64_t np = 0;
     if (!ctx || check_csr(row_ptr, nL, &np) || (nL > 0 && !new_count) || (np > 0 && (!cand || !centres || !cluster_of)))
         return EBVO_ERR_ARG;
-    EBVO_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
-    Slot *sp;
-    if ((rc = host_slot(ctx, &sp)))
-        return rc;
-    Slot &s = *sp;
+    HostCall hc(ctx, HostCall::PAIR_BUFFERS);
+    if (hc.rc)
+        return hc.rc;
+    Slot &s = hc.slot();
     if (nL == 0)
         return EBVO_OK;
-    const size_t npz = (size_t)np;
-    if ((rc = ebvo_grow(ctx, s, s.row_ptr, sizeof(int32_t) * ((size_t)nL + 1))) ||
-        (rc = ebvo_grow(ctx, s, s.cand_cnt, sizeof(int32_t) * ((size_t)nL + 1))) ||
-        (rc = ebvo_grow(ctx, s, s.rc_edges, sizeof(ebvo_edge) * (npz + 1))) ||
-        (rc = ebvo_grow(ctx, s, s.scratch_c, sizeof(ebvo_edge) * (npz + 1))) ||
-        (rc = ebvo_grow(ctx, s, s.pair_left, sizeof(int32_t) * (npz + 1))))
+    const size_t npz = (size_t)np, nLz = (size_t)nL;
+    if (hc.grow(s.row_ptr, sizeof(int32_t) * (nLz + 1)) || hc.grow(s.cand_cnt, sizeof(int32_t) * (nLz + 1)) ||
+        hc.grow(s.rc_edges, sizeof(ebvo_edge) * (npz + 1)) || hc.grow(s.scratch_c, sizeof(ebvo_edge) * (npz + 1)) ||
+        hc.grow(s.pair_left, sizeof(int32_t) * (npz + 1)) || hc.up(s.row_ptr.p, row_ptr, sizeof(int32_t) * (nLz + 1)) ||
+        hc.up(s.rc_edges.p, cand, sizeof(ebvo_edge) * npz))
+        return hc.rc;
+    if (int rc = glue_cluster_enqueue(ctx, s, (const ebvo_edge *)s.rc_edges.p, (const int32_t *)s.row_ptr.p, nL, by_orientation,
+                                      skip_single, (int32_t *)s.cand_cnt.p, (ebvo_edge *)s.scratch_c.p, (int32_t *)s.pair_left.p))
         return rc;
-    hipStream_t st = s.stream;
-    EBVO_HIP(ctx, hipMemcpyAsync(s.row_ptr.p, row_ptr, sizeof(int32_t) * ((size_t)nL + 1), hipMemcpyHostToDevice, st));
-    if (npz)
-        EBVO_HIP(ctx, hipMemcpyAsync(s.rc_edges.p, cand, sizeof(ebvo_edge) * npz, hipMemcpyHostToDevice, st));
-    if ((rc = glue_cluster_enqueue(ctx, s, (const ebvo_edge *)s.rc_edges.p, (const int32_t *)s.row_ptr.p, nL, by_orientation,
-                                   skip_single, (int32_t *)s.cand_cnt.p, (ebvo_edge *)s.scratch_c.p, (int32_t *)s.pair_left.p)))
-        return rc;
-    EBVO_HIP(ctx, hipMemcpyAsync(new_count, s.cand_cnt.p, sizeof(int32_t) * (size_t)nL, hipMemcpyDeviceToHost, st));
-    if (npz)
-    {
-        EBVO_HIP(ctx, hipMemcpyAsync(centres, s.scratch_c.p, sizeof(ebvo_edge) * npz, hipMemcpyDeviceToHost, st));
-        EBVO_HIP(ctx, hipMemcpyAsync(cluster_of, s.pair_left.p, sizeof(int32_t) * npz, hipMemcpyDeviceToHost, st));
-    }
-    EBVO_HIP(ctx, hipStreamSynchronize(st));
-    return EBVO_OK;
+    hc.down(new_count, s.cand_cnt.p, sizeof(int32_t) * nLz);
+    hc.down(centres, s.scratch_c.p, sizeof(ebvo_edge) * npz);
+    hc.down(cluster_of, s.pair_left.p, sizeof(int32_t) * npz);
+    return hc.finish();
 }
 
 extern "C" int ebvo_finalize_pairs(ebvo_ctx *ctx, const ebvo_stereo_calib *calib, const ebvo_edge *left,
@@ -2614,28 +2613,23 @@ extern "C" int ebvo_finalize_pairs(ebvo_ctx *ctx, const ebvo_stereo_calib *calib
 {
     if (!ctx || !calib || n < 0 || (n > 0 && (!left || !right || !out16)))
         return EBVO_ERR_ARG;
-    EBVO_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
-    Slot *sp;
-    if ((rc = host_slot(ctx, &sp)))
-        return rc;
-    Slot &s = *sp;
+    HostCall hc(ctx, HostCall::PAIR_BUFFERS);
+    if (hc.rc)
+        return hc.rc;
+    Slot &s = hc.slot();
     if (n == 0)
         return EBVO_OK;
     const size_t nz = (size_t)n;
-    if ((rc = ebvo_grow(ctx, s, s.scratch_b, sizeof(ebvo_edge) * nz)) || (rc = ebvo_grow(ctx, s, s.scratch_c, sizeof(ebvo_edge) * nz)) ||
-        (rc = ebvo_grow(ctx, s, s.gn_out, sizeof(double) * 16 * nz)))
+    if (hc.grow(s.scratch_b, sizeof(ebvo_edge) * nz) || hc.grow(s.scratch_c, sizeof(ebvo_edge) * nz) ||
+        hc.grow(s.gn_out, sizeof(double) * 16 * nz) || hc.up(s.scratch_b.p, left, sizeof(ebvo_edge) * nz) ||
+        hc.up(s.scratch_c.p, right, sizeof(ebvo_edge) * nz))
+        return hc.rc;
+    if (int rc = refine_finalize_pairs_enqueue(ctx, s, calib->K_left, calib->K_right, calib->R21, calib->T21,
+                                               (const ebvo_edge *)s.scratch_b.p, (const ebvo_edge *)s.scratch_c.p, n,
+                                               (double *)s.gn_out.p))
         return rc;
-    hipStream_t st = s.stream;
-    EBVO_HIP(ctx, hipMemcpyAsync(s.scratch_b.p, left, sizeof(ebvo_edge) * nz, hipMemcpyHostToDevice, st));
-    EBVO_HIP(ctx, hipMemcpyAsync(s.scratch_c.p, right, sizeof(ebvo_edge) * nz, hipMemcpyHostToDevice, st));
-    if ((rc = refine_finalize_pairs_enqueue(ctx, s, calib->K_left, calib->K_right, calib->R21, calib->T21,
-                                            (const ebvo_edge *)s.scratch_b.p, (const ebvo_edge *)s.scratch_c.p, n,
-                                            (double *)s.gn_out.p)))
-        return rc;
-    EBVO_HIP(ctx, hipMemcpyAsync(out16, s.gn_out.p, sizeof(double) * 16 * nz, hipMemcpyDeviceToHost, st));
-    EBVO_HIP(ctx, hipStreamSynchronize(st));
-    return EBVO_OK;
+    hc.down(out16, s.gn_out.p, sizeof(double) * 16 * nz);
+    return hc.finish();
 }
 
 // ---- photometric refinement of the kept matches of a resident pair ---------------------------------------------
@@ -3068,27 +3062,25 @@ extern "C" int ebvo_sift_descriptors(ebvo_ctx *ctx, const uint8_t *img, int h, i
 {
     if (!ctx || !img || n < 0 || (n > 0 && (!edges || !desc)))
         return EBVO_ERR_ARG;
-    EBVO_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
-    Slot *sp;
-    if ((rc = check_size(ctx, h, w)) || (rc = host_slot(ctx, &sp)))
+    if (int rc = check_size(ctx, h, w))
         return rc;
-    Slot &s = *sp;
+    HostCall hc(ctx, HostCall::PAIR_BUFFERS);
+    if (hc.rc)
+        return hc.rc;
+    Slot &s = hc.slot();
     if (n == 0)
         return EBVO_OK;
     const size_t npx = (size_t)h * w, nz = (size_t)n;
-    if ((rc = upload_image(ctx, s, 0, img, h, w, stride)) || (rc = ebvo_grow(ctx, s, s.sift_img, sizeof(float) * 2 * npx)) ||
-        (rc = ebvo_grow(ctx, s, s.scratch_b, sizeof(ebvo_edge) * nz)) ||
-        (rc = ebvo_grow(ctx, s, s.sift_f32, sizeof(float) * 256 * nz)))
-        return rc;
-    EBVO_HIP(ctx, hipMemcpyAsync(s.scratch_b.p, edges, sizeof(ebvo_edge) * nz, hipMemcpyHostToDevice, s.stream));
+    if (hc.image(0, img, h, w, stride) || hc.grow(s.sift_img, sizeof(float) * 2 * npx) || hc.grow(s.scratch_b, sizeof(ebvo_edge) * nz) ||
+        hc.grow(s.sift_f32, sizeof(float) * 256 * nz) || hc.up(s.scratch_b.p, edges, sizeof(ebvo_edge) * nz))
+        return hc.rc;
     float *tmp = (float *)s.sift_img.p, *base = tmp + npx;
+    int rc;
     if ((rc = sift_base_enqueue(ctx, s, s.im[0].img, h, w, w, tmp, base)) ||
         (rc = sift_descriptors_enqueue(ctx, s, base, h, w, (const ebvo_edge *)s.scratch_b.p, n, (float *)s.sift_f32.p, nullptr)))
         return rc;
-    EBVO_HIP(ctx, hipMemcpyAsync(desc, s.sift_f32.p, sizeof(float) * 256 * nz, hipMemcpyDeviceToHost, s.stream));
-    EBVO_HIP(ctx, hipStreamSynchronize(s.stream));
-    return EBVO_OK;
+    hc.down(desc, s.sift_f32.p, sizeof(float) * 256 * nz);
+    return hc.finish();
 }
 
 extern "C" int ebvo_sift_min_distances(ebvo_ctx *ctx, const float *left_desc, int nL, const float *cand_desc,
@@ -3097,34 +3089,30 @@ extern "C" int ebvo_sift_min_distances(ebvo_ctx *ctx, const float *left_desc, in
     int64_t np = 0;
     if (!ctx || check_csr(row_ptr, nL, &np) || (np > 0 && (!left_desc || !cand_desc || !dist)))
         return EBVO_ERR_ARG;
-    EBVO_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
-    Slot *sp;
-    if ((rc = host_slot(ctx, &sp)))
-        return rc;
-    Slot &s = *sp;
+    HostCall hc(ctx, HostCall::PAIR_BUFFERS);
+    if (hc.rc)
+        return hc.rc;
+    Slot &s = hc.slot();
     if (np == 0)
         return EBVO_OK;
     const size_t npz = (size_t)np, nLz = (size_t)nL;
-    if ((rc = ebvo_grow(ctx, s, s.sift_f32, sizeof(float) * 256 * (npz + nLz))) ||
-        (rc = ebvo_grow(ctx, s, s.sift_desc, 256 * (npz + nLz))) ||
-        (rc = ebvo_grow(ctx, s, s.row_ptr, sizeof(int32_t) * (nLz + 1))) ||
-        (rc = ebvo_grow(ctx, s, s.pair_left, sizeof(int32_t) * npz)) || (rc = ebvo_grow(ctx, s, s.sift_dist, sizeof(double) * npz)))
-        return rc;
-    hipStream_t st = s.stream;
+    if (hc.grow(s.sift_f32, sizeof(float) * 256 * (npz + nLz)) || hc.grow(s.sift_desc, 256 * (npz + nLz)) ||
+        hc.grow(s.row_ptr, sizeof(int32_t) * (nLz + 1)) || hc.grow(s.pair_left, sizeof(int32_t) * npz) ||
+        hc.grow(s.sift_dist, sizeof(double) * npz))
+        return hc.rc;
     float *fl = (float *)s.sift_f32.p, *fc = fl + 256 * nLz;
     uint8_t *ul = (uint8_t *)s.sift_desc.p, *uc = ul + 256 * nLz;
-    EBVO_HIP(ctx, hipMemcpyAsync(fl, left_desc, sizeof(float) * 256 * nLz, hipMemcpyHostToDevice, st));
-    EBVO_HIP(ctx, hipMemcpyAsync(fc, cand_desc, sizeof(float) * 256 * npz, hipMemcpyHostToDevice, st));
-    EBVO_HIP(ctx, hipMemcpyAsync(s.row_ptr.p, row_ptr, sizeof(int32_t) * (nLz + 1), hipMemcpyHostToDevice, st));
+    if (hc.up(fl, left_desc, sizeof(float) * 256 * nLz) || hc.up(fc, cand_desc, sizeof(float) * 256 * npz) ||
+        hc.up(s.row_ptr.p, row_ptr, sizeof(int32_t) * (nLz + 1)))
+        return hc.rc;
+    int rc;
     if ((rc = sift_to_u8_enqueue(ctx, s, fl, (int64_t)(256 * (nLz + npz)), ul)) ||
         (rc = match_expand_rows_enqueue(ctx, s, (const int32_t *)s.row_ptr.p, nL, np, (int32_t *)s.pair_left.p)) ||
         (rc = sift_distances_enqueue(ctx, s, ul, uc, (const int32_t *)s.pair_left.p, nullptr, np, EBVO_SIFT_THRESHOLD,
                                      (double *)s.sift_dist.p, nullptr)))
         return rc;
-    EBVO_HIP(ctx, hipMemcpyAsync(dist, s.sift_dist.p, sizeof(double) * npz, hipMemcpyDeviceToHost, st));
-    EBVO_HIP(ctx, hipStreamSynchronize(st));
-    return EBVO_OK;
+    hc.down(dist, s.sift_dist.p, sizeof(double) * npz);
+    return hc.finish();
 }
 
 // ---- input side: cv::undistort ---------------------------------------------------------------------------------
@@ -3133,22 +3121,18 @@ extern "C" int ebvo_undistort(ebvo_ctx *ctx, const uint8_t *img, int h, int w, p
 {
     if (!ctx || !img || !out || !K || n_dist < 0 || n_dist > 5 || (n_dist > 0 && !dist) || out_stride < w)
         return EBVO_ERR_ARG;
-    EBVO_HIP(ctx, hipSetDevice(ctx->device));
-    int rc;
-    Slot *sp;
-    if ((rc = check_size(ctx, h, w)) || (rc = host_slot(ctx, &sp)))
+    if (int rc = check_size(ctx, h, w))
         return rc;
-    Slot &s = *sp;
-    if ((rc = upload_image(ctx, s, 0, img, h, w, stride)) ||
-        (rc = refine_undistort_enqueue(ctx, s, s.im[0].img, w, h, w, K, dist, n_dist, s.im[0].undist_xs, s.im[1].img, w)))
+    HostCall hc(ctx, HostCall::PAIR_BUFFERS);
+    if (hc.rc)
+        return hc.rc;
+    Slot &s = hc.slot();
+    if (hc.image(0, img, h, w, stride))
+        return hc.rc;
+    if (int rc = refine_undistort_enqueue(ctx, s, s.im[0].img, w, h, w, K, dist, n_dist, s.im[0].undist_xs, s.im[1].img, w))
         return rc;
-    if (out_stride == (ptrdiff_t)w)
-        EBVO_HIP(ctx, hipMemcpyAsync(out, s.im[1].img, (size_t)w * h, hipMemcpyDeviceToHost, s.stream));
-    else
-        EBVO_HIP(ctx, hipMemcpy2DAsync(out, (size_t)out_stride, s.im[1].img, (size_t)w, (size_t)w, (size_t)h,
-                                       hipMemcpyDeviceToHost, s.stream));
-    EBVO_HIP(ctx, hipStreamSynchronize(s.stream));
-    return EBVO_OK;
+    hc.down_rows(out, (size_t)out_stride, s.im[1].img, (size_t)w, (size_t)h);
+    return hc.finish();
 }
 
 extern "C" int ebvo_stereo_set_undistort(ebvo_ctx *ctx, const ebvo_undistort_params *p)
@@ -4038,12 +4022,10 @@ extern "C" int ebvo_pose_from_quads(ebvo_ctx *ctx, const ebvo_edge *kf_left, con
                                     const ebvo_stereo_calib *cal, const ebvo_pose_params *p, ebvo_pose_result *res,
                                     uint8_t *inlier, double *quad_geom, int32_t *rank_order)
 {
-    if (!ctx || n_kf < 0 || !row_ptr || (n_kf > 0 && (!kf_left || !kf_right)) || !pose_args_ok(cal, p, res) || row_ptr[0] != 0)
+    int64_t np = 0;
+    if (!ctx || (n_kf > 0 && (!kf_left || !kf_right)) || !pose_args_ok(cal, p, res) || check_csr(row_ptr, n_kf, &np))
         return EBVO_ERR_ARG;
-    for (int i = 0; i < n_kf; ++i)
-        if (row_ptr[i + 1] < row_ptr[i])
-            return EBVO_ERR_ARG;
-    const int n = row_ptr[n_kf];
+    const int n = (int)np;
     if (n > 0 && (!cf_left || !cf_right))
         return EBVO_ERR_ARG;
     Slot &s = *ctx->slots[0];
@@ -4081,105 +4063,6 @@ static bool pose_cascade_args_ok(const ebvo_pose_params *p, int n_runs, const eb
 
 // Host quads of a GT call, checked, counted and uploaded into slot 0's own pose buffer.  n_listed / n_sel: listed rows and
 // selected quads, counted here; upload = false: only check and count.
-// ---- host-array calls: copies between a caller's arrays and a carved device buffer ----------------------------------------
-// Nothing is copied for an empty array or a null host pointer (an optional argument the caller left out).
-static int copy_up(ebvo_ctx *ctx, hipStream_t st, void *dst_dev, const void *src_host, size_t bytes)
-{
-    if (bytes && src_host)
-        EBVO_HIP(ctx, hipMemcpyAsync(dst_dev, src_host, bytes, hipMemcpyHostToDevice, st));
-    return EBVO_OK;
-}
-
-static int copy_down(ebvo_ctx *ctx, hipStream_t st, void *dst_host, const void *src_dev, size_t bytes)
-{
-    if (bytes && dst_host)
-        EBVO_HIP(ctx, hipMemcpyAsync(dst_host, src_dev, bytes, hipMemcpyDeviceToHost, st));
-    return EBVO_OK;
-}
-
-// The host-array calls run on slot 0's stream with a buffer of their own (host_up): the slot's pair, its results and its
-// armed state stay as they are (unlike host_slot(), whose callers reuse the pair's buffers).
-static int gt_host_slot(ebvo_ctx *ctx, Slot **out)
-{
-    Slot &s = *ctx->slots[0];
-    if (s.in_flight || s.fin_in_flight || s.tq_in_flight)
-    {
-        ctx->last_error = "slot 0 has submitted work in flight; call ebvo_stereo_wait / ebvo_stereo_finalize_wait / ebvo_temporal_match_wait first";
-        return EBVO_ERR_STATE;
-    }
-    *out = &s;
-    return EBVO_OK;
-}
-
-// One host-array call.  It takes slot 0, carves the slot's staging buffer and copies on the slot's stream.  The copies read and
-// write the caller's arrays and the function's locals, so none of them may outlive the call: finish() waits for them, and the
-// destructor does on every return that did not get there.  A local that down() writes into is declared before this object.
-struct HostCall
-{
-    ebvo_ctx *ctx;
-    Slot *s = nullptr;
-    int rc;               // the slot's state first, then the first failure of stage() or of a copy; every helper returns it
-    bool pending = false; // copies were enqueued since the last finish()
-
-    explicit HostCall(ebvo_ctx *c) : ctx(c), rc(gt_host_slot(c, &s)) {}
-    HostCall(const HostCall &) = delete;
-    HostCall &operator=(const HostCall &) = delete;
-    ~HostCall()
-    {
-        if (pending)
-            (void)hipStreamSynchronize(s->stream);
-    }
-
-    Slot &slot() const { return *s; }
-    // the staging buffer holds L.total() bytes; at<T>(offset) is an array of it
-    int stage(const Carve &L)
-    {
-        if (rc)
-            return rc;
-        const hipError_t e = hipSetDevice(ctx->device);
-        if (e != hipSuccess)
-            return rc = ebvo_fail_hip(ctx, e, "hipSetDevice(ctx->device)", __FILE__, __LINE__);
-        return rc = ebvo_grow(ctx, *s, s->host_up, L.total(), false);
-    }
-    template <class T> T *at(size_t offset) const { return (T *)((char *)s->host_up.p + offset); }
-
-    int up(void *dst_dev, const void *src_host, size_t bytes)
-    {
-        pending = true;
-        return rc ? rc : (rc = copy_up(ctx, s->stream, dst_dev, src_host, bytes));
-    }
-    // `rows` rows of row_bytes each, src_pitch bytes apart on the host, packed on the device
-    int up_rows(void *dst_dev, const void *src_host, size_t row_bytes, size_t src_pitch, size_t rows)
-    {
-        pending = true;
-        if (rc)
-            return rc;
-        const hipError_t e = hipMemcpy2DAsync(dst_dev, row_bytes, src_host, src_pitch, row_bytes, rows, hipMemcpyHostToDevice, s->stream);
-        return e == hipSuccess ? rc : (rc = ebvo_fail_hip(ctx, e, "hipMemcpy2DAsync(dst_dev, src_host)", __FILE__, __LINE__));
-    }
-    int down(void *dst_host, const void *src_dev, size_t bytes)
-    {
-        pending = true;
-        return rc ? rc : (rc = copy_down(ctx, s->stream, dst_host, src_dev, bytes));
-    }
-    int fill(void *dst_dev, int byte, size_t bytes)
-    {
-        if (rc || !bytes)
-            return rc;
-        const hipError_t e = hipMemsetAsync(dst_dev, byte, bytes, s->stream);
-        return e == hipSuccess ? rc : (rc = ebvo_fail_hip(ctx, e, "hipMemsetAsync(dst_dev, byte, bytes, stream)", __FILE__, __LINE__));
-    }
-    // wait for the stream whatever happened before; an earlier failure comes before the wait's own
-    int finish()
-    {
-        pending = false;
-        const hipError_t e = hipStreamSynchronize(s->stream);
-        if (!rc && e != hipSuccess)
-            rc = ebvo_fail_hip(ctx, e, "hipStreamSynchronize(stream)", __FILE__, __LINE__);
-        return rc;
-    }
-};
-
 struct PoseHostQuads
 {
     const ebvo_edge *kfL = nullptr, *kfR = nullptr, *cfL = nullptr, *cfR = nullptr;
@@ -4193,12 +4076,10 @@ static int pose_host_quads_check(ebvo_ctx *ctx, const ebvo_edge *kf_left, const 
                                  const ebvo_edge *cf_left, const ebvo_edge *cf_right, const uint8_t *row_listed, const uint8_t *kf_is_tp,
                                  PoseHostQuads *q)
 {
-    if (!ctx || n_kf < 0 || !row_ptr || (n_kf > 0 && (!kf_left || !kf_right)) || row_ptr[0] != 0)
+    int64_t np = 0;
+    if (!ctx || (n_kf > 0 && (!kf_left || !kf_right)) || check_csr(row_ptr, n_kf, &np))
         return EBVO_ERR_ARG;
-    for (int i = 0; i < n_kf; ++i)
-        if (row_ptr[i + 1] < row_ptr[i])
-            return EBVO_ERR_ARG;
-    q->n = row_ptr[n_kf];
+    q->n = (int)np;
     if (q->n > 0 && (!cf_left || !cf_right))
         return EBVO_ERR_ARG;
     q->n_listed = q->n_sel = 0;
@@ -4457,7 +4338,6 @@ extern "C" int ebvo_temporal_refine_pose(ebvo_ctx *ctx, int slot, const ebvo_ste
 }
 
 // ---- alignment of the pose to the current frame's TOED edges (align_kernels.hip) ---------------------------------------
-static int gt_host_slot(ebvo_ctx *ctx, Slot **out);
 extern "C" void ebvo_align_default_params(ebvo_align_params *p)
 {
     if (!p)
