@@ -974,6 +974,21 @@ __device__ inline void sample_row(const uint8_t *__restrict__ img, int h, int w,
     const int i = row - 3;
     if (__all(!active || patch_inside(h, w, ex, ey)))
     {
+        // Coordinates of the row's seven samples, x_j = cs * i - sn * j + cx and y_j = sn * i + cs * j + cy (j = -3 .. 3), from
+        // shared terms: cs * i and sn * i once, the products P_m = sn * m and Q_m = cs * m for m = 1, 2, 3 once.  Bit for bit the
+        // expressions above: sn * (-m) = -(sn * m) and a - (-b) = a + b in IEEE arithmetic, so column -m takes
+        // (cs * i + P_m) + cx and (sn * i - Q_m) + cy.  The compiler finds those six shared products by itself; what it must
+        // keep is column j = 0, cs * i - sn * 0 + cx: the product is a signed zero, the difference is cs * i except that a
+        // zero cs * i may change its sign -- and any zero vanishes in the last addition BECAUSE cx AND cy ARE NOT ZERO here
+        // (patch_inside holds for every sampling lane: ex, ey >= 9.3 and |5 sn|, |5 cs| <= 5, so cx, cy >= 4.3).  So column 0 is
+        // cs * i + cx, sn * i + cy: two multiplications and two additions fewer per row.  sample_row_border keeps the
+        // expression as written (its cx, cy can be zero).
+        const double ci = cs * (i), si = sn * (i);
+        const double P[4] = {0.0, sn * 1, sn * 2, sn * 3}, Q[4] = {0.0, cs * 1, cs * 2, cs * 3};
+        auto coord = [&](int j, double &x, double &y) {
+            x = j > 0 ? (ci - P[j]) + cx : j < 0 ? (ci + P[-j]) + cx : ci + cx;
+            y = j > 0 ? (si + Q[j]) + cy : j < 0 ? (si - Q[-j]) + cy : si + cy;
+        };
         // the NaN rule of an integer coordinate (measure zero) is applied once per row, and only when some lane met it: no
         // per-sample selects on the common path
         bool all_ok = true;
@@ -982,9 +997,8 @@ __device__ inline void sample_row(const uint8_t *__restrict__ img, int h, int w,
 #pragma unroll
             for (int c = 0; c < 7; ++c)
             {
-                const int j = c - 3;
-                const double x = cs * (i)-sn * (j) + cx;
-                const double y = sn * (i) + cs * (j) + cy;
+                double x, y;
+                coord(c - 3, x, y);
                 bool ok;
                 p[c] = (float)(PIX2 ? bilinear_inside2_raw(pix2, pitch, x, y, ok) : bilinear_inside_raw(img, pitch, x, y, ok));
                 all_ok = all_ok && ok;
@@ -997,9 +1011,8 @@ __device__ inline void sample_row(const uint8_t *__restrict__ img, int h, int w,
 #pragma unroll
                 for (int c = 0; c < 7; ++c)
                 {
-                    const int j = c - 3;
-                    const double x = cs * (i)-sn * (j) + cx;
-                    const double y = sn * (i) + cs * (j) + cy;
+                    double x, y;
+                    coord(c - 3, x, y);
                     if (__builtin_amdgcn_fract(x) == 0.0 || __builtin_amdgcn_fract(y) == 0.0)
                         p[c] = __builtin_nanf("");
                 }
@@ -1235,7 +1248,11 @@ __global__ void expand_rows_kernel(const int32_t *__restrict__ row_ptr, DevN nLd
 //                the normalised rows are the same floats, the reductions the same additions.
 constexpr int BANK_SIDE = 56;   // floats per side of a bank entry: 7 rows x 8 floats (224 B, 16-byte aligned rows)
 constexpr int BANK_EDGE = 112;  // floats per edge (448 B)
-constexpr int NCC_NW = 4;       // left edges per wave (one sampling round: four 16-lane groups)
+#ifndef EBVO_NCC_NW
+#define EBVO_NCC_NW 8 // 4 or 8 (8 measured ahead); the other builds with make EXTRA=-DEBVO_NCC_NW=4
+#endif
+constexpr int NCC_NW = EBVO_NCC_NW; // left edges per wave (a sampling round is four 16-lane groups: NCC_NW / 4 rounds a tile)
+constexpr int NCC_EL_SHIFT = 29; // a preloaded column index carries its pair's local row above this bit (ncc_tile_kernel)
 constexpr int NCC_WPE = 4;      // waves per SIMD the tile kernel is compiled for (the prefetched loads need the registers)
 
 __device__ inline void right_bank_body(const uint8_t *__restrict__ img, const uint16_t *__restrict__ pix2, int h, int w, int pitch,
@@ -1410,7 +1427,8 @@ __global__ __launch_bounds__(256, WPE) void ncc_tile_kernel(const uint8_t *__res
                                                        double *__restrict__ sims, double *__restrict__ best,
                                                        uint8_t *__restrict__ keep, int32_t *__restrict__ match_part)
 {
-    static_assert(NW == 4, "one sampling round: four 16-lane groups, one per left edge of the tile");
+    static_assert(NW == 4 || NW == 8, "NW / 4 sampling rounds of four 16-lane groups, one group per left edge");
+    constexpr int ROUNDS = NW / 4;
     __shared__ __attribute__((aligned(16))) float s_left_all[4][NW * 2 * 7 * 8];
     __shared__ int s_mc;
     const int nL = devn(nLd);
@@ -1438,8 +1456,8 @@ __global__ __launch_bounds__(256, WPE) void ncc_tile_kernel(const uint8_t *__res
     struct Head
     {
         int rp_l;      // lane t <= NW: row_ptr[e0 + min(t, rows)], clamped to the capacity of the pair buffers
-        double2 xy, sc; // the lane's left edge (16-lane group el = lane >> 4) and sin / cos of its orientation
-    };
+        double2 xy, sc; // the lane's left edge of the first sampling round (16-lane group el = lane >> 4) and sin / cos of its
+    };                  // orientation; a later round's edge is loaded while the first round is sampled
     auto load_head = [&](int tile) {
         Head hd;
         const int e0 = tile * NW;
@@ -1455,6 +1473,23 @@ __global__ __launch_bounds__(256, WPE) void ncc_tile_kernel(const uint8_t *__res
         hd.xy = *reinterpret_cast<const double2 *>(&L[ec].x);
         hd.sc = scL[ec];
         return hd;
+    };
+    // one sampling round: left edges e0 + 4 rnd .. e0 + 4 rnd + 3 of the tile, 16 lanes each, into their slots of s_left
+    auto sample_round = [&](int rnd, int rows, const double2 &xy, const double2 &sc) {
+        const int el = rnd * 4 + (lane >> 4);
+        const bool active = el < rows && row < 7;
+        float p[7], nr[7];
+#pragma unroll
+        for (int c = 0; c < 7; ++c)
+            p[c] = 0.0f;
+        sample_row<true>(imgL, h, w, pitch, xy.x, xy.y, sc.x, sc.y, side, row, p, active, pix2L);
+        const bool sent = normalise_rows(active, p, nr);
+        if (active)
+        {
+            float4 *dst = reinterpret_cast<float4 *>(&s_left[((el * 2 + side) * 7 + row) * 8]);
+            dst[0] = make_float4(nr[0], nr[1], nr[2], nr[3]);
+            dst[1] = make_float4(nr[4], nr[5], nr[6], sent ? 1.0f : 0.0f);
+        }
     };
     int tile = t_begin + slot * 4 + wave;
     Head cur{};
@@ -1472,27 +1507,26 @@ __global__ __launch_bounds__(256, WPE) void ncc_tile_kernel(const uint8_t *__res
         const int k0 = rps[0], k1 = rps[NW]; // lanes beyond `rows` hold rp[rows]
         // the tile's first 128 column indices, two per lane (an average tile has 18 pairs; one with more than 128 reads them
         // where it needs them)
-        int ci_l = 0, ci_h = 0;
+        unsigned ci_l = 0, ci_h = 0;
         if (k0 + lane < k1)
-            ci_l = col_idx[k0 + lane];
+            ci_l = (unsigned)col_idx[k0 + lane];
         if (k0 + 64 + lane < k1)
-            ci_h = col_idx[k0 + 64 + lane];
-        // phase 1: the tile's left patches (src/Stereo_Matches.cpp:578), normalised as get_patch_similarity does
+            ci_h = (unsigned)col_idx[k0 + 64 + lane];
+        // phase 1: the tile's left patches (src/Stereo_Matches.cpp:578), normalised as get_patch_similarity does, four edges
+        // a round.  The edge of a later round is requested before the first round is sampled and arrives behind it; a round
+        // without edges (the last tile of the list) is skipped, wave-uniformly.
         {
-            const int el = lane >> 4;
-            const bool active = el < rows && row < 7;
-            float p[7], nr[7];
-#pragma unroll
-            for (int c = 0; c < 7; ++c)
-                p[c] = 0.0f;
-            sample_row<true>(imgL, h, w, pitch, cur.xy.x, cur.xy.y, cur.sc.x, cur.sc.y, side, row, p, active, pix2L);
-            const bool sent = normalise_rows(active, p, nr);
-            if (active)
+            double2 xy2 = cur.xy, sc2 = cur.sc;
+            if (ROUNDS > 1 && rows > 4)
             {
-                float4 *dst = reinterpret_cast<float4 *>(&s_left[((el * 2 + side) * 7 + row) * 8]);
-                dst[0] = make_float4(nr[0], nr[1], nr[2], nr[3]);
-                dst[1] = make_float4(nr[4], nr[5], nr[6], sent ? 1.0f : 0.0f);
+                const int el = 4 + (lane >> 4);
+                const int ec = (el < rows && row < 7) ? e0 + el : 0;
+                xy2 = *reinterpret_cast<const double2 *>(&L[ec].x);
+                sc2 = scL[ec];
             }
+            sample_round(0, rows, cur.xy, cur.sc);
+            if (ROUNDS > 1 && rows > 4)
+                sample_round(1, rows, xy2, sc2);
         }
         const int next_tile = tile + slots * 4;
         Head nxt{};
@@ -1513,17 +1547,37 @@ __global__ __launch_bounds__(256, WPE) void ncc_tile_kernel(const uint8_t *__res
         const int own_u = ((r8l >> 1) ^ (r8l >> 2)) & 1, own_v = (r8l ^ (r8l >> 2)) & 1;
         const int row7 = r8l < 7 ? r8l : 6; // the eighth lane reads row 6 again (in bounds) and contributes zeros
         const int off_a = own_v * BANK_SIDE + row7 * 8, off_b = (own_v ^ 1) * BANK_SIDE + row7 * 8;
+        const float *la_base = s_left + (own_u * 7 + row7) * 8, *lb_base = s_left + ((own_u ^ 1) * 7 + row7) * 8;
+        // local row of pair k: the number of row starts rp[1 .. NW - 1] at or below k (a row start beyond `rows` is k1, above
+        // every pair of the tile)
+        auto local_row = [&](int k) {
+            int el = 0;
+#pragma unroll
+            for (int t = 1; t < NW; ++t)
+                el += k >= rps[t] ? 1 : 0;
+            return el;
+        };
+        // A preloaded pair's local row is found HERE, once per pair by the lane that holds its column index, and travels in the
+        // index's top three bits: the search is paid per 64 pairs instead of per step of 8.  (A right-edge index stays below
+        // 2^29: the host refuses a larger edge capacity.)
+        if (k1 - k0 <= 128)
+        {
+            ci_l |= (unsigned)local_row(k0 + lane) << NCC_EL_SHIFT;
+            if (k1 - k0 > 64)
+                ci_h |= (unsigned)local_row(k0 + 64 + lane) << NCC_EL_SHIFT;
+        }
         // bank rows of the eight pairs starting at kb: lanes past the end read the last pair again and store nothing.  The eight
         // pairs lie in one 64-pair chunk (kb - k0 is a multiple of 8), so which of the two index registers holds them is
-        // wave-uniform; `preloaded` is false only for a tile of more than 128 pairs.
-        auto bank_rows = [&](auto preloaded, int kb, float4 &a0, float4 &a1, float4 &b0, float4 &b1) {
+        // wave-uniform; `preloaded` is false only for a tile of more than 128 pairs.  `pk` is the packed index (preloaded only).
+        auto bank_rows = [&](auto preloaded, int kb, unsigned &pk, float4 &a0, float4 &a1, float4 &b0, float4 &b1) {
             const int k = kb + (lane >> 3);
             const int kc = k < k1 ? k : k1 - 1;
             int ri;
             if (decltype(preloaded)::value)
             {
                 const int kbc = kb < k1 ? kb : k1 - 1;
-                ri = __shfl(kbc - k0 < 64 ? ci_l : ci_h, (kc - k0) & 63);
+                pk = __shfl(kbc - k0 < 64 ? ci_l : ci_h, (kc - k0) & 63);
+                ri = (int)(pk & ((1u << NCC_EL_SHIFT) - 1));
             }
             else
                 ri = col_idx[kc];
@@ -1535,17 +1589,14 @@ __global__ __launch_bounds__(256, WPE) void ncc_tile_kernel(const uint8_t *__res
             b0 = rb4[0];
             b1 = rb4[1];
         };
-        auto score = [&](int kb, const float4 &a0, const float4 &a1, const float4 &b0, const float4 &b1) {
+        auto score = [&](auto preloaded, int kb, unsigned pk, const float4 &a0, const float4 &a1, const float4 &b0,
+                         const float4 &b1) {
             const int k = kb + (lane >> 3);
             const bool valid = k < k1;
             const int kc = valid ? k : k1 - 1;
-            // local row of pair k: the number of row starts rp[1 .. rows - 1] at or below k
-            int el = 0;
-#pragma unroll
-            for (int t = 1; t < NW; ++t)
-                el += (t < rows && kc >= rps[t]) ? 1 : 0;
-            const float4 *la4 = reinterpret_cast<const float4 *>(&s_left[((el * 2 + own_u) * 7 + row7) * 8]);
-            const float4 *lb4 = reinterpret_cast<const float4 *>(&s_left[((el * 2 + (own_u ^ 1)) * 7 + row7) * 8]);
+            const int el = decltype(preloaded)::value ? (int)(pk >> NCC_EL_SHIFT) : local_row(kc);
+            const float4 *la4 = reinterpret_cast<const float4 *>(la_base + el * (2 * 7 * 8));
+            const float4 *lb4 = reinterpret_cast<const float4 *>(lb_base + el * (2 * 7 * 8));
             const float4 p0 = la4[0], p1 = la4[1], m0 = lb4[0], m1 = lb4[1];
             const float ra[7] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z};
             const float rb[7] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z};
@@ -1599,14 +1650,15 @@ __global__ __launch_bounds__(256, WPE) void ncc_tile_kernel(const uint8_t *__res
         // wait for every load in flight, the prefetched ones included.
         auto score_tile = [&](auto preloaded) {
             float4 xa0, xa1, xb0, xb1, ya0, ya1, yb0, yb1;
-            bank_rows(preloaded, k0, xa0, xa1, xb0, xb1);
+            unsigned xk = 0, yk = 0;
+            bank_rows(preloaded, k0, xk, xa0, xa1, xb0, xb1);
             for (int kb = k0; kb < k1; kb += 16)
             {
-                bank_rows(preloaded, kb + 8, ya0, ya1, yb0, yb1);
-                score(kb, xa0, xa1, xb0, xb1);
-                bank_rows(preloaded, kb + 16, xa0, xa1, xb0, xb1);
+                bank_rows(preloaded, kb + 8, yk, ya0, ya1, yb0, yb1);
+                score(preloaded, kb, xk, xa0, xa1, xb0, xb1);
+                bank_rows(preloaded, kb + 16, xk, xa0, xa1, xb0, xb1);
                 if (kb + 8 < k1) // wave-uniform
-                    score(kb + 8, ya0, ya1, yb0, yb1);
+                    score(preloaded, kb + 8, yk, ya0, ya1, yb0, yb1);
             }
         };
         if (k1 - k0 > 128)
@@ -2398,6 +2450,11 @@ int match_ncc_resident_enqueue(ebvo_ctx *ctx, Slot &s, int h, int w, int cap_edg
         return rc;
     if (ctx->stop_stage == 11)
         return EBVO_OK;
+    if (cap_edges >= (1 << NCC_EL_SHIFT)) // ncc_tile_kernel carries a pair's local row above its right-edge index
+    {
+        ctx->last_error = "edge capacity beyond what the NCC tile kernel indexes";
+        return EBVO_ERR_ARG;
+    }
     {
         ProfScope ps(ctx, s, K_NCC_PAIRS);
         int nblk = (int)blocks_for(cap_edges, NCC_NW * 4, EBVO_MATCH_PARTS);
@@ -2421,8 +2478,11 @@ int match_ncc_resident_enqueue(ebvo_ctx *ctx, Slot &s, int h, int w, int cap_edg
         nblk = nblk < 8 ? 8 : (nblk & ~7); // the XCD-aware order needs a multiple of 8 (tiles are walked grid-stride)
         nblk = nblk < EBVO_MATCH_PARTS ? nblk : EBVO_MATCH_PARTS;
         s.n_match_part = nblk;
-        // NW = 4 left edges per wave, at most 5 waves per SIMD: measured best of {4, 8, 16} x {4, 5, 6, 8} (a bigger tile
-        // serialises more sampling rounds in one wave; a higher occupancy target spills)
+        // NW = 8 left edges per wave, compiled for four waves per SIMD.  Before the round-4 rewrite NW = 4 was the best of {4, 8, 16},
+        // the kernel alone and latency-bound; with six pairs in flight the pair rate follows the instruction count, and a tile of eight
+        // pays the per-tile bookkeeping half as often and fills its steps of eight pairs better: measured again in round 9,
+        // parent / NW = 4 / NW = 8 alternating, 3708 / 3749 / 3792 pairs/s with ranges apart (DESIGN 5.3 item 9,
+        // profiles/r09_ab_headline.txt).  A higher occupancy target spills.
         for (int rep = 0; rep < ((ctx->repeat_mask & 8) ? 2 : 1); ++rep)
             hipLaunchKernelGGL((ncc_tile_kernel<NCC_NW, NCC_WPE>), dim3(nblk), dim3(256), 0, s.stream, ncc_img(s, iL),
                                (const uint16_t *)s.im[iL].pix2, h, w, w, (const ebvo_edge *)s.im[iL].edges,
