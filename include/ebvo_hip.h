@@ -1059,7 +1059,9 @@ int ebvo_depth_carry(ebvo_ctx *ctx, const ebvo_edge *kf_left, const ebvo_edge *k
  * computed first, into buffers of the call's own, from the old keyframe's mates, its resident state and the slot's final
  * mates; then the slot is installed as ebvo_temporal_set_keyframe installs it (the same store, the same bits); then the
  * carried state is installed, so that the new keyframe is NOT at the prior.  Needs a keyframe besides what
- * ebvo_temporal_set_keyframe needs; its refusals otherwise (nothing in flight in any slot).  An old keyframe still at the prior
+ * ebvo_temporal_set_keyframe needs; its refusals otherwise: EBVO_ERR_STATE while the CALLED slot has work in flight (a pair,
+ * a finalisation or a match) and while ANY slot has a temporal match in flight.  A stereo pair or a finalisation in flight in
+ * another slot does not refuse it: a frame loop promotes while the next pair's chain runs.  An old keyframe still at the prior
  * has nothing to carry: the call then is ebvo_temporal_set_keyframe, the record holds n_old and n_new and zeros, and the new
  * keyframe is at the prior.  On any refusal the old keyframe and its state stay as they were.  Pending priors are dropped and
  * the keyframe generation is bumped, as by ebvo_temporal_set_keyframe.  The decision to switch stays the caller's. */
